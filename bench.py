@@ -18,21 +18,26 @@ ONE kernel launch (16 x 4096^2 RGBA8 = 1 GiB of source per step, well past the 2
 really come from HBM).  Multi-GPU: every rank encodes its own textures (independent textures -> no data-path
 collective).  The timed region is exactly K such steps between barriers -> `value`.
 
-After it, for N > 1, a second region of K steps times encode -> RCCL gather of the compressed output to rank 0
+With --full, after it, for N > 1, a second region of K steps times encode -> RCCL gather of the compressed output to rank 0
 ("wall time from first launch to completion of the RCCL gather on rank 0"), with the gather of batch k on
 a second stream overlapping the encode of batch k+1 -> `value_with_gather`, `gather_ms` (one un-overlapped gather).
 
-`configs` (same line): after the c2 legs the OTHER BASELINE configurations -- c3 (DXT5 8192^2), c4 (ETC1 kSmallerError, 1024 x
+`configs` (same line, --full): after the c2 legs the OTHER BASELINE configurations -- c3 (DXT5 8192^2), c4 (ETC1 kSmallerError, 1024 x
 1024^2 over the ranks), c5 (PVRTC 2bpp 4096^2) -- run a handful of timed steps each, with their own roofline and parity.
-`slab` (same line): ONE large image (4096^2 / 8192^2 DXT5 / 16384^2) split into block-row slabs over the ranks
+`slab` (same line, --full): ONE large image (4096^2 / 8192^2 DXT5 / 16384^2) split into block-row slabs over the ranks
 (sharding.slab_geometry, reference compressor4x4_helper.h:202-214: row-major blocks -> contiguous output ranges), strong
 scaling, plus the gather of the slabs into rank 0's final buffer.  `--shard slab` makes that the headline line instead.
 
-One JSON line is printed by rank 0.  Besides the driver contract it carries
-  roofline     -- algorithmic bytes per launch / mean launch duration (HIP events on the launch stream); `bound` says
-                  which unit limits the kernel; `hbm_frac` and (where a matching PMC profile is committed) `valu_frac`
+One JSON line is printed by rank 0.  A plain run does only what the headline needs: set-up, preconditioning and warm-up,
+the K timed steps, and the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the config and
+the roofline of the timed launches).  `--full` adds every other leg after the headline measurement: the parity check,
+the encode -> gather region (N > 1) and everything below, the `configs` / `slab` / `next_rows` legs of the default line, and
+  roofline     -- HBM traffic and VALU fraction counted in the run (rocprofv3 --pmc child passes), clock under load
   cpu_baseline -- the oracle port (oracle/ic_oracle.c) timed on this host's cores on a bounded sample
   host_api     -- the host-buffer drop-in (icamd_compress, H2D + kernel + D2H), never the reported `value`
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (the compressed blocks) to DIR as float32 .npy, so that
+two builds can be compared output for output: the inputs are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -97,6 +102,12 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="textures per rank per step (one launch)")
     ap.add_argument("--content", default="noise", choices=["noise", "smooth", "flat"])
     ap.add_argument("--etc-strategy", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, run every other leg too (parity, gather, roofline counters, CPU baseline, host "
+                         "API, sustained, single image, next rows, configs, slab); the --no-* options below drop single legs of it. "
+                         "Without it a run times the K steps and prints the line. (--shard slab always runs its own legs.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the compressed blocks of the last timed step to DIR as float32 .npy (a fixed sample where large)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the encode->gather region")
     ap.add_argument("--no-next-rows", action="store_true",
                     help="default line, N = 1: skip the `next_rows` legs (decoders, Downsample, DXT1->ETC1 transcode of 16 x 4096^2)")
@@ -132,6 +143,8 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: debugging only (several ranks sharing one GPU; the gather is staged through the host)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.shard == "slab":
+        ap.error("--dump-outputs writes the headline steps' output; --shard slab has no such steps")
     preset = CONFIGS[args.config or "c2"] if (args.config or not (args.workload or args.size or args.batch)) else {}
     args.preset = (args.config or "c2") if preset else None
     args.workload = args.workload or preset.get("workload", "dxt1_rgba8")
@@ -184,6 +197,26 @@ def make_batch(torch, content, batch, size, comps, device, seed, height=None, ro
     noisy = noisy.repeat_interleave(16, dim=1).repeat_interleave(16, dim=2)
     noise = torch.randint(0, 256, img.shape, dtype=torch.uint8, device=device, generator=g)
     return torch.where(noisy, noise, img)[:, :h, :size].contiguous()
+
+
+DUMP_WORDS = 1 << 20  # 8-byte words written by --dump-outputs over all ranks: <= 32 MiB of float32 blocks + 8 MiB of indices
+
+
+def dump_outputs(torch, out_dir, out, rank, world):
+    """--dump-outputs: `out` (textures x encoded bytes, uint8), what the timed path handed its caller, as float32.  Every
+    encoded texture is a whole number of 8-byte words (blocks are 8 or 16 bytes), so the output is viewed as words; where it
+    holds more than this rank's share of DUMP_WORDS, a fixed sample of them (numpy seed 0, sorted) is written, and beside it
+    the flat word indices of the sample (float64: exact below 2^53).  Files carry a rank suffix when there are several ranks."""
+    import numpy as np
+    words = out.reshape(-1, 8)
+    n = words.shape[0]
+    keep = max(1, DUMP_WORDS // world)
+    idx = np.arange(n) if n <= keep else np.unique(np.random.default_rng(0).integers(0, n, keep))
+    sample = words.index_select(0, torch.from_numpy(idx).to(words.device)).cpu().numpy()
+    suffix = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "blocks%s.npy" % suffix), sample.astype(np.float32))
+    np.save(os.path.join(out_dir, "block_word_index%s.npy" % suffix), idx.astype(np.float64))
 
 
 def cpu_baseline(T, codec, comps, size, strategy, host_img):
@@ -1373,6 +1406,17 @@ def main():
         result["roofline"] = {"bound": limiting_unit, "achieved": round(a0, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                               "frac": round(a0 / HBM_PEAK_GBPS, 4), "traffic": t0_, "traffic_source": src0_,
                               "kernel": pkg.kernel_name(codec, comps), "kernel_ms": round(kernel_ms, 4)}
+        result["library"] = {"path": os.path.relpath(pkg.LIB_PATH, ROOT), "overridden": bool(pkg.LIB_OVERRIDDEN),
+                             "version": pkg.lib().icamd_version().decode()}
+    if args.dump_outputs:  # outs[0] holds the last timed step's output (every timed step writes it; synchronised above)
+        dump_outputs(torch, args.dump_outputs, outs[0], rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- watchdog: the contract's measurement is done; nothing below may cost the run its line.  Exceptions are caught leg by
     # leg, but a collective that HANGS (the multi-rank paths have only ever run over gloo / one forced RCCL rank) would hold the
     # line back until the launcher's own limit.  After --watchdog-seconds rank 0 prints what it has, every rank exits 0.
@@ -1520,8 +1564,6 @@ def main():
         if world == 1 and args.preset == "c2" and args.content == "noise" and not args.no_next_rows:
             ctx.leg = "next_rows"
             result["next_rows"] = next_rows_leg()
-        result["library"] = {"path": os.path.relpath(pkg.LIB_PATH, ROOT), "overridden": bool(pkg.LIB_OVERRIDDEN),
-                             "version": pkg.lib().icamd_version().decode()}
     # ---- the other BASELINE configurations and the one-large-image slab legs, in the same line (every rank takes part).
     # Only the default line (preset c2, no overrides) carries them; each leg frees its buffers before the next.
     default_line = args.preset == "c2" and args.content == "noise"

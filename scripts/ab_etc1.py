@@ -1,6 +1,6 @@
 import os, sys, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--no-cpu-baseline", "--no-host-api", "--no-sustained", "--no-single-image", "--no-extra-configs", "--no-slab", "--steps", "10", "--warmup", "3", "--precondition-seconds", "0.3"]
+COMMON = ["--full", "--no-cpu-baseline", "--no-host-api", "--no-sustained", "--no-single-image", "--no-extra-configs", "--no-slab", "--steps", "10", "--warmup", "3", "--precondition-seconds", "0.3"]
 for rnd in range(2):
     for lib in sys.argv[1:]:
         env = dict(os.environ, ICAMD_ALLOW_LIB_OVERRIDE="1", ICAMD_LIB_PATH=os.path.join(ROOT, lib))

@@ -3,7 +3,7 @@
 usage: python scripts/ab_etc1_xcd.py <lib> <lib> ..."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--no-cpu-baseline", "--no-host-api", "--no-sustained", "--no-single-image", "--no-extra-configs", "--no-slab", "--no-next-rows",
+COMMON = ["--full", "--no-cpu-baseline", "--no-host-api", "--no-sustained", "--no-single-image", "--no-extra-configs", "--no-slab", "--no-next-rows",
           "--steps", "20", "--warmup", "3", "--precondition-seconds", "0.3"]
 CASES = (["--config", "c4"], ["--config", "c4", "--content", "smooth"], ["--config", "c4", "--content", "flat"],
          ["--workload", "etc1_rgb888", "--content", "smooth"], ["--workload", "etc1_rgb888", "--etc-strategy", "3"])

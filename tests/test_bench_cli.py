@@ -38,6 +38,37 @@ def test_explicit_flags_leave_the_presets():
         assert unit in ("hbm", "valu") and bpp == comps + {0: 0.5, 1: 1.0, 2: 0.5, 3: 0.25, 4: 0.5}[codec]  # 4: PVRTC 4 bpp (extension)
 
 
+def test_full_and_dump_outputs_options():
+    b = _bench()
+    a = b.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    import pytest
+    with pytest.raises(SystemExit):
+        b.parse_args(["--shard", "slab", "--dump-outputs", "out"])
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(monkeypatch, tmp_path):
+    """Small outputs are written whole; larger ones as the same seeded sample of 8-byte words on every run, within the
+    budget, each word with its flat index."""
+    import numpy as np
+    import torch
+    b = _bench()
+    out = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (3, 8 * 500), dtype=np.uint8))
+    b.dump_outputs(torch, str(tmp_path / "all"), out, 0, 1)
+    blocks = np.load(tmp_path / "all" / "blocks.npy")
+    assert blocks.dtype == np.float32 and blocks.shape == (1500, 8)
+    assert blocks.astype(np.uint8).tobytes() == out.numpy().tobytes()
+    monkeypatch.setattr(b, "DUMP_WORDS", 200)
+    for d in ("s1", "s2"):
+        b.dump_outputs(torch, str(tmp_path / d), out, 1, 2)
+    s1, s2 = (np.load(tmp_path / d / "blocks_rank1.npy") for d in ("s1", "s2"))
+    idx = np.load(tmp_path / "s1" / "block_word_index_rank1.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) <= 100 and np.all(np.diff(idx) > 0) and idx[-1] < 1500
+    assert np.array_equal(s1, s2) and np.array_equal(s1, out.numpy().reshape(-1, 8)[idx.astype(np.int64)].astype(np.float32))
+
+
 def test_live_counter_passes_degrade_to_the_committed_profile(monkeypatch, tmp_path):
     """bench.py counts roofline.traffic / valu_frac in the run itself (rocprofv3 --pmc child passes).  Where that cannot
     work -- no rocprofv3, the run itself under a profiler, a failing pass (this container: no GPU) -- it must say so, fall

@@ -1046,10 +1046,10 @@ def test_bench_watchdog_prints_the_line_when_the_extra_legs_overrun(pkg):
     """r05: after the contract's K timed steps nothing may cost the run its line.  With a 2 s watchdog the default command is
     still inside its extra legs when it fires: ONE line, exit code 0, the headline fields and the roofline present, marked;
     and over two gloo ranks every rank leaves (the launcher would otherwise report the survivors' time-outs)."""
-    d = _run_bench(["--steps", "3", "--warmup", "1", "--watchdog-seconds", "2", "--precondition-seconds", "0"], timeout=300)
+    d = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--watchdog-seconds", "2", "--precondition-seconds", "0"], timeout=300)
     assert "watchdog" in d and d["value"] > 0 and d["n_gpus"] == 1 and d["roofline"]["frac"] > 0 and d["config"]["preset"] == "c2"
     assert "slab" not in d  # (the last leg cannot have finished within 2 s)
-    d = _run_bench(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--watchdog-seconds", "2",
+    d = _run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--watchdog-seconds", "2",
                     "--precondition-seconds", "0"], timeout=300)
     assert "watchdog" in d and d["n_gpus"] == 2 and d["value"] > 0
 
@@ -1063,7 +1063,7 @@ def test_bench_bare_command_self_launches_ranks(pkg):
     for extra in (["--workload", "dxt1_rgba8", "--size", "1024", "--batch", "3"], ["--config", "c4"]):
         if extra == ["--config", "c4"] and backend == "gloo":
             extra = ["--workload", "etc1_rgb888", "--size", "256", "--batch", "5"]
-        d = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--backend", backend, "--no-cpu-baseline"] + extra)
+        d = _run_bench(["--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--backend", backend, "--no-cpu-baseline"] + extra)
         assert d["n_gpus"] == 2 and d["steps"] == 4 and d["parity"].startswith("bit-exact")
         assert d["value"] > 0 and d["value_with_gather"] > 0 and d["gather_ms"] > 0 and d["rank0_copy_matches"] is True
         # (no upper bound of value_with_gather against value: 4 steps of two different timed regions are not
@@ -1072,17 +1072,42 @@ def test_bench_bare_command_self_launches_ranks(pkg):
 
 def test_bench_config_presets(pkg):
     for cfg, codec, size in (("c3", "dxt5_rgba8", 8192), ("c5", "pvrtc2_rgba8", 4096)):
-        d = _run_bench(["--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-api",
+        d = _run_bench(["--full", "--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-api",
                         "--sustained-seconds", "0.5"])
         assert d["config"]["codec"] == codec and d["config"]["texture"] == [size, size] and d["config"]["preset"] == cfg
         assert d["parity"].startswith("bit-exact") and d["roofline"]["bound"] == "valu"
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_steps_output(pkg, tmp_path):
+    """Without --full the line holds the headline and none of the other legs; --dump-outputs writes the blocks of the last
+    timed step, the same on every run with the same arguments, and those are the oracle's blocks of the seeded input."""
+    import importlib.util
+    import os
+    import torch
+    args = ["--workload", "dxt1_rgba8", "--size", "1024", "--batch", "3", "--steps", "4", "--warmup", "1"]
+    d = _run_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 4 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mpixels/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "int32" and d["roofline"]["kernel_ms"] > 0
+    assert not {"parity", "cpu_baseline", "host_api", "sustained", "single_image", "configs", "slab", "next_rows"} & set(d)
+    _run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    a, b = np.load(tmp_path / "a" / "blocks.npy"), np.load(tmp_path / "b" / "blocks.npy")
+    idx = np.load(tmp_path / "a" / "block_word_index.npy")
+    per = 1024 * 1024 // 16 * 8  # DXT1: 8 bytes per 4x4 block
+    assert a.dtype == np.float32 and idx.dtype == np.float64 and a.shape == (3 * per // 8, 8)
+    assert np.array_equal(a, b) and np.array_equal(idx, np.arange(3 * per // 8))
+    spec = importlib.util.spec_from_file_location("icamd_bench", os.path.join(T.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    src = bench.make_batch(torch, "noise", 3, 1024, 4, torch.device("cuda", 0), seed=0)
+    want = T.oracle_encode(T.DXT1, src[2].cpu().numpy(), 1024, 1024, 4)
+    assert a[2 * per // 8:].astype(np.uint8).tobytes() == want
 
 
 def test_bench_default_line_carries_every_baseline_config_and_the_slab_legs(pkg):
     """The line the driver records (bench.py with no --config): c2 headline + `configs` {c3, c4, c5} + `slab` (one 4096^2 /
     8192^2 / 16384^2 image in block-row slabs, gathered into rank 0's final buffer), each with its own parity; and the
     slab mode as a headline line, over the RCCL code path with one forced rank."""
-    d = _run_bench(["--steps", "3", "--warmup", "1", "--extra-steps", "2", "--no-sustained", "--no-single-image", "--no-host-api",
+    d = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--extra-steps", "2", "--no-sustained", "--no-single-image", "--no-host-api",
                     "--no-cpu-baseline", "--precondition-seconds", "0"], timeout=900)
     assert d["config"]["preset"] == "c2" and d["parity"].startswith("bit-exact")
     assert sorted(d["configs"]) == ["c3", "c4", "c5", "c5_4bpp", "c5_8192"]
@@ -1130,7 +1155,7 @@ def test_bench_rehearsal_of_the_drivers_eight_rank_command(pkg):
     check of the 8-rank run executes; only the transport differs from RCCL."""
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 8 else "gloo"
-    d = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--extra-steps", "2", "--precondition-seconds", "0",
+    d = _run_bench(["--full", "--gpus", "8", "--steps", "3", "--warmup", "1", "--extra-steps", "2", "--precondition-seconds", "0",
                     "--backend", backend], timeout=1500)
     assert d["n_gpus"] == 8 and d["config"]["world_size"] == 8 and d["scaling"] == "weak"
     assert d["parity"].startswith("bit-exact") and d["config"]["textures_per_step_all_gpus"] == 8 * 16
@@ -1172,7 +1197,7 @@ def test_rccl_code_path_executes_with_a_single_rank(pkg):
                         os.path.join(T.ROOT, "tests", "nccl_worker.py")], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0 and "NCCL_WORKER_OK" in p.stdout, (p.stdout[-3000:], p.stderr[-3000:])
     for impl in ("torch", "c"):  # r06: the gather legs default to the library's own collective (icamd_gather_blocks_rccl)
-        d = _run_bench(["--gpus", "1", "--force-distributed", "--backend", "nccl", "--steps", "4", "--warmup", "1",
+        d = _run_bench(["--full", "--gpus", "1", "--force-distributed", "--backend", "nccl", "--steps", "4", "--warmup", "1",
                         "--workload", "dxt1_rgba8", "--size", "1024", "--batch", "3", "--no-cpu-baseline", "--no-host-api",
                         "--no-sustained", "--no-single-image", "--precondition-seconds", "0"]
                        + (["--gather-impl", "torch"] if impl == "torch" else []))
@@ -1226,7 +1251,7 @@ def test_every_inter_gpu_path_on_a_multi_gpu_box(pkg):
     _sharded_case(pkg, pkg.ETC1, 3, 256, len(devices) + 1, devices)
     _sharded_case(pkg, pkg.PVRTC2, 4, 256, len(devices) + 2, devices)
     # 4
-    d = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--extra-steps", "2", "--no-sustained", "--no-single-image",
+    d = _run_bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--extra-steps", "2", "--no-sustained", "--no-single-image",
                     "--no-host-api", "--no-cpu-baseline", "--precondition-seconds", "0"], timeout=1200)
     assert d["n_gpus"] == 2 and d["config"]["world_size"] == 2 and d["rank0_copy_matches"] is True
     for name, leg in d["configs"].items():
