@@ -31,6 +31,9 @@ RGB, BGR, RGBA, BGRA = 0, 1, 2, 3
 ETC_SPLIT_HORIZONTALLY, ETC_SPLIT_VERTICALLY, ETC_SMALLER_ERROR, ETC_HEURISTIC = 0, 1, 2, 3
 DXT1, DXT5, ETC1, PVRTC2 = 0, 1, 2, 3
 PVRTC4 = 4  # EXTENSION, parity unpinned: PVRTC1 4 bpp (include/ic_amd.h); icamd_encode_device only
+# EXTENSION, parity pinned through the reference's DXT5 alpha path (include/ic_amd.h): BC4 (RGTC1, one channel, 8 bytes per
+# block) and BC5 (RGTC2, two channels, 16 bytes per block); encode_device / decode_device / encode_batch_sharded_device only
+BC4, BC5 = 5, 6
 OK, FALSE = 0, 1
 
 EXPORTS = [
@@ -193,7 +196,9 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
                   grid_height=None, grid_width=None, row_stride_bytes=None, n_images=1,
                   src_image_stride_bytes=None, out=None, stream=None):
     """Launch the encode kernel on `src` (a torch.uint8 CUDA tensor, any shape, contiguous bytes).
-    Returns the output tensor [n_images, encoded_size] (device).  No synchronisation."""
+    Returns the output tensor [n_images, encoded_size] (device).  No synchronisation.
+    BC4 reads R from 1..4-byte pixels, BC5 reads R and G from 2..4-byte pixels: R = byte 0 (byte 2 with swap_rb, which needs
+    3 or 4 bytes per pixel), G = byte 1."""
     assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
     gh = height if grid_height is None else max(grid_height, height)
     gw = width if grid_width is None else max(grid_width, width)
@@ -278,7 +283,7 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
-    comps = 4 if codec in (DXT5, PVRTC2, PVRTC4) else 3
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, BC4: 1, BC5: 2}.get(codec, 3)  # BC4 -> R8, BC5 -> RG8
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

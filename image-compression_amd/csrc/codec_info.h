@@ -1,0 +1,16 @@
+// codec_info.h -- per-codec constants shared by the host code and the kernels (no device work).
+#ifndef ICAMD_CODEC_INFO_H_
+#define ICAMD_CODEC_INFO_H_
+
+#include <stdint.h>
+
+#include "ic_amd.h"
+
+namespace icamd {
+
+// Bytes of one 4 x 4 block (PVRTC included: 8 bytes per 8 x 4 / 4 x 4 block): 16 for DXT5 (alpha half + colour half) and BC5
+// (two BC4 halves), 8 for every other codec.
+constexpr uint32_t codec_block_bytes(int codec) { return (codec == ICAMD_DXT5 || codec == ICAMD_BC5) ? 16u : 8u; }
+
+}  // namespace icamd
+#endif  // ICAMD_CODEC_INFO_H_

@@ -4,13 +4,15 @@
 // google/image-compression stops at the raw block stream (CompressedImage, compressed_image.h:52-66 carries format +
 // dimensions only), so there is NOTHING in the reference to pin these against: parity unpinned by construction.  The
 // layouts below are written from the public file-format descriptions:
-//   * DDS  -- "DDS " magic + 124-byte DDS_HEADER with a FOURCC pixel format (DXT1 / DXT5 only; the legacy header has
-//             no code for ETC1 or PVRTC);
+//   * DDS  -- "DDS " magic + 124-byte DDS_HEADER with a FOURCC pixel format (DXT1 / DXT5, and ATI1 / ATI2 for BC4 / BC5;
+//             the legacy header has no code for ETC1 or PVRTC);
 //   * KTX  -- KTX 1.1: 12-byte identifier, 13 little-endian uint32 fields, then per mip level uint32 imageSize + data
 //             (glInternalFormat: COMPRESSED_RGB_S3TC_DXT1_EXT 0x83F0, COMPRESSED_RGBA_S3TC_DXT5_EXT 0x83F3,
-//             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03);
+//             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03, COMPRESSED_RED_RGTC1 0x8DBB with base format
+//             GL_RED, COMPRESSED_RG_RGTC2 0x8DBD with base format GL_RG);
 //   * PKM  -- "PKM 10": 16-byte big-endian header, ETC1 only, exactly one level;
-//   * PVR  -- PVR v3: 52-byte little-endian header (pixel format 1 = PVRTC 2bpp RGBA, 6 = ETC1, 7 = DXT1, 11 = DXT5),
+//   * PVR  -- PVR v3: 52-byte little-endian header (pixel format 1 = PVRTC 2bpp RGBA, 6 = ETC1, 7 = DXT1, 11 = DXT5,
+//             12 = BC4, 13 = BC5),
 //             no metadata, levels follow largest first.  PVRTC data is stored in the Z-order the encoder already
 //             produces (pvrtc_compressor.cc:551-580).
 // Mip level l of an h x w texture is max(1, h >> l) x max(1, w >> l) pixels; its block stream is what
@@ -22,6 +24,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "codec_info.h"
 #include "ic_amd.h"
 
 namespace icamd {
@@ -49,9 +52,11 @@ inline size_t container_header_size(int container) {
 
 inline bool container_supports(int container, int codec) {
   switch (container) {
-    case ICAMD_CONTAINER_DDS: return codec == ICAMD_DXT1 || codec == ICAMD_DXT5;
+    case ICAMD_CONTAINER_DDS: return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5;
     case ICAMD_CONTAINER_KTX:
-    case ICAMD_CONTAINER_PVR: return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2;
+    case ICAMD_CONTAINER_PVR:
+      return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
+             codec == ICAMD_BC5;
     case ICAMD_CONTAINER_PKM: return codec == ICAMD_ETC1;
     default: return false;
   }
@@ -65,7 +70,7 @@ inline size_t container_level_bytes(int codec, uint32_t height, uint32_t width, 
     if ((height >> level) < 8 || (width >> level) < 8) return 0;
     return (size_t)w * h / 4;
   }
-  return (size_t)((h + 3) / 4) * ((w + 3) / 4) * (codec == ICAMD_DXT5 ? 16u : 8u);
+  return (size_t)((h + 3) / 4) * ((w + 3) / 4) * codec_block_bytes(codec);
 }
 
 // framing bytes in front of every level (KTX: the uint32 imageSize)
@@ -86,7 +91,7 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 28, levels);                                                        // dwMipMapCount
       put_le32(out + 76, 32);                                                            // ddspf.dwSize
       put_le32(out + 80, 0x4u);                                                          // DDPF_FOURCC
-      memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : "DXT5", 4);
+      memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1" : "ATI2", 4);
       put_le32(out + 108, 0x1000u | (levels > 1 ? 0x8u | 0x400000u : 0u));               // DDSCAPS_TEXTURE [COMPLEX MIPMAP]
       break;
     }
@@ -97,9 +102,12 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 16, 0);            // glType (compressed)
       put_le32(out + 20, 1);            // glTypeSize
       put_le32(out + 24, 0);            // glFormat (compressed)
-      const uint32_t internal = codec == ICAMD_DXT1 ? 0x83F0u : codec == ICAMD_DXT5 ? 0x83F3u : codec == ICAMD_ETC1 ? 0x8D64u : 0x8C03u;
+      const uint32_t internal = codec == ICAMD_DXT1 ? 0x83F0u : codec == ICAMD_DXT5 ? 0x83F3u : codec == ICAMD_ETC1 ? 0x8D64u
+                                : codec == ICAMD_BC4 ? 0x8DBBu : codec == ICAMD_BC5 ? 0x8DBDu : 0x8C03u;
       put_le32(out + 28, internal);
-      put_le32(out + 32, (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2) ? 0x1908u : 0x1907u);  // GL_RGBA / GL_RGB
+      const uint32_t base = codec == ICAMD_BC4 ? 0x1903u : codec == ICAMD_BC5 ? 0x8227u                    // GL_RED / GL_RG
+                            : (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2) ? 0x1908u : 0x1907u;         // GL_RGBA / GL_RGB
+      put_le32(out + 32, base);
       put_le32(out + 36, width);
       put_le32(out + 40, height);
       put_le32(out + 44, 0);            // pixelDepth
@@ -121,7 +129,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
     case ICAMD_CONTAINER_PVR: {
       put_le32(out, 0x03525650u);  // "PVR\3"
       put_le32(out + 4, 0);        // flags
-      put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u : 11u);
+      put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u
+                        : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : 11u);
       put_le32(out + 16, 0);       // colour space: linear RGB
       put_le32(out + 20, 0);       // channel type: unsigned byte, normalised
       put_le32(out + 24, height);

@@ -2,6 +2,7 @@
 // lane, 8/16-byte coalesced block loads, 12/16-byte row-segment stores (Compressor4x4Helper::Decompress,
 // internal/compressor4x4_helper.h:218-262: blocks past the image edge are clipped).
 #include "blockops_block.h"  // decode_block.h + the palette-plane row decoders
+#include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
@@ -13,7 +14,7 @@ __device__ __forceinline__ void decode_one(const DecodeParams &P, uint32_t k) {
   const uint32_t img = fastdiv(k, P.div_bpi);
   const uint32_t rem = k - img * P.blocks_per_image;
   const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
-  const uint8_t *src = P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * (CODEC == ICAMD_DXT5 ? 16 : 8);
+  const uint8_t *src = P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * codec_block_bytes(CODEC);
   const bool swap = P.swap_rb != 0;
   uint32_t w[4] = { 0, 0, 0, 0 };
   if (CODEC == ICAMD_DXT5) {

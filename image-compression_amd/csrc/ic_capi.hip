@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "codec_info.h"
 #include "containers.h"
 #include "ic_abi.h"
 #include "ic_launch.h"
@@ -327,6 +328,36 @@ int pvrtc_encode_device_impl(int src_components, uint32_t height, uint32_t width
   return ICAMD_OK;
 }
 
+// EXTENSION (include/ic_amd.h ICAMD_BC4): BC4 from 1..4-byte sources, BC5 from 2..4-byte ones; R = byte 0 (byte 2 when swap_rb
+// and the source has 3 or 4 bytes), G = byte 1.  The argument checks come before any device work.
+int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_height,
+                            uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
+                            size_t dst_image_stride_bytes, const void *d_src, void *d_dst, hipStream_t stream) {
+  if (src_components < (codec == ICAMD_BC5 ? 2 : 1) || src_components > 4)
+    return fail(ICAMD_ERR_ARG, codec == ICAMD_BC5 ? "BC5 needs 2, 3 or 4 source components" : "BC4 needs 1 to 4 source components");
+  if (swap_rb && src_components < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (n_images == 0) return ICAMD_OK;
+  const int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  icamd::GridParams P;
+  P.src = static_cast<const uint8_t *>(d_src);
+  P.dst = static_cast<uint8_t *>(d_dst);
+  P.src_image_stride = src_image_stride_bytes;
+  P.dst_image_stride = dst_image_stride_bytes;
+  P.height = height;
+  P.width = width;
+  P.block_rows = num_blocks4(std::max(height, grid_height));
+  P.block_cols = num_blocks4(std::max(width, grid_width));
+  P.row_stride = row_stride_bytes;
+  P.n_images = n_images;
+  P.swap_rb = swap_rb ? 1u : 0u;
+  P.etc_strategy = P.log2_tile_cols = P.tile_row0 = P.force_gather = 0;
+  ICAMD_HIP(icamd::launch_bc45_encode(codec, src_components, P, stream), codec == ICAMD_BC5 ? "launch bc5" : "launch bc4");
+  return ICAMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,6 +378,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_ETC1: return icamd::etc1_kernel_name(src_components);
     case ICAMD_PVRTC2: return icamd::pvrtc2_kernel_name();
     case ICAMD_PVRTC4: return icamd::pvrtc4_kernel_name();
+    case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
   }
   return "";
 }
@@ -371,7 +403,7 @@ size_t icamd_compute_compressed_data_size(int compressor, int format, uint32_t h
 size_t icamd_encoded_size(int codec, uint32_t grid_height, uint32_t grid_width) {
   if (codec == ICAMD_PVRTC2) return (size_t)grid_width * grid_height / 4;
   if (codec == ICAMD_PVRTC4) return (size_t)grid_width * grid_height / 2;
-  return (size_t)num_blocks4(grid_height) * num_blocks4(grid_width) * (codec == ICAMD_DXT5 ? 16u : 8u);
+  return (size_t)num_blocks4(grid_height) * num_blocks4(grid_width) * icamd::codec_block_bytes(codec);
 }
 
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
@@ -380,6 +412,10 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                         const void *d_src, void *d_dst, void *hip_stream) try {
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (codec == ICAMD_BC4 || codec == ICAMD_BC5)
+    return bc45_encode_device_impl(codec, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
+                                   n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst,
+                                   static_cast<hipStream_t>(hip_stream));
   if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
@@ -443,7 +479,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
       B.height = height > top * 4u ? height - top * 4u : 0u;
       if (B.height != 0) {  // (a CompressAndPad grid whose lower band lies wholly below the image is not split)
         B.src = P.src + (size_t)top * 4u * row_stride_bytes;
-        B.dst = P.dst + (size_t)top * P.block_cols * (codec == ICAMD_DXT5 ? 16u : 8u);
+        B.dst = P.dst + (size_t)top * P.block_cols * icamd::codec_block_bytes(codec);
         ICAMD_HIP(hipEventRecord(lane->fork, stream), "split: fork event");
         ICAMD_HIP(hipStreamWaitEvent(lane->side, lane->fork, 0), "split: fork wait");
         ICAMD_HIP(launch(B, lane->side), "launch (lower band)");
@@ -634,7 +670,7 @@ static int compress_host_common(Staging &st, bool pinned, bool and_pad, int comp
     ICAMD_HIP(hipMemcpyAsync(h_dst, d_out, out_size, hipMemcpyDeviceToHost, s), "D2H copy");
     ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
   } else {
-    const uint32_t block_bytes = codec == ICAMD_DXT5 ? 16u : 8u;
+    const uint32_t block_bytes = icamd::codec_block_bytes(codec);
     const uint32_t img_block_rows = num_blocks4(height), grid_block_rows = num_blocks4(gh), block_cols = num_blocks4(gw);
     uint64_t band_rows = std::max<uint64_t>(1, kHostBandBytes / (4u * stride));  // block rows per band
     if (band_rows * 2 > img_block_rows) band_rows = img_block_rows;               // small images: one band
@@ -705,14 +741,32 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                         const void *d_blocks, void *d_pixels, void *hip_stream) try {
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
-  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4)
+  const bool bc45 = codec == ICAMD_BC4 || codec == ICAMD_BC5;
+  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 && !bc45)
     return ICAMD_FALSE;
+  if (bc45 && swap_rb) return fail(ICAMD_ERR_ARG, "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
   uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
+  if (bc45) {
+    // EXTENSION (include/ic_amd.h ICAMD_BC4): R8 / RG8 rows; 64-bit addressing and chunked grids, so no banding is needed
+    icamd::Bc45DecodeParams P;
+    P.blocks = blocks;
+    P.pixels = pixels;
+    P.src_image_stride = src_image_stride_bytes;
+    P.dst_image_stride = dst_image_stride_bytes;
+    P.height = height;
+    P.width = width;
+    P.block_rows = num_blocks4(height);
+    P.block_cols = num_blocks4(width);
+    P.row_stride = width * (codec == ICAMD_BC5 ? 2u : 1u) + padding_bytes_per_row;
+    P.log2_tile_cols = P.tile_row0 = 0;
+    ICAMD_HIP(icamd::launch_bc45_decode(codec, n_images, P, stream), "launch bc4 / bc5 decode");
+    return ICAMD_OK;
+  }
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4) {
     // EXTENSION (the reference's PvrtcCompressor::Decompress returns false, pvrtc.cc:669-672; 4 bpp: no such format there at
     // all): the sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650), RGBA8 out, no row padding, one launch per <= 2^30 blocks
@@ -728,7 +782,7 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     }
     return ICAMD_OK;
   }
-  const uint32_t block_bytes = codec == ICAMD_DXT5 ? 16u : 8u;
+  const uint32_t block_bytes = icamd::codec_block_bytes(codec);
   const uint32_t row_stride = width * (codec == ICAMD_DXT5 ? 4u : 3u) + padding_bytes_per_row;
   const uint64_t block_cols = num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
   const uint64_t kMaxBlocks = (1ull << 31) - 1;
@@ -1043,7 +1097,7 @@ bool subimage_geometry(int compressor, int format, uint32_t ch, uint32_t cw, uin
                        uint32_t w, int *block_bytes) {
   int codec;
   if (!blockop_codec(compressor, format, &codec)) return false;
-  *block_bytes = codec == ICAMD_DXT5 ? 16 : 8;
+  *block_bytes = (int)icamd::codec_block_bytes(codec);
   if (row % 4 || col % 4 || h % 4 || w % 4) return false;
   // 64-bit sums: the reference's uint32 start + extent can wrap and then accept a window outside the image
   return !(row > ch || col > cw || (uint64_t)row + h > ch || (uint64_t)col + w > cw);
@@ -1360,7 +1414,8 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
                           const uint8_t *const *level_data, const size_t *level_sizes, uint8_t *out, size_t out_size) try {
   using namespace icamd;
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
-  if (codec < ICAMD_DXT1 || codec > ICAMD_PVRTC2) return fail(ICAMD_ERR_ARG, "unknown codec");
+  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && codec != ICAMD_BC4 && codec != ICAMD_BC5))
+    return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);
   if (need == 0 || out_size != need) return ICAMD_FALSE;

@@ -120,6 +120,19 @@ struct DecodeParams {
 };
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
 
+// BC4 / BC5 (extension, bc45_kernels.hip).  Encode: GridParams as for DXT, comps = 1..4 (BC4) / 2..4 (BC5).  Decode: n_images
+// block grids of block_rows x block_cols, R8 / RG8 rows of row_stride bytes; log2_tile_cols / tile_row0 are the launcher's.
+struct Bc45DecodeParams {
+  const uint8_t *blocks;
+  uint8_t *pixels;
+  uint64_t src_image_stride, dst_image_stride;
+  uint32_t height, width, block_rows, block_cols, row_stride;
+  uint32_t log2_tile_cols, tile_row0;
+};
+hipError_t launch_bc45_encode(int codec, int comps, const GridParams &P, hipStream_t stream);
+hipError_t launch_bc45_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
+const char *bc45_kernel_name(int codec, int comps);
+
 // Compressed-domain operations on one image's block grid.
 struct BlockOpParams {
   const uint8_t *src;

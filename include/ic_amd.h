@@ -44,7 +44,23 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * same rules and by decoding.  Accepted by icamd_encode_device (RGBA8, square power of two >= 8, no row padding:
         * size * size / 2 bytes per image, blocks in the 2 bpp Z order) and icamd_encoded_size only; under stream capture it needs a
         * caller workspace of icamd_pvrtc4_workspace_size bytes (icamd_pvrtc2_set_workspace). */
-       ICAMD_PVRTC4 = 4 };
+       ICAMD_PVRTC4 = 4,
+       /* EXTENSION, PARITY PINNED through the reference's DXT5 alpha path: BC4 (RGTC1, one channel, 8 bytes per 4 x 4 block)
+        * and BC5 (RGTC2, two channels, 16 bytes per block).  The reference has no BC4 / BC5 compressor; these are defined
+        * through it:
+        *   BC4 of channel c of an image = bytes 0..7 of every 16-byte block that the reference's DXT5 encoder
+        *       (EncodeDxt5Block, dxtc.cc:516-528) writes for the RGBA image whose alpha is channel c -- same raster block
+        *       order, same edge replication, same has_one_pixel rule (a block wholly right of AND below the image, i.e. only
+        *       on a padded grid, gets alpha0 = alpha1 = its corner pixel and all codes 0);
+        *   BC5 = BC4(R) followed by BC4(G) in each 16-byte block (the standard RGTC2 layout).
+        * Decoding follows DecodeAlphaValues (dxtc.cc:195-217, truncating CombineUint8Fast interpolation) and the 3-bit code
+        * order of DecodeDxt5Block (dxtc.cc:240-267).  Unsigned (UNORM) only; the channels are R and G.
+        * Source channels read by icamd_encode_device: R = byte 0 (byte 2 when swap_rb and src_components >= 3), G = byte 1;
+        * BC4 accepts src_components 1..4, BC5 2..4, swap_rb only with 3 or 4 (otherwise ICAMD_ERR_ARG).
+        * icamd_decode_device writes R8 (BC4) or RG8 (BC5) rows and needs swap_rb = 0.  Reachable through icamd_encode_device,
+        * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_encoded_size, icamd_kernel_name and the container
+        * functions only: no Compressor + format pair selects them. */
+       ICAMD_BC4 = 5, ICAMD_BC5 = 6 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -141,7 +157,7 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
 
 /* Generic block-grid encoder over a batch of equally-shaped images (one launch).
  *   codec            ICAMD_DXT1 / DXT5 / ETC1 / PVRTC2
- *   src_components   3 or 4 bytes per source pixel.  4 with DXT1/ETC1 is the
+ *   src_components   3 or 4 bytes per source pixel (BC4: 1..4, BC5: 2..4).  4 with DXT1/ETC1 is the
  *                    "RGBA8, alpha ignored" extension named by BASELINE.json; its result
  *                    is defined as the reference's output for the alpha-stripped image.
  *   swap_rb          source is B,G,R(,A) (NeedsRedAndBlueSwapped, compressed_image.h:202-204)
@@ -152,7 +168,8 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
  * d_dst + i*dst_image_stride_bytes (row-major blocks; PVRTC: Z-order, pvrtc.cc:551-580).
  * Any uint32 geometry runs (grids, batches and strides beyond one launch's limits are chunked internally).
  * Alignment: DXT / ETC accept any pointers and strides; PVRTC reads 16 bytes at a time and requires d_src (and
- * src_image_stride_bytes) 16-byte aligned, d_dst (and dst_image_stride_bytes) 8-byte aligned, else ICAMD_ERR_ARG. */
+ * src_image_stride_bytes) 16-byte aligned, d_dst (and dst_image_stride_bytes) 8-byte aligned, else ICAMD_ERR_ARG.
+ * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT. */
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
                         uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
                         uint32_t row_stride_bytes, uint32_t n_images,
@@ -168,7 +185,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
  * Z order :80-86) and needs square power-of-two sizes and padding_bytes_per_row == 0.  codec ICAMD_PVRTC4 (r05) is the
  * decoder of the 4 bpp extension encoder, under the same conditions and as unpinned as that: 4 x 4 blocks, every pixel its
  * own 2-bit value (weights 0, 3, 5, 8; a block with colour-word bit 0 set -- the encoder never writes one -- takes PVRTC1's
- * punch-through weights 0, 4, 4, 8 with alpha 0 for value 2). */
+ * punch-through weights 0, 4, 4, 8 with alpha 0 for value 2).  ICAMD_BC4 / ICAMD_BC5 (extension, see ICAMD_BC4) write
+ * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG. */
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t padding_bytes_per_row, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
@@ -328,7 +346,8 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
 /* ---- container framing (EXTENSION: SURVEY.md 8(f) row 4, tail) ----
  * The reference ends at the raw block stream (compressed_image.h:52-66); it has no file-container code, so there is
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
- * descriptions (csrc/containers.h): DDS (DXT1 / DXT5), KTX 1.1 and PVR v3 (all four codecs), PKM (ETC1, one level).
+ * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
+ * PVRTC2, BC4, BC5), PKM (ETC1, one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
  * icamd_compress / icamd_downsample return for that size (PVRTC: square power-of-two levels of 8 x 8 and up only). */
 enum { ICAMD_CONTAINER_DDS = 0, ICAMD_CONTAINER_KTX = 1, ICAMD_CONTAINER_PKM = 2, ICAMD_CONTAINER_PVR = 3 };
