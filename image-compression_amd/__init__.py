@@ -46,6 +46,8 @@ EXPORTS = [
     "icamd_encode_batch_sharded_device", "icamd_clock_probe_device", "icamd_wall_clock_rate_khz",
     "icamd_container_size", "icamd_container_write",
     "icamd_rccl_available", "icamd_rccl_get_unique_id", "icamd_rccl_comm_init", "icamd_rccl_comm_destroy", "icamd_gather_blocks_rccl",
+    "icamd_mip_max_levels", "icamd_mip_chain_size", "icamd_mip_workspace_size", "icamd_encode_mips_device",
+    "icamd_mip_pyramid_device", "icamd_compress_mips",
 ]
 RCCL_UNIQUE_ID_BYTES = 128
 CONTAINER_DDS, CONTAINER_KTX, CONTAINER_PKM, CONTAINER_PVR = 0, 1, 2, 3
@@ -160,6 +162,20 @@ def lib():
             L.icamd_rccl_comm_destroy.argtypes = [_vp]
             L.icamd_gather_blocks_rccl.restype = _ci
             L.icamd_gather_blocks_rccl.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
+        if not LIB_OVERRIDDEN or hasattr(L, "icamd_encode_mips_device"):  # mip-chain entry points
+            L.icamd_mip_max_levels.restype = _u32
+            L.icamd_mip_max_levels.argtypes = [_u32, _u32]
+            L.icamd_mip_chain_size.restype = _sz
+            L.icamd_mip_chain_size.argtypes = [_ci, _u32, _u32, _u32, _vp]
+            L.icamd_mip_workspace_size.restype = _sz
+            L.icamd_mip_workspace_size.argtypes = [_ci, _ci, _u32, _u32, _u32, _u32]
+            L.icamd_encode_mips_device.restype = _ci
+            L.icamd_encode_mips_device.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp,
+                                                   _sz, _vp]
+            L.icamd_mip_pyramid_device.restype = _ci
+            L.icamd_mip_pyramid_device.argtypes = [_ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
+            L.icamd_compress_mips.restype = _ci
+            L.icamd_compress_mips.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
         L.icamd_device_count.restype = _ci
         L.icamd_last_error.restype = ctypes.c_char_p
         L.icamd_version.restype = ctypes.c_char_p
@@ -645,3 +661,127 @@ class RcclGather:
             lib().icamd_rccl_comm_destroy(self.comm)
             self.comm = ctypes.c_void_p()
 
+
+
+# ---- mip chains (EXTENSION, include/ic_amd.h): one source image -> every level, each encoded from its own pixels ----
+def mip_max_levels(height, width):
+    """floor(log2(max(height, width))) + 1: the levels of a full chain (0 for an empty image)."""
+    return lib().icamd_mip_max_levels(height, width)
+
+
+def mip_chain_size(codec, height, width, levels=None):
+    """(bytes of one image's chain, [offset of level l for l in 0..levels]) -- the last entry is the total; (0, None) where
+    the codec / size / level count is refused."""
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    offs = (ctypes.c_size_t * (max(levels, 0) + 1))()
+    n = lib().icamd_mip_chain_size(codec, height, width, levels, offs)
+    return (n, list(offs)) if n else (0, None)
+
+
+def mip_workspace_size(codec, src_components, height, width, levels=None, n_images=1):
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    return lib().icamd_mip_workspace_size(codec, src_components, height, width, levels, n_images)
+
+
+def _check_out(out, n_images, per, what):
+    """A caller's `out` must be the [n_images, per] uint8 device tensor the kernels write (per = the destination image
+    stride) and the views index: a shorter one would be written past its end."""
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n_images
+            and out.shape[1] == max(per, 1)):
+        raise ValueError("%s: out must be a contiguous uint8 CUDA tensor of shape [%d, %d], got %s %s"
+                         % (what, n_images, max(per, 1), tuple(out.shape), out.dtype))
+
+
+def mip_level_shape(height, width, level):
+    return max(1, height >> level), max(1, width >> level)
+
+
+def encode_mips_device(codec, src, height, width, src_components, *, levels=None, swap_rb=False,
+                       etc_strategy=ETC_SMALLER_ERROR, n_images=1, row_stride_bytes=None, src_image_stride_bytes=None,
+                       dst_image_stride_bytes=None, out=None, workspace=None, stream=None):
+    """Fused mip-chain encode (icamd_encode_mips_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes).
+    Returns (flat, views): flat is [n_images, dst_image_stride] (device), views[l] = flat[:, offset[l]:offset[l + 1]], the
+    blocks of level l.  The workspace is allocated here unless the caller passes one (a uint8 CUDA tensor of at least
+    mip_workspace_size bytes).  No synchronisation."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    total, offs = mip_chain_size(codec, height, width, levels)
+    per = total if dst_image_stride_bytes is None else dst_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
+    _check_out(out, n_images, per, "encode_mips_device")
+    ws_bytes = mip_workspace_size(codec, src_components, height, width, levels, n_images) if total else 0
+    if workspace is None and ws_bytes:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=src.device)
+    if workspace is not None and not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("encode_mips_device: workspace must be a contiguous uint8 CUDA tensor")
+    ws_ptr = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    ws_len = workspace.numel() if workspace is not None else 0
+    st = lib().icamd_encode_mips_device(codec, etc_strategy, src_components, int(swap_rb), height, width, stride, levels,
+                                        n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
+                                        ctypes.c_void_p(out.data_ptr()), ws_ptr, ws_len, _stream_handle(stream))
+    if not _check(st, "icamd_encode_mips_device"):
+        return None
+    return out, [out[:, offs[l]:offs[l + 1]] for l in range(levels)]
+
+
+def mip_pyramid_size(src_components, height, width, levels=None):
+    """(bytes of one image's pyramid output -- levels 1 .. levels-1 --, [offset of level l for l in 1..levels])."""
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    offs = [0]
+    for l in range(1, levels):
+        h, w = mip_level_shape(height, width, l)
+        offs.append(offs[-1] + h * w * src_components)
+    return offs[-1], offs
+
+
+def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_images=1, row_stride_bytes=None,
+                       src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, stream=None):
+    """The pixel pyramid alone (icamd_mip_pyramid_device).  Returns (flat, views): views[l - 1] is level l as a
+    [n_images, h_l, w_l, src_components] view, for l = 1 .. levels-1."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    total, offs = mip_pyramid_size(src_components, height, width, levels)
+    per = total if dst_image_stride_bytes is None else dst_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
+    _check_out(out, n_images, per, "mip_pyramid_device")
+    st = lib().icamd_mip_pyramid_device(src_components, height, width, stride, levels, n_images, img_stride, per,
+                                        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                        _stream_handle(stream))
+    if not _check(st, "icamd_mip_pyramid_device"):
+        return None
+    views = []
+    for l in range(1, levels):
+        h, w = mip_level_shape(height, width, l)
+        views.append(out[:, offs[l - 1]:offs[l]].view(n_images, h, w, src_components))
+    return out, views
+
+
+def compress_mips_host(compressor, fmt, buffer, height, width, *, levels=None, padding_bytes_per_row=0,
+                       etc_strategy=ETC_SMALLER_ERROR, out_size=None):
+    """Host-buffer mip chain (icamd_compress_mips): bytes of the whole chain, or None where the reference's conventions
+    return false."""
+    import numpy as np
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    src = np.frombuffer(bytes(buffer), dtype=np.uint8) if not isinstance(buffer, np.ndarray) else np.ascontiguousarray(buffer)
+    if out_size is None:
+        codec = {(COMPRESSOR_DXTC, RGB): DXT1, (COMPRESSOR_DXTC, BGR): DXT1, (COMPRESSOR_DXTC, RGBA): DXT5,
+                 (COMPRESSOR_DXTC, BGRA): DXT5, (COMPRESSOR_ETC, RGB): ETC1}.get((compressor, fmt))
+        out_size = mip_chain_size(codec, height, width, levels)[0] if codec is not None else 0
+    out = np.empty(max(out_size, 1), dtype=np.uint8)
+    st = lib().icamd_compress_mips(compressor, etc_strategy, fmt, height, width, padding_bytes_per_row, levels,
+                                   src.ctypes.data, out.ctypes.data, out_size)
+    if not _check(st, "icamd_compress_mips"):
+        return None
+    return out[:out_size].tobytes()

@@ -358,6 +358,61 @@ int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t
   return ICAMD_OK;
 }
 
+
+// ---- mip chains (EXTENSION, include/ic_amd.h): pass planning shared by the fused encode and the pixel pyramid ----
+uint32_t mip_dim(uint32_t v, uint32_t l) { return l >= 32u ? 1u : std::max(1u, v >> l); }
+uint32_t mip_max_levels(uint32_t h, uint32_t w) {
+  if (h == 0 || w == 0) return 0;
+  uint32_t m = std::max(h, w), l = 0;
+  while (m >>= 1) ++l;
+  return l + 1u;
+}
+bool mip_codec(int codec) {
+  return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_BC4 || codec == ICAMD_BC5;
+}
+// One kernel launch: levels [l0, l0 + n) of the chain from level l0's pixels.  A pass over more than one 128 x 128 tile
+// reaches local level 5 in blocks (6 with pixels only); `handoff`: further levels follow, from level l0 + 6's pixels.
+struct MipPass {
+  uint32_t l0, n, in_h, in_w;
+  bool handoff;
+};
+std::vector<MipPass> mip_plan(uint32_t h, uint32_t w, uint32_t levels, bool pyramid) {
+  std::vector<MipPass> plan;
+  for (uint32_t l0 = 0;; l0 += 6u) {
+    MipPass p;
+    p.l0 = l0;
+    p.in_h = mip_dim(h, l0);
+    p.in_w = mip_dim(w, l0);
+    const bool single = p.in_h <= 128u && p.in_w <= 128u;
+    p.n = single ? levels - l0 : std::min(levels - l0, pyramid ? 7u : 6u);
+    p.handoff = l0 + p.n < levels;
+    plan.push_back(p);
+    if (!p.handoff) break;
+  }
+  return plan;
+}
+// bytes of one image's handoff image at level l (COMPS bytes per pixel)
+size_t mip_level_pixels(uint32_t h, uint32_t w, uint32_t l, int comps) { return (size_t)mip_dim(h, l) * mip_dim(w, l) * (size_t)comps; }
+// one image's pixel pyramid (levels 1 .. levels-1, tight rows, back to back)
+size_t mip_pyramid_bytes(uint32_t h, uint32_t w, uint32_t levels, int comps) {
+  size_t total = 0;
+  for (uint32_t l = 1; l < levels; ++l) total += mip_level_pixels(h, w, l, comps);
+  return total;
+}
+size_t mip_workspace_bytes(int codec, uint32_t h, uint32_t w, uint32_t levels, int comps, uint32_t n_images) {
+  if (codec == ICAMD_ETC1) return mip_pyramid_bytes(h, w, levels, comps) * n_images;  // the pyramid, then the ETC1 kernels
+  size_t total = 0;
+  for (const MipPass &p : mip_plan(h, w, levels, false))
+    if (p.handoff) total += mip_level_pixels(h, w, p.l0 + 6u, comps) * n_images;
+  return total;
+}
+int mip_check_components(int codec, int comps, int swap_rb) {
+  const bool ok = codec == ICAMD_DXT5 ? comps == 4 : (codec == ICAMD_DXT1 || codec == ICAMD_ETC1) ? comps == 3 || comps == 4
+                : codec == ICAMD_BC4 ? comps >= 1 && comps <= 4 : comps >= 2 && comps <= 4;
+  if (!ok) return fail(ICAMD_ERR_ARG, "mip chain: source components not accepted by this codec (as icamd_encode_device)");
+  if (swap_rb && comps < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
+  return ICAMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1431,6 +1486,176 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
     std::memcpy(p, level_data[l], level_sizes[l]);
     p += level_sizes[l];
   }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+
+// ---- mip chains (EXTENSION) ----
+uint32_t icamd_mip_max_levels(uint32_t height, uint32_t width) { return mip_max_levels(height, width); }
+
+size_t icamd_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets) {
+  if (!mip_codec(codec) || levels == 0 || levels > mip_max_levels(height, width)) return 0;
+  size_t total = 0;
+  for (uint32_t l = 0; l < levels; ++l) {
+    if (level_offsets) level_offsets[l] = total;
+    total += icamd_encoded_size(codec, mip_dim(height, l), mip_dim(width, l));
+  }
+  if (level_offsets) level_offsets[levels] = total;
+  return total;
+}
+
+size_t icamd_mip_workspace_size(int codec, int src_components, uint32_t height, uint32_t width, uint32_t levels,
+                                uint32_t n_images) {
+  if (!mip_codec(codec) || src_components < 1 || src_components > 4 || levels == 0 || levels > mip_max_levels(height, width))
+    return 0;
+  return mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
+}
+
+int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, int swap_rb, uint32_t height, uint32_t width,
+                             uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
+                             size_t workspace_bytes, void *hip_stream) try {
+  if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
+    return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
+  if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  int rc = mip_check_components(codec, src_components, swap_rb);
+  if (rc != ICAMD_OK) return rc;
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  size_t offsets[33];
+  const size_t chain = icamd_mip_chain_size(codec, height, width, levels, offsets);
+  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)src_components;
+  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < chain))
+    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
+  const size_t ws_need = mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
+  if (ws_need && (!d_workspace || workspace_bytes < ws_need))
+    return fail(ICAMD_ERR_ARG, "workspace smaller than icamd_mip_workspace_size");
+  if (n_images == 0) return ICAMD_OK;
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (codec == ICAMD_ETC1) {
+    // level 0 from the source and every other level from the pixel pyramid in the workspace, each through the ETC1 kernels
+    // of icamd_encode_device (a fused ETC1 kernel is deferred)
+    uint8_t *dst = static_cast<uint8_t *>(d_dst), *ws = static_cast<uint8_t *>(d_workspace);
+    const size_t pyr = mip_pyramid_bytes(height, width, levels, src_components);
+    rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, height, width, row_stride_bytes, n_images,
+                             src_image_stride_bytes, dst_image_stride_bytes, d_src, dst, hip_stream);
+    if (rc == ICAMD_OK && levels > 1)
+      rc = icamd_mip_pyramid_device(src_components, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes, pyr,
+                                    d_src, ws, hip_stream);
+    size_t poff = 0;
+    for (uint32_t l = 1; l < levels && rc == ICAMD_OK; ++l) {
+      const uint32_t lh = mip_dim(height, l), lw = mip_dim(width, l);
+      rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, lh, lw, lh, lw, lw * (uint32_t)src_components,
+                               n_images, pyr, dst_image_stride_bytes, ws + poff, dst + offsets[l], hip_stream);
+      poff += mip_level_pixels(height, width, l, src_components);
+    }
+    return rc;
+  }
+  const uint8_t *in = static_cast<const uint8_t *>(d_src);
+  uint64_t in_image_stride = src_image_stride_bytes;
+  uint32_t in_row_stride = row_stride_bytes;
+  uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+  for (const MipPass &p : mip_plan(height, width, levels, false)) {
+    icamd::MipParams P = {};
+    P.src = in;
+    P.src_image_stride = in_image_stride;
+    P.row_stride = in_row_stride;
+    P.height = p.in_h;
+    P.width = p.in_w;
+    P.dst = static_cast<uint8_t *>(d_dst);
+    P.dst_image_stride = dst_image_stride_bytes;
+    for (uint32_t j = 0; j < p.n; ++j) P.level_off[j] = offsets[p.l0 + j];
+    P.enc_mask = (1u << p.n) - 1u;
+    P.swap_rb = swap_rb ? 1u : 0u;
+    if (p.handoff) {  // level l0 + 6's pixels, tight rows, images back to back: the next pass's input
+      const size_t per = mip_level_pixels(height, width, p.l0 + 6u, src_components);
+      P.pix = ws;
+      P.pix_image_stride = per;
+      P.pix_mask = 1u << 6;
+      in = ws;
+      in_image_stride = per;
+      in_row_stride = mip_dim(width, p.l0 + 6u) * (uint32_t)src_components;
+      ws += per * n_images;
+    }
+    ICAMD_HIP(icamd::launch_mip_pass(codec, src_components, P, n_images, stream), "launch mip chain");
+  }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                             uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, void *hip_stream) try {
+  if (src_components < 1 || src_components > 4) return fail(ICAMD_ERR_ARG, "src_components must be 1 .. 4");
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  size_t poff[34];  // poff[l]: bytes of levels 1 .. l-1 (level l's offset in one image's output)
+  poff[1] = 0;
+  for (uint32_t l = 1; l < levels; ++l) poff[l + 1] = poff[l] + mip_level_pixels(height, width, l, src_components);
+  const size_t per = mip_pyramid_bytes(height, width, levels, src_components);
+  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)src_components;
+  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < per))
+    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
+  if (n_images == 0) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (levels == 1) return ICAMD_OK;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  uint8_t *dst = static_cast<uint8_t *>(d_dst);
+  for (const MipPass &p : mip_plan(height, width, levels, true)) {
+    icamd::MipParams P = {};
+    P.src = p.l0 == 0 ? static_cast<const uint8_t *>(d_src) : dst + poff[p.l0];
+    P.src_image_stride = p.l0 == 0 ? src_image_stride_bytes : dst_image_stride_bytes;
+    P.row_stride = p.l0 == 0 ? row_stride_bytes : p.in_w * (uint32_t)src_components;
+    P.height = p.in_h;
+    P.width = p.in_w;
+    P.pix = dst;
+    P.pix_image_stride = dst_image_stride_bytes;
+    for (uint32_t j = 1; j < p.n; ++j) P.pix_off[j] = poff[p.l0 + j];
+    P.pix_mask = ((1u << p.n) - 1u) & ~1u;
+    ICAMD_HIP(icamd::launch_mip_pass(icamd::kMipPyramidMode, src_components, P, n_images, stream), "launch mip pyramid");
+  }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
+                        uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
+                        size_t out_size) try {
+  if (compressor == ICAMD_COMPRESSOR_PVRTC)
+    return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
+  if (!buffer || !out || height == 0 || width == 0) return ICAMD_FALSE;
+  int codec = 0, comps = 0;
+  bool swap = false;
+  if (!resolve_codec(compressor, format, &codec, &comps, &swap)) return ICAMD_FALSE;  // dxtc.cc:735-750, etc.cc:747-758
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if (out_size != icamd_mip_chain_size(codec, height, width, levels, nullptr)) return ICAMD_FALSE;
+  const size_t stride = (size_t)width * comps + padding_bytes_per_row;
+  if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const size_t in_bytes = (size_t)(height - 1) * stride + (size_t)width * comps;
+  const size_t ws_off = (out_size + 255u) & ~(size_t)255u;
+  const size_t ws = mip_workspace_bytes(codec, height, width, levels, comps, 1);
+  Staging &st = tls_staging();
+  rc = st.ensure(in_bytes, ws_off + ws);
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t s = st.stream;
+  uint8_t *d_out = static_cast<uint8_t *>(st.d_out);
+  ICAMD_HIP(hipMemcpyAsync(st.d_in, buffer, in_bytes, hipMemcpyHostToDevice, s), "H2D copy");
+  rc = icamd_encode_mips_device(codec, etc_strategy, comps, swap, height, width, (uint32_t)stride, levels, 1, 0, 0, st.d_in,
+                                d_out, ws ? d_out + ws_off : nullptr, ws, s);
+  if (rc != ICAMD_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  ICAMD_HIP(hipMemcpyAsync(out, d_out, out_size, hipMemcpyDeviceToHost, s), "D2H copy");
+  ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 

@@ -133,6 +133,24 @@ hipError_t launch_bc45_encode(int codec, int comps, const GridParams &P, hipStre
 hipError_t launch_bc45_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
 const char *bc45_kernel_name(int codec, int comps);
 
+// Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
+// n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of
+// enc_mask: encode level j's blocks to dst + level_off[j]; bit j of pix_mask (j >= 1): write level j's pixels as tight
+// COMPS-byte rows to pix + pix_off[j].  A pass over more than one 128 x 128 tile builds at most local level 6.
+struct MipParams {
+  const uint8_t *src;
+  uint8_t *dst, *pix;
+  uint64_t src_image_stride, dst_image_stride, pix_image_stride;
+  uint64_t level_off[8], pix_off[8];
+  uint32_t height, width, row_stride;
+  uint32_t enc_mask, pix_mask;
+  uint32_t swap_rb;
+  uint32_t tile_row0;  // first tile row of this launch (set by launch_mip_pass)
+};
+constexpr int kMipPyramidMode = -1;  // `mode` of the pixel-pyramid kernels (no encoder)
+// mode: ICAMD_DXT1 / DXT5 / BC4 / BC5 or kMipPyramidMode (ETC1 chains are the pyramid + the ETC1 kernels, ic_capi.hip)
+hipError_t launch_mip_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream);
+
 // Compressed-domain operations on one image's block grid.
 struct BlockOpParams {
   const uint8_t *src;

@@ -88,6 +88,11 @@ class Compressor {
 //   CompressAndPadDevice   one image over a larger block grid             -> icamd_compress_and_pad_device
 //   CompressBatchDevice    n_images equally shaped images in ONE launch, image i at d_buffer + i * src_image_stride_bytes ->
 //                          d_out + i * dst_image_stride_bytes              -> icamd_encode_device
+//   CompressMipChain       host buffer -> levels 0 .. levels-1 of its mip chain, each encoded from its own pixels (the
+//                          2 x 2 truncating pyramid of include/ic_amd.h): images[l] receives exactly the data and metadata
+//                          Compress writes for level l's pixels (padding_bytes_per_row for level 0, 0 below); owned or
+//                          external storage as Compress.  false for PVRTC, a format Compress refuses, levels outside
+//                          1 .. floor(log2(max(height, width))) + 1     -> icamd_compress_mips
 #define ICAMD_DECLARE_DEVICE_EXTENSION()                                                                              \
   bool CompressDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,     \
                       const void *d_buffer, void *d_out, size_t out_size, void *hip_stream);                         \
@@ -96,6 +101,8 @@ class Compressor {
                             size_t out_size, void *hip_stream);                                                      \
   bool CompressBatchDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,\
                            uint32 n_images, const void *d_buffer, size_t src_image_stride_bytes, void *d_out,        \
-                           size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream)
+                           size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream);              \
+  bool CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,     \
+                        const uint8 *buffer, uint32 levels, CompressedImage *images)
 
 #endif  // IMAGE_COMPRESSION_PUBLIC_COMPRESSOR_H_

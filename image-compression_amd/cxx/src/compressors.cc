@@ -365,9 +365,34 @@ bool DeviceBatch(int compressor, int etc_strategy, CompressedImage::Format forma
                                           src_image_stride_bytes, dst_image_stride_bytes, d_buffer, d_out, hip_stream),
                       "icamd_encode_device");
 }
+// Levels 0 .. levels-1 of the mip chain in one fused device pass (icamd_compress_mips), split into one CompressedImage per
+// level with the metadata Compress4x4 gives that level's pixels.
+bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImage::Format format, uint32 height, uint32 width,
+              uint32 padding_bytes_per_row, const uint8 *buffer, uint32 levels, CompressedImage *images) {
+  if (!buffer || !images || height == 0 || width == 0) return false;
+  if (compressor == ICAMD_COMPRESSOR_PVRTC || !icamd_supports_format(compressor, format)) return false;
+  if (levels == 0 || levels > icamd_mip_max_levels(height, width)) return false;
+  std::vector<size_t> offsets(levels + 1);
+  const int codec = compressor == ICAMD_COMPRESSOR_ETC ? ICAMD_ETC1 : (GetNumFormatComponents(format) == 3 ? ICAMD_DXT1 : ICAMD_DXT5);
+  const size_t total = icamd_mip_chain_size(codec, height, width, levels, offsets.data());
+  if (total == 0) return false;
+  for (uint32 l = 0; l < levels; ++l) {
+    const uint32 h = std::max(1u, height >> l), w = std::max(1u, width >> l);
+    const CompressedImage::Metadata metadata(format, name, h, w, 4 * BlocksFor(h), 4 * BlocksFor(w), l ? 0 : padding_bytes_per_row);
+    if (!PrepareImage(metadata, offsets[l + 1] - offsets[l], &images[l])) return false;
+  }
+  std::vector<uint8> chain(total);
+  if (!ReportStatus(icamd_compress_mips(compressor, etc_strategy, format, height, width, padding_bytes_per_row, levels, buffer,
+                                        chain.data(), total),
+                    "icamd_compress_mips"))
+    return false;
+  for (uint32 l = 0; l < levels; ++l)
+    std::memcpy(images[l].GetMutableData(), chain.data() + offsets[l], offsets[l + 1] - offsets[l]);
+  return true;
+}
 }  // namespace
 
-#define ICAMD_DEFINE_DEVICE_EXTENSION(CLASS, COMPRESSOR, STRATEGY)                                                             \
+#define ICAMD_DEFINE_DEVICE_EXTENSION(CLASS, COMPRESSOR, STRATEGY, NAME)                                                           \
   bool CLASS::CompressDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,        \
                              const void *d_buffer, void *d_out, size_t out_size, void *hip_stream) {                           \
     return DeviceOne(COMPRESSOR, STRATEGY, format, height, width, height, width, padding_bytes_per_row, d_buffer, d_out,       \
@@ -384,10 +409,14 @@ bool DeviceBatch(int compressor, int etc_strategy, CompressedImage::Format forma
                                   size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream) {                \
     return DeviceBatch(COMPRESSOR, STRATEGY, format, height, width, padding_bytes_per_row, n_images, d_buffer,                 \
                        src_image_stride_bytes, d_out, dst_image_stride_bytes, out_size_per_image, hip_stream);                 \
+  }                                                                                                                            \
+  bool CLASS::CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,      \
+                               const uint8 *buffer, uint32 levels, CompressedImage *images) {                                  \
+    return MipChain(COMPRESSOR, STRATEGY, NAME, format, height, width, padding_bytes_per_row, buffer, levels, images);       \
   }
-ICAMD_DEFINE_DEVICE_EXTENSION(DxtcCompressor, ICAMD_COMPRESSOR_DXTC, 0)
-ICAMD_DEFINE_DEVICE_EXTENSION(EtcCompressor, ICAMD_COMPRESSOR_ETC, compression_strategy_)
-ICAMD_DEFINE_DEVICE_EXTENSION(PvrtcCompressor, ICAMD_COMPRESSOR_PVRTC, 0)
+ICAMD_DEFINE_DEVICE_EXTENSION(DxtcCompressor, ICAMD_COMPRESSOR_DXTC, 0, "dxtc")
+ICAMD_DEFINE_DEVICE_EXTENSION(EtcCompressor, ICAMD_COMPRESSOR_ETC, compression_strategy_, "etc")
+ICAMD_DEFINE_DEVICE_EXTENSION(PvrtcCompressor, ICAMD_COMPRESSOR_PVRTC, 0, "pvrtc")
 #undef ICAMD_DEFINE_DEVICE_EXTENSION
 
 // ------------------------------------------------------------ transcoder

@@ -358,6 +358,51 @@ size_t icamd_container_size(int container, int codec, uint32_t height, uint32_t 
 int icamd_container_write(int container, int codec, uint32_t height, uint32_t width, uint32_t levels,
                           const uint8_t *const *level_data, const size_t *level_sizes, uint8_t *out, size_t out_size);
 
+/* ---- mip chains (EXTENSION: one source image -> every level of its mip chain, each level encoded from pixels) ----
+ * Level l of a height x width source P_0 is h_l x w_l = max(1, height >> l) x max(1, width >> l) pixels (the container
+ * dimensions above); a full chain has L_max = floor(log2(max(height, width))) + 1 levels (icamd_mip_max_levels).
+ * P_{l+1}[y][x], per channel, is the truncating average (a + b + c + d) / 4 of P_l at (y0, x0), (y0, x1), (y1, x0),
+ * (y1, x1) -- the reference's Average4Uint8Fast, color_util.h:335-343 -- with y0 = 2y, y1 = min(2y + 1, h_l - 1) and
+ * x0, x1 alike.  The pyramid is cascaded (each level from the one above); the last row / column of an odd-sized level is
+ * dropped, not averaged with a replicated copy (clamping happens only where a side is already 1).
+ * The bytes of level l are exactly icamd_encode_device(codec, etc_strategy, src_components, swap_rb, h_l, w_l, h_l, w_l,
+ * w_l * src_components, 1, ...) of P_l -- for DXT1 / DXT5 / ETC1 the reference's Compress of those pixels -- and levels
+ * are packed back to back, largest first: level l starts at offset[l] = sum over k < l of icamd_encoded_size(codec, h_k,
+ * w_k), so that the level views go straight into icamd_container_write.  Averaging is per channel: swap_rb commutes. */
+uint32_t icamd_mip_max_levels(uint32_t height, uint32_t width);  /* 0 for an empty image */
+/* Bytes of one image's chain of `levels` levels; fills level_offsets[0 .. levels] (levels + 1 entries) when non-NULL.
+ * 0 for PVRTC / unknown codecs, an empty image or levels outside 1 .. L_max. */
+size_t icamd_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets);
+/* Device workspace icamd_encode_mips_device needs for that call (0: none; also 0 for arguments it refuses): the pixels of
+ * level 6 (and 12, 18, ...) of every image, src_components bytes each, for chains longer than one pass reaches; for ETC1
+ * the whole pixel pyramid (levels 1 .. levels-1 of every image, about a third of the source). */
+size_t icamd_mip_workspace_size(int codec, int src_components, uint32_t height, uint32_t width, uint32_t levels,
+                                uint32_t n_images);
+/* Encodes levels 0 .. levels-1 of n_images sources (src_image_stride_bytes apart, rows of row_stride_bytes) into d_dst
+ * (dst_image_stride_bytes apart, each image one chain laid out as above).  DXT1 / DXT5 / BC4 / BC5 read the source once:
+ * one fused kernel per pass builds the 2 x 2 pyramid on chip and writes every level's blocks (2 launches for 4096^2, 3 for
+ * 16384^2).  ETC1 has no fused kernel yet: it runs the ETC1 kernels on level 0 and on every level of the pixel pyramid,
+ * which it builds in the workspace (the source is read twice).
+ * Source rules as icamd_encode_device: DXT1 / ETC1 (any strategy) 3 or 4 bytes per pixel, DXT5 4, BC4 1..4, BC5 2..4,
+ * swap_rb only with 3 or 4; any alignment and row padding.  ICAMD_FALSE for null pointers or an empty image;
+ * ICAMD_ERR_ARG for PVRTC2 / PVRTC4 (whole-image encoders: use icamd_mip_pyramid_device, then icamd_encode_device per
+ * level), levels of 0 or more than L_max, a workspace smaller than icamd_mip_workspace_size, or (n_images > 1) image
+ * strides smaller than an image.  No allocation, no synchronisation: it can be captured into a graph. */
+int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, int swap_rb, uint32_t height,
+                             uint32_t width, uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,
+                             void *d_dst, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The pixel pyramid alone: levels 1 .. levels-1 of each image as tight rows of w_l * src_components bytes (1..4), back
+ * to back (level 1 first) -- for PVRTC or uncompressed use.  Same argument rules; levels == 1 writes nothing. */
+int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes,
+                             uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *hip_stream);
+/* Host buffers, Compressor + format as icamd_compress (its ICAMD_FALSE conventions: a format the compressor refuses, or
+ * out_size != icamd_mip_chain_size); out receives the whole chain.  PVRTC: ICAMD_ERR_ARG. */
+int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
+                        uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
+                        size_t out_size);
+
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
 const char *icamd_last_error(void);       /* thread-local message for the last negative status */

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""Device-resident throughput of the fused mip-chain encode (icamd_encode_mips_device, include/ic_amd.h mip-chain section).
+
+Legs: every codec at 16 x 4096^2 RGBA8 (BC4 / BC5 read bytes 0 / 0-1 of the same source), ETC1 at 64 x 1024^2 RGBA8, DXT1 at
+1 x 16384^2 RGBA8.  Three variants per leg:
+  (a) fused   the whole chain through icamd_encode_mips_device
+  (b) level0  level 0 alone through icamd_encode_device
+  (c) unfused level 0 through icamd_encode_device, then icamd_mip_pyramid_device and icamd_encode_device per level
+Method as scripts/bench_bc45.py: untimed warm-up calls, device events around K back-to-back calls, repeated; the median and
+min / max of ms per call.  Algorithmic bytes = source read once + every level's blocks written once, against 8 TB/s.
+Parity: image 0 of (a) against (c) (every level), which the GPU tier pins to the oracle.  PSNR of (a)'s levels against the
+pixel pyramid, and of the compressed-domain chain (icamd_downsample_device per level, DXT1 / DXT5 / ETC1), reported only.
+
+  python scripts/bench_mips.py [--k 10] [--reps 5] [--legs dxt1,dxt5,etc1,bc4,bc5,etc1_1024,dxt1_16384] [--no-psnr]
+One JSON line per leg; exit status 1 if any parity check fails."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import ic_amd_loader  # noqa: E402
+
+pkg = ic_amd_loader.load_package()
+import ic_testlib as T  # noqa: E402
+
+PEAK_BPS = 8e12
+LEGS = {  # name: (codec, n_images, size)
+    "dxt1": (pkg.DXT1, 16, 4096), "dxt5": (pkg.DXT5, 16, 4096), "etc1": (pkg.ETC1, 16, 4096), "bc4": (pkg.BC4, 16, 4096),
+    "bc5": (pkg.BC5, 16, 4096), "etc1_1024": (pkg.ETC1, 64, 1024), "dxt1_16384": (pkg.DXT1, 1, 16384),
+}
+
+
+def time_calls(fn, k, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(k):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / k)
+    return out
+
+
+def psnr(a, b):
+    mse = float(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2))
+    return 99.0 if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--legs", default=",".join(LEGS))
+    ap.add_argument("--no-psnr", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    lib = pkg.lib()
+    bad = False
+    for leg in a.legs.split(","):
+        codec, n, s = LEGS[leg]
+        comps = 4
+        levels = pkg.mip_max_levels(s, s)
+        total, offs = pkg.mip_chain_size(codec, s, s)
+        img0 = T.s_mixed(s, s, comps, index=1).reshape(s, s, comps)
+        src = torch.from_numpy(img0.reshape(-1).copy()).to(dev)
+        src = src.repeat(n) if n > 1 else src
+        out = torch.empty((n, total), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(1, pkg.mip_workspace_size(codec, comps, s, s, levels, n)),), dtype=torch.uint8, device=dev)
+        pyr_per, poffs = pkg.mip_pyramid_size(comps, s, s, levels)
+        pyr = torch.empty((n, pyr_per), dtype=torch.uint8, device=dev)
+        out_c = torch.empty((n, total), dtype=torch.uint8, device=dev)
+        st = pkg._stream_handle()
+        img_bytes = s * s * comps
+
+        def fused():
+            pkg.encode_mips_device(codec, src, s, s, comps, n_images=n, out=out, workspace=ws)
+
+        def level0():
+            lib.icamd_encode_device(codec, 2, comps, 0, s, s, s, s, s * comps, n, img_bytes, total, src.data_ptr(),
+                                    out_c.data_ptr(), st)
+
+        def unfused():
+            level0()
+            lib.icamd_mip_pyramid_device(comps, s, s, s * comps, levels, n, img_bytes, pyr_per, src.data_ptr(), pyr.data_ptr(), st)
+            for l in range(1, levels):
+                lh, lw = pkg.mip_level_shape(s, s, l)
+                lib.icamd_encode_device(codec, 2, comps, 0, lh, lw, lh, lw, lw * comps, n, pyr_per, total,
+                                        pyr.data_ptr() + poffs[l - 1], out_c.data_ptr() + offs[l], st)
+
+        res = {}
+        for name, fn in (("fused", fused), ("level0", level0), ("unfused", unfused)):
+            t = time_calls(fn, a.k, a.reps, a.warmup)
+            res[name] = (statistics.median(t), min(t), max(t))
+        unfused()
+        torch.cuda.synchronize()
+        parity = bool(torch.equal(out[0], out_c[0]))
+        bad |= not parity
+        written = n * total
+        read = n * img_bytes
+        rec = {"leg": leg, "codec": codec, "n_images": n, "size": s, "levels": levels, "parity_fused_vs_unfused": parity}
+        for name, (med, lo, hi) in res.items():
+            rec[name + "_ms"] = round(med, 4)
+            rec[name + "_ms_min_max"] = [round(lo, 4), round(hi, 4)]
+            rec[name + "_mpix_s"] = round(n * s * s / (med * 1e-3) / 1e6, 1)
+        rec["fused_alg_GBps"] = round((read + written) / (res["fused"][0] * 1e-3) / 1e9, 1)
+        rec["fused_frac_8TBps"] = round((read + written) / (res["fused"][0] * 1e-3) / PEAK_BPS, 3)
+        rec["fused_over_level0"] = round(res["fused"][0] / res["level0"][0], 3)
+        rec["unfused_over_fused"] = round(res["unfused"][0] / res["fused"][0], 3)
+        if not a.no_psnr:
+            chain = out[0].cpu().numpy()
+            pyramid = [img0]
+            for l in range(1, levels):
+                pyramid.append(pyr[0, poffs[l - 1]:poffs[l]].cpu().numpy().reshape(*pkg.mip_level_shape(s, s, l), comps))
+            ch = 1 if codec == pkg.BC4 else 2 if codec == pkg.BC5 else 4 if codec == pkg.DXT5 else 3
+            rec["psnr_fused"] = []
+            for l in range(levels):
+                lh, lw = pkg.mip_level_shape(s, s, l)
+                blk = torch.from_numpy(chain[offs[l]:offs[l + 1]].copy()).to(dev)
+                dec = pkg.decode_device(codec, blk, lh, lw).cpu().numpy().reshape(lh, lw, -1)
+                rec["psnr_fused"].append(round(psnr(dec[..., :ch], pyramid[l][..., :ch]), 2))
+            if codec in (pkg.DXT1, pkg.DXT5, pkg.ETC1):
+                comp, fmt = (pkg.COMPRESSOR_ETC, pkg.RGB) if codec == pkg.ETC1 else (pkg.COMPRESSOR_DXTC, pkg.RGB if codec == pkg.DXT1 else pkg.RGBA)
+                c3 = 4 if codec == pkg.DXT5 else 3
+                base = torch.from_numpy(np.ascontiguousarray(img0[..., :c3]).reshape(-1)).to(dev)
+                cur = pkg.encode_device(codec, base, s, s, c3)
+                rec["psnr_compressed_domain"] = []
+                for l in range(levels):
+                    lh, lw = pkg.mip_level_shape(s, s, l)
+                    if l:
+                        cur = pkg.downsample_device(comp, fmt, cur.view(1, -1), *pkg.mip_level_shape(s, s, l - 1))
+                        if cur is None:
+                            break
+                    dec = pkg.decode_device(codec, cur.reshape(-1).contiguous(), lh, lw).cpu().numpy().reshape(lh, lw, -1)
+                    rec["psnr_compressed_domain"].append(round(psnr(dec[..., :ch], pyramid[l][..., :ch]), 2))
+        print(json.dumps(rec), flush=True)
+        del src, out, ws, pyr, out_c
+        torch.cuda.empty_cache()
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
