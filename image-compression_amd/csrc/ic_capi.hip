@@ -110,22 +110,18 @@ struct Staging {
   hipStream_t stream = nullptr, stream2 = nullptr;  // two streams: bands of one image alternate between them
   void *d_in = nullptr, *d_out = nullptr;
   size_t cap_in = 0, cap_out = 0;
-  void *h_in = nullptr, *h_out = nullptr;  // pinned host mirrors (batch workers only)
-  size_t cap_hin = 0, cap_hout = 0;
   // No destructor: a Staging is never destroyed (see TlsStaging below) -- no HIP call may run from a thread_local or
   // static destructor, where the HIP runtime can already be gone.
   void drop() {
     if (d_in) (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
     if (stream) (void)hipStreamDestroy(stream);
     if (stream2) (void)hipStreamDestroy(stream2);
-    d_in = d_out = h_in = h_out = nullptr;
-    cap_in = cap_out = cap_hin = cap_hout = 0;
+    d_in = d_out = nullptr;
+    cap_in = cap_out = 0;
     stream = stream2 = nullptr;
   }
-  int ensure(size_t in_bytes, size_t out_bytes, bool pinned = false) {
+  int ensure(size_t in_bytes, size_t out_bytes) {
     int dev = 0;
     ICAMD_HIP(hipGetDevice(&dev), "hipGetDevice");
     if (dev != device) {  // thread moved to another device: drop the old buffers
@@ -145,18 +141,6 @@ struct Staging {
       d_out = nullptr; cap_out = 0;
       if (hipMalloc(&d_out, out_bytes) != hipSuccess) return fail(ICAMD_ERR_ALLOC, "hipMalloc(output staging)");
       cap_out = out_bytes;
-    }
-    if (pinned && in_bytes > cap_hin) {
-      if (h_in) (void)hipHostFree(h_in);
-      h_in = nullptr; cap_hin = 0;
-      if (hipHostMalloc(&h_in, in_bytes, hipHostMallocDefault) != hipSuccess) return fail(ICAMD_ERR_ALLOC, "hipHostMalloc(input)");
-      cap_hin = in_bytes;
-    }
-    if (pinned && out_bytes > cap_hout) {
-      if (h_out) (void)hipHostFree(h_out);
-      h_out = nullptr; cap_hout = 0;
-      if (hipHostMalloc(&h_out, out_bytes, hipHostMallocDefault) != hipSuccess) return fail(ICAMD_ERR_ALLOC, "hipHostMalloc(output)");
-      cap_hout = out_bytes;
     }
     return ICAMD_OK;
   }
@@ -209,47 +193,6 @@ struct TlsStaging {
 thread_local TlsStaging g_tls_staging;
 Staging &tls_staging() { return g_tls_staging.get(); }
 
-// ---- one large image per call as two concurrent bands (experiment knob) ----
-// ICAMD_SPLIT_SINGLE=1 (read once): icamd_encode_device / icamd_compress_device calls with ONE image of at least
-// ICAMD_SPLIT_SINGLE_MIN_BLOCKS (default 2^20 = one 4096^2 image) 4x4 blocks run as two kernels, the lower band on a per-thread
-// side stream between a fork and a join event.  What it measured is in profiles/r06_ab_single_image_split.log and DESIGN.md 5.
-int split_single_mode() {
-  static const int mode = [] { const char *e = getenv("ICAMD_SPLIT_SINGLE"); return e && e[0] == '1' ? 1 : 0; }();
-  return mode;
-}
-uint64_t split_single_min_blocks() {
-  static const uint64_t n = [] {
-    const char *e = getenv("ICAMD_SPLIT_SINGLE_MIN_BLOCKS");
-    const long long v = e && *e ? atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : (1ull << 20);
-  }();
-  return n;
-}
-struct SplitLane {
-  int device = -1;
-  hipStream_t side = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-// The calling thread's side stream and events on the current device (created on first use, re-created when the thread moves to
-// another device; never destroyed: no HIP call may run from a thread_local destructor).  nullptr: could not be created.
-SplitLane *tls_split_lane() {
-  static thread_local SplitLane lane;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (lane.device != dev || !lane.side) {
-    lane = SplitLane();
-    if (hipStreamCreateWithFlags(&lane.side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&lane.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&lane.join, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      lane = SplitLane();
-      return nullptr;
-    }
-    lane.device = dev;
-  }
-  return &lane;
-}
-
 int require_device() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -258,11 +201,11 @@ int require_device() {
 }
 
 // What (compressor, format) encodes to; returns false when the reference's Compress would.
-bool resolve_codec(int compressor, int format, int *codec, int *comps, bool *swap) {
+bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr, bool *swap = nullptr) {
   const int c = format_components(format);
   if (c == 0) return false;
-  *comps = c;
-  *swap = format_swaps(format);
+  if (comps) *comps = c;
+  if (swap) *swap = format_swaps(format);
   if (compressor == ICAMD_COMPRESSOR_DXTC) {  // dxtc.cc:741-749: 3 components -> DXT1, else DXT5
     *codec = c == 3 ? ICAMD_DXT1 : ICAMD_DXT5;
     return true;
@@ -275,19 +218,37 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps, bool *swa
   return false;
 }
 
-bool blockop_codec(int compressor, int format, int *codec) {
-  int comps;
-  bool swap;
-  return resolve_codec(compressor, format, codec, &comps, &swap);
+// Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 3 or 4, DXT5 4, BC4 1..4, BC5 2..4.
+bool codec_accepts_components(int codec, int comps) {
+  switch (codec) {
+    case ICAMD_DXT1: case ICAMD_ETC1: return comps == 3 || comps == 4;
+    case ICAMD_DXT5: return comps == 4;
+    case ICAMD_BC4: return comps >= 1 && comps <= 4;
+    case ICAMD_BC5: return comps >= 2 && comps <= 4;
+  }
+  return false;
 }
 
-// host-buffer wrappers: stage in, run, stage out
+// The sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650): a square power of two of at least 8 x 8 (for a square
+// power of two, width % 8 == 0 && height % 4 == 0 is width >= 8).  The reference sizes its output with the uint32 product
+// width * height / 4 (pvrtc.cc:631-634), which wraps to 0 at 65536^2 -- it would then write 2^30 bytes into a zero-byte
+// buffer; refused here (the kernels also index pixels with 32 bits).
+bool pvrtc_size_ok(uint32_t height, uint32_t width) { return is_pow2(width) && width == height && width >= 8u && width < 65536u; }
+
+// Compressor::Compress of PVRTC, device or host buffers (pvrtc.cc:636-667): no row padding, the reference's output size.
+// `format` is deliberately not validated (neither does the reference): the buffer is read as RGBA8888, pvrtc.cc:664.
+bool pvrtc_compress_ok(uint32_t height, uint32_t width, uint32_t padding_bytes_per_row, size_t out_size) {
+  return pvrtc_size_ok(height, width) && padding_bytes_per_row == 0 && out_size == (size_t)(width * height / 4);
+}
+
+// host-buffer wrappers: stage in, run, stage out.  The device output holds dev_out_bytes (>= out_size, of which the first
+// out_size come back); in_place: the result is read back from the input buffer.
 template <typename F>
-int staged_blockop(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_size, bool in_place, F &&run) {
+int staged_blockop(Staging &st, const void *in, size_t in_size, void *out, size_t out_size, size_t dev_out_bytes,
+                   bool in_place, F &&run) {
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  Staging &st = tls_staging();
-  rc = st.ensure(std::max<size_t>(in_size, 1), std::max<size_t>(out_size, 1));
+  rc = st.ensure(std::max<size_t>(in_size, 1), std::max<size_t>(dev_out_bytes, 1));
   if (rc != ICAMD_OK) return rc;
   hipStream_t s = st.stream;
   ICAMD_HIP(hipMemcpyAsync(st.d_in, in, in_size, hipMemcpyHostToDevice, s), "H2D copy");
@@ -301,46 +262,43 @@ int staged_blockop(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_s
   return ICAMD_OK;
 }
 
-// PVRTC branch of icamd_encode_device.  internal_workspace: the call comes from the library's own host-buffer path
-// (its staging stream), which must not borrow the workspace a caller registered for its own streams / graphs.
-int pvrtc_encode_device_impl(int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes,
-                             uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
-                             const void *d_src, void *d_dst, hipStream_t stream, bool internal_workspace) {
-  // preconditions of PvrtcCompressor::Compress, pvrtc.cc:636-650 (source always read as RGBA8888)
-  if (!is_pow2(width) || !is_pow2(height) || width != height || width % 8 || height % 4) return ICAMD_FALSE;
-  // the reference sizes its output with the uint32 product width * height / 4 (pvrtc.cc:631-634), which wraps to 0 at
-  // 65536^2 -- it would then write 2^30 bytes into a zero-byte buffer; refused here
-  if (width >= 65536u) return ICAMD_FALSE;
-  if (src_components != 4 || row_stride_bytes != width * 4u) return ICAMD_FALSE;
-  if (reinterpret_cast<uintptr_t>(d_src) % 16u || reinterpret_cast<uintptr_t>(d_dst) % 8u ||
-      (n_images > 1 && (src_image_stride_bytes % 16u || dst_image_stride_bytes % 8u)))
-    return fail(ICAMD_ERR_ARG, "PVRTC: source must be 16-byte aligned, output 8-byte aligned");
+icamd::PvrtcParams pvrtc_params(const void *d_src, void *d_dst, uint32_t size, uint32_t n_images, size_t src_image_stride_bytes,
+                                size_t dst_image_stride_bytes) {
   icamd::PvrtcParams P;
   P.src = static_cast<const uint8_t *>(d_src);
   P.dst = static_cast<uint8_t *>(d_dst);
   P.src_image_stride = src_image_stride_bytes;
   P.dst_image_stride = dst_image_stride_bytes;
-  P.size = width;
-  P.log2_size = ilog2(width);
+  P.size = size;
+  P.log2_size = ilog2(size);
   P.n_images = n_images;
+  return P;
+}
+
+// PVRTC branch of icamd_encode_device.  internal_workspace: the call comes from the library's own host-buffer path
+// (its staging stream), which must not borrow the workspace a caller registered for its own streams / graphs.
+// PVRTC4 is an EXTENSION (parity unpinned, include/ic_amd.h): PVRTC1 4 bpp under the same preconditions.
+int pvrtc_encode_device_impl(int codec, int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes,
+                             uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, hipStream_t stream, bool internal_workspace) {
+  // preconditions of PvrtcCompressor::Compress (source always read as RGBA8888, no row padding)
+  if (!pvrtc_size_ok(height, width)) return ICAMD_FALSE;
+  if (src_components != 4 || row_stride_bytes != width * 4u) return ICAMD_FALSE;
+  if (reinterpret_cast<uintptr_t>(d_src) % 16u || reinterpret_cast<uintptr_t>(d_dst) % 8u ||
+      (n_images > 1 && (src_image_stride_bytes % 16u || dst_image_stride_bytes % 8u)))
+    return fail(ICAMD_ERR_ARG, "PVRTC: source must be 16-byte aligned, output 8-byte aligned");
+  icamd::PvrtcParams P = pvrtc_params(d_src, d_dst, width, n_images, src_image_stride_bytes, dst_image_stride_bytes);
   P.internal_workspace = internal_workspace;
-  ICAMD_HIP(icamd::launch_pvrtc2(P, stream), "launch pvrtc2");
+  if (codec == ICAMD_PVRTC4)
+    ICAMD_HIP(icamd::launch_pvrtc4(P, stream), "launch pvrtc4");
+  else
+    ICAMD_HIP(icamd::launch_pvrtc2(P, stream), "launch pvrtc2");
   return ICAMD_OK;
 }
 
-// EXTENSION (include/ic_amd.h ICAMD_BC4): BC4 from 1..4-byte sources, BC5 from 2..4-byte ones; R = byte 0 (byte 2 when swap_rb
-// and the source has 3 or 4 bytes), G = byte 1.  The argument checks come before any device work.
-int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_height,
-                            uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
-                            size_t dst_image_stride_bytes, const void *d_src, void *d_dst, hipStream_t stream) {
-  if (src_components < (codec == ICAMD_BC5 ? 2 : 1) || src_components > 4)
-    return fail(ICAMD_ERR_ARG, codec == ICAMD_BC5 ? "BC5 needs 2, 3 or 4 source components" : "BC4 needs 1 to 4 source components");
-  if (swap_rb && src_components < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
-  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components)
-    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
-  if (n_images == 0) return ICAMD_OK;
-  const int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
+icamd::GridParams grid_params(const void *d_src, void *d_dst, uint32_t height, uint32_t width, uint32_t grid_height,
+                              uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
+                              size_t dst_image_stride_bytes, int swap_rb, uint32_t etc_strategy) {
   icamd::GridParams P;
   P.src = static_cast<const uint8_t *>(d_src);
   P.dst = static_cast<uint8_t *>(d_dst);
@@ -348,14 +306,113 @@ int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t
   P.dst_image_stride = dst_image_stride_bytes;
   P.height = height;
   P.width = width;
-  P.block_rows = num_blocks4(std::max(height, grid_height));
+  P.block_rows = num_blocks4(std::max(height, grid_height));  // helper.h:487-488,501-502
   P.block_cols = num_blocks4(std::max(width, grid_width));
   P.row_stride = row_stride_bytes;
   P.n_images = n_images;
   P.swap_rb = swap_rb ? 1u : 0u;
-  P.etc_strategy = P.log2_tile_cols = P.tile_row0 = P.force_gather = 0;
+  P.etc_strategy = etc_strategy;
+  P.log2_tile_cols = P.tile_row0 = P.force_gather = 0;
+  return P;
+}
+
+// EXTENSION (include/ic_amd.h ICAMD_BC4): BC4 from 1..4-byte sources, BC5 from 2..4-byte ones; R = byte 0 (byte 2 when swap_rb
+// and the source has 3 or 4 bytes), G = byte 1.  The argument checks come before any device work.
+int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_height,
+                            uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
+                            size_t dst_image_stride_bytes, const void *d_src, void *d_dst, hipStream_t stream) {
+  if (!codec_accepts_components(codec, src_components))
+    return fail(ICAMD_ERR_ARG, codec == ICAMD_BC5 ? "BC5 needs 2, 3 or 4 source components" : "BC4 needs 1 to 4 source components");
+  if (swap_rb && src_components < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (n_images == 0) return ICAMD_OK;
+  const int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, swap_rb, 0);
   ICAMD_HIP(icamd::launch_bc45_encode(codec, src_components, P, stream), codec == ICAMD_BC5 ? "launch bc5" : "launch bc4");
   return ICAMD_OK;
+}
+
+// The compressed-domain batches (pad, downsample) once their arguments are checked: P holds the block grids, and
+// as many images go in one launch as the 32-bit block index allows.
+int blockop_batch(hipError_t (*launch)(int, const icamd::BlockOpParams &, hipStream_t), const char *what, int codec,
+                  icamd::BlockOpParams &P, int etc_strategy, uint32_t src_height, uint32_t src_width, uint32_t n_images,
+                  const void *d_blocks, size_t src_image_stride_bytes, void *d_out, size_t dst_image_stride_bytes,
+                  void *hip_stream) {
+  if (n_images == 0) return ICAMD_OK;  // (after the checks: a call the reference would refuse is refused for any count)
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const uint64_t per = (uint64_t)P.out_rows * P.out_cols;
+  if (per >= (1ull << 31)) return fail(ICAMD_ERR_ARG, "more than 2^31 blocks in one image");
+  P.etc_strategy = (uint32_t)etc_strategy;
+  P.src_height = src_height; P.src_width = src_width;
+  P.div_out_cols = icamd::make_fastdiv(P.out_cols);
+  P.out_per_image = (uint32_t)per;
+  P.div_out_per_image = icamd::make_fastdiv(P.out_per_image);
+  P.src_image_stride = src_image_stride_bytes;
+  P.dst_image_stride = dst_image_stride_bytes;
+  const uint64_t group = std::max<uint64_t>(1, ((1ull << 31) - 1) / per);
+  for (uint64_t first = 0; first < n_images; first += group) {
+    const uint64_t count = std::min<uint64_t>(group, n_images - first);
+    P.src = static_cast<const uint8_t *>(d_blocks) + first * src_image_stride_bytes;
+    P.dst = static_cast<uint8_t *>(d_out) + first * dst_image_stride_bytes;
+    P.n_images = (uint32_t)count;
+    P.total_out = (uint32_t)(per * count);
+    ICAMD_HIP(launch(codec, P, static_cast<hipStream_t>(hip_stream)), what);
+  }
+  return ICAMD_OK;
+}
+
+// The device list of a batch entry point: every ordinal must name a visible device (*visible: how many there are).
+int check_device_list(const char *entry, const int *devices, int n_devices, int *visible) {
+  ICAMD_HIP(hipGetDeviceCount(visible), "hipGetDeviceCount");
+  for (int d = 0; d < n_devices; ++d)
+    if (devices[d] < 0 || devices[d] >= *visible) {
+      char text[kErrorChars];
+      std::snprintf(text, sizeof text, "%s: bad device ordinal", entry);
+      return fail(ICAMD_ERR_ARG, text);
+    }
+  return ICAMD_OK;
+}
+
+// One worker thread per device-list entry, but no more than there are images: work(d, local, error) does images d,
+// d + n_devices, ... -- it writes each one's status to local[i] and a failure's text to `error`, and lets no exception out.
+// statuses[] (optional) receives every image's status; the result is the first non-OK one in image order, and the
+// error text that of the first worker that has one.
+template <typename Work>
+int run_workers(const char *entry, int n_devices, uint32_t n_images, int *statuses, Work &&work) {
+  std::vector<int> local(n_images, ICAMD_OK);
+  std::vector<WorkerError> errors((size_t)n_devices);
+  std::vector<std::thread> workers;
+  workers.reserve((size_t)n_devices);
+  int not_started_from = n_devices;  // list entries from here on have no worker (thread creation failed)
+  {
+    JoinAll join_on_every_path_out{workers};
+    for (int d = 0; d < n_devices && (uint32_t)d < n_images; ++d) {
+      try {
+        workers.emplace_back([&, d]() noexcept { work(d, local, errors[(size_t)d]); });
+      } catch (...) {  // std::system_error from the thread's creation (or bad_alloc): the workers started so far finish
+        (void)abi_exception();
+        not_started_from = d;
+        break;
+      }
+    }
+  }  // all started workers joined
+  for (int d = not_started_from; d < n_devices; ++d) {
+    for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = ICAMD_ERR_ALLOC;
+    std::snprintf(errors[(size_t)d].text, kErrorChars, "%s: could not start a worker thread", entry);
+  }
+  int first = ICAMD_OK;
+  for (uint32_t i = 0; i < n_images; ++i) {
+    if (statuses) statuses[i] = local[i];
+    if (first == ICAMD_OK && local[i] != ICAMD_OK) first = local[i];
+  }
+  if (first < 0)
+    for (const WorkerError &e : errors)
+      if (!e.empty()) { set_last_error(e.text); break; }
+  return first;
 }
 
 
@@ -407,10 +464,23 @@ size_t mip_workspace_bytes(int codec, uint32_t h, uint32_t w, uint32_t levels, i
   return total;
 }
 int mip_check_components(int codec, int comps, int swap_rb) {
-  const bool ok = codec == ICAMD_DXT5 ? comps == 4 : (codec == ICAMD_DXT1 || codec == ICAMD_ETC1) ? comps == 3 || comps == 4
-                : codec == ICAMD_BC4 ? comps >= 1 && comps <= 4 : comps >= 2 && comps <= 4;
-  if (!ok) return fail(ICAMD_ERR_ARG, "mip chain: source components not accepted by this codec (as icamd_encode_device)");
+  if (!codec_accepts_components(codec, comps))
+    return fail(ICAMD_ERR_ARG, "mip chain: source components not accepted by this codec (as icamd_encode_device)");
   if (swap_rb && comps < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
+  return ICAMD_OK;
+}
+// The geometry checks of the mip entry points: the level count, the row stride, and (n_images > 1) the image strides
+// against one image's source and output -- its encoded chain, or its pixel pyramid when codec is icamd::kMipPyramidMode.
+int mip_check_geometry(int codec, int comps, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                       uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes) {
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)comps) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)comps;
+  const size_t dst_bytes = codec == icamd::kMipPyramidMode ? mip_pyramid_bytes(height, width, levels, comps)
+                                                           : icamd_mip_chain_size(codec, height, width, levels, nullptr);
+  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < dst_bytes))
+    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
   return ICAMD_OK;
 }
 }  // namespace
@@ -467,93 +537,35 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                         const void *d_src, void *d_dst, void *hip_stream) try {
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   if (codec == ICAMD_BC4 || codec == ICAMD_BC5)
     return bc45_encode_device_impl(codec, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
-                                   n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst,
-                                   static_cast<hipStream_t>(hip_stream));
+                                   n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, stream);
   if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
 
-  if (codec == ICAMD_PVRTC2)
-    return pvrtc_encode_device_impl(src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
+  if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
+    return pvrtc_encode_device_impl(codec, src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
                                     dst_image_stride_bytes, d_src, d_dst, stream, false);
-  if (codec == ICAMD_PVRTC4) {
-    // EXTENSION (parity unpinned, include/ic_amd.h): PVRTC1 4 bpp under the preconditions of PvrtcCompressor::Compress
-    // (pvrtc.cc:636-650: square power of two, RGBA8888, no row padding), at least 8 x 8
-    if (!is_pow2(width) || width != height || width < 8u || width >= 65536u) return ICAMD_FALSE;
-    if (src_components != 4 || row_stride_bytes != width * 4u) return ICAMD_FALSE;
-    if (reinterpret_cast<uintptr_t>(d_src) % 16u || reinterpret_cast<uintptr_t>(d_dst) % 8u ||
-        (n_images > 1 && (src_image_stride_bytes % 16u || dst_image_stride_bytes % 8u)))
-      return fail(ICAMD_ERR_ARG, "PVRTC: source must be 16-byte aligned, output 8-byte aligned");
-    icamd::PvrtcParams P;
-    P.src = static_cast<const uint8_t *>(d_src);
-    P.dst = static_cast<uint8_t *>(d_dst);
-    P.src_image_stride = src_image_stride_bytes;
-    P.dst_image_stride = dst_image_stride_bytes;
-    P.size = width;
-    P.log2_size = ilog2(width);
-    P.n_images = n_images;
-    ICAMD_HIP(icamd::launch_pvrtc4(P, stream), "launch pvrtc4");
-    return ICAMD_OK;
-  }
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1) return fail(ICAMD_ERR_ARG, "unknown codec");
-  if (codec == ICAMD_DXT5 && src_components != 4) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
+  if (!codec_accepts_components(codec, src_components)) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
   if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
 
-  icamd::GridParams P;
-  P.src = static_cast<const uint8_t *>(d_src);
-  P.dst = static_cast<uint8_t *>(d_dst);
-  P.src_image_stride = src_image_stride_bytes;
-  P.dst_image_stride = dst_image_stride_bytes;
-  P.height = height;
-  P.width = width;
-  P.block_rows = num_blocks4(std::max(height, grid_height));  // helper.h:487-488,501-502
-  P.block_cols = num_blocks4(std::max(width, grid_width));
-  P.row_stride = row_stride_bytes;
-  P.n_images = n_images;
-  P.swap_rb = swap_rb ? 1u : 0u;
-  P.etc_strategy = (uint32_t)etc_strategy;
-  P.log2_tile_cols = P.tile_row0 = P.force_gather = 0;
-  auto launch = [&](const icamd::GridParams &G, hipStream_t s) {
-    return codec == ICAMD_ETC1 ? icamd::launch_etc1(src_components, G, s) : icamd::launch_dxt(codec, src_components, G, s);
-  };
-  // ONE large image per call: optionally as two bands of block rows, the second on a side stream that is
-  // forked from and joined back into the caller's stream by events (legal under stream capture too).  Off by default: see
-  // split_single_mode() for what it measured.
-  if (n_images == 1 && split_single_mode() != 0 && (uint64_t)P.block_rows * P.block_cols >= split_single_min_blocks() && P.block_rows >= 2) {
-    SplitLane *lane = tls_split_lane();
-    if (lane) {
-      const uint32_t top = P.block_rows / 2u;
-      icamd::GridParams A = P, B = P;
-      A.block_rows = top;
-      A.height = std::min(height, top * 4u);
-      B.block_rows = P.block_rows - top;
-      B.height = height > top * 4u ? height - top * 4u : 0u;
-      if (B.height != 0) {  // (a CompressAndPad grid whose lower band lies wholly below the image is not split)
-        B.src = P.src + (size_t)top * 4u * row_stride_bytes;
-        B.dst = P.dst + (size_t)top * P.block_cols * icamd::codec_block_bytes(codec);
-        ICAMD_HIP(hipEventRecord(lane->fork, stream), "split: fork event");
-        ICAMD_HIP(hipStreamWaitEvent(lane->side, lane->fork, 0), "split: fork wait");
-        ICAMD_HIP(launch(B, lane->side), "launch (lower band)");
-        ICAMD_HIP(launch(A, stream), "launch (upper band)");
-        ICAMD_HIP(hipEventRecord(lane->join, lane->side), "split: join event");
-        ICAMD_HIP(hipStreamWaitEvent(stream, lane->join, 0), "split: join wait");
-        return ICAMD_OK;
-      }
-    }
-  }
-  ICAMD_HIP(launch(P, stream), codec == ICAMD_ETC1 ? "launch etc1" : "launch dxt");
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, swap_rb, (uint32_t)etc_strategy);
+  if (codec == ICAMD_ETC1)
+    ICAMD_HIP(icamd::launch_etc1(src_components, P, stream), "launch etc1");
+  else
+    ICAMD_HIP(icamd::launch_dxt(codec, src_components, P, stream), "launch dxt");
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 
 int icamd_pvrtc2_encode_region_device(uint32_t size, uint32_t first_block, uint32_t n_blocks, const void *d_src,
                                       void *d_dst_region, void *hip_stream) try {
   if (!d_src || !d_dst_region || n_blocks == 0) return ICAMD_FALSE;
-  if (!is_pow2(size) || size < 8) return ICAMD_FALSE;  // pvrtc.cc:640-646
-  if (size >= 65536u) return ICAMD_FALSE;              // as icamd_encode_device: the kernels index pixels with 32 bits
+  if (!pvrtc_size_ok(size, size)) return ICAMD_FALSE;  // as icamd_encode_device
   const uint64_t blocks = (uint64_t)(size / 8) * (size / 4);
   if (!is_pow2(n_blocks) || (first_block & (n_blocks - 1u)) != 0 || (uint64_t)first_block + n_blocks > blocks)
     return fail(ICAMD_ERR_ARG, "PVRTC region must be a power-of-two, aligned range of the image's blocks");
@@ -561,13 +573,7 @@ int icamd_pvrtc2_encode_region_device(uint32_t size, uint32_t first_block, uint3
     return fail(ICAMD_ERR_ARG, "PVRTC: source must be 16-byte aligned, output 8-byte aligned");
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  icamd::PvrtcParams P;
-  P.src = static_cast<const uint8_t *>(d_src);
-  P.dst = static_cast<uint8_t *>(d_dst_region);
-  P.src_image_stride = P.dst_image_stride = 0;
-  P.size = size;
-  P.log2_size = ilog2(size);
-  P.n_images = 1;
+  icamd::PvrtcParams P = pvrtc_params(d_src, d_dst_region, size, 1, 0, 0);
   P.region_first = first_block;
   P.region_blocks = n_blocks;
   ICAMD_HIP(icamd::launch_pvrtc2(P, static_cast<hipStream_t>(hip_stream)), "launch pvrtc2 region");
@@ -642,24 +648,13 @@ int icamd_compress_device(int compressor, int etc_strategy, int format,
                           uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
                           const void *d_buffer, void *d_out, size_t out_size, void *hip_stream) try {
   if (compressor == ICAMD_COMPRESSOR_PVRTC) {
-    // pvrtc.cc:636-667.  `format` is deliberately not validated (neither does the reference).
-    if (!d_buffer || !d_out || height == 0 || width == 0) return ICAMD_FALSE;
-    if (!is_pow2(width) || !is_pow2(height) || width != height) return ICAMD_FALSE;
-    if (padding_bytes_per_row != 0) return ICAMD_FALSE;
-    if (width % 8 != 0 || height % 4 != 0) return ICAMD_FALSE;
-    if (width >= 65536u) return ICAMD_FALSE;  // the reference's uint32 width * height / 4 wraps (see pvrtc_encode_device_impl)
-    if (out_size != (size_t)(width * height / 4)) return ICAMD_FALSE;
+    if (!d_buffer || !d_out || !pvrtc_compress_ok(height, width, padding_bytes_per_row, out_size)) return ICAMD_FALSE;
     return icamd_encode_device(ICAMD_PVRTC2, 0, 4, 0, height, width, height, width, width * 4u, 1, 0, 0,
                                d_buffer, d_out, hip_stream);
   }
   return icamd_compress_and_pad_device(compressor, etc_strategy, format, height, width, height, width,
                                        padding_bytes_per_row, d_buffer, d_out, out_size, hip_stream);
 } ICAMD_ABI_CATCH
-
-// Measured on the MI355X box (r01, 32 x 2048^2 kRGB -> DXT1, workers on one device): pageable copies 21 GB/s with one
-// worker; page-locked mirrors 10 / 14 / 20 / 22 GB/s with 1 / 2 / 4 / 8 workers -- the extra CPU memcpy costs more
-// than the asynchronous DMA gains, so the batch path keeps the pageable copies.
-constexpr bool kBatchPinnedStaging = false;
 
 // Source bytes per band of the host-buffer pipeline (whole block rows): the kernel and the D2H copy of band i run
 // underneath the H2D copy of band i+1.  Measured on the MI355X box (r02, one 4096^2 kRGB image = 48 MiB, pageable
@@ -673,10 +668,11 @@ constexpr size_t kHostBandBytes = (size_t)32 << 20;
 // of whole block rows -- blocks are independent and stored row-major (helper.h:202-214), so a band is an image of its
 // own and its blocks are one contiguous byte range of the output -- and band i's H2D copy, kernel and D2H copy are
 // enqueued on stream i % 2: the copy engines and the kernel of consecutive bands overlap.  Caller buffers that are
-// page-locked (icamd_host_register / hipHostMalloc) are DMA-ed directly at the PCIe rate; pageable ones go through the
-// runtime's own staging.  PVRTC (toroidal neighbourhood, Z-order output) is staged whole.
-// `pinned`: copy through the Staging's page-locked mirrors (batch workers only, see above).
-static int compress_host_common(Staging &st, bool pinned, bool and_pad, int compressor, int etc_strategy, int format,
+// page-locked (icamd_host_register, or allocated pinned) are DMA-ed directly at the PCIe rate; pageable ones go through the
+// runtime's own staging.  PVRTC (toroidal neighbourhood, Z-order output) is staged whole.  Batch workers copy from
+// pageable memory too: page-locked mirrors measured 10 / 14 / 20 / 22 GB/s with 1 / 2 / 4 / 8 workers against 21 GB/s
+// for one pageable worker (r01, 32 x 2048^2 kRGB -> DXT1) -- the extra CPU memcpy costs more than the DMA gains.
+static int compress_host_common(Staging &st, bool and_pad, int compressor, int etc_strategy, int format,
                                 uint32_t height, uint32_t width, uint32_t padded_height, uint32_t padded_width,
                                 uint32_t padding_bytes_per_row, const uint8_t *buffer, uint8_t *out,
                                 size_t out_size) {
@@ -687,85 +683,65 @@ static int compress_host_common(Staging &st, bool pinned, bool and_pad, int comp
   uint32_t gh = height, gw = width;
   if (pvrtc) {
     if (and_pad) return ICAMD_FALSE;  // pvrtc.cc:684-691
-    // pvrtc.cc:636-667
-    if (!is_pow2(width) || !is_pow2(height) || width != height || padding_bytes_per_row != 0) return ICAMD_FALSE;
-    if (width % 8 != 0 || height % 4 != 0) return ICAMD_FALSE;
-    if (width >= 65536u) return ICAMD_FALSE;  // the reference's uint32 width * height / 4 wraps (see pvrtc_encode_device_impl)
-    if (out_size != (size_t)(width * height / 4)) return ICAMD_FALSE;
+    if (!pvrtc_compress_ok(height, width, padding_bytes_per_row, out_size)) return ICAMD_FALSE;
   } else {
     if (!resolve_codec(compressor, format, &codec, &comps, &swap)) return ICAMD_FALSE;  // dxtc.cc:735-750, etc.cc:747-758
     gh = std::max(height, padded_height);
     gw = std::max(width, padded_width);
     if (out_size != icamd_encoded_size(codec, gh, gw)) return ICAMD_FALSE;  // compressor4x4_helper.cc:34-41
   }
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
   const size_t stride = (size_t)width * comps + padding_bytes_per_row;
-  if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
   // the reference never touches the padding after the LAST row (pixel4x4.h:47-48 addresses row * stride + col)
   const size_t in_bytes = (size_t)(height - 1) * stride + (size_t)width * comps;
-  rc = st.ensure(in_bytes, std::max<size_t>(out_size, 1), pinned);
+  if (pvrtc)  // (no row padding: the stride fits 32 bits)
+    return staged_blockop(st, buffer, in_bytes, out, out_size, out_size, false, [&](void *din, void *dout, hipStream_t s) {
+      return pvrtc_encode_device_impl(ICAMD_PVRTC2, 4, height, width, width * 4u, 1, 0, 0, din, dout, s, true);
+    });
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
+  rc = st.ensure(in_bytes, std::max<size_t>(out_size, 1));
   if (rc != ICAMD_OK) return rc;
   uint8_t *d_in = static_cast<uint8_t *>(st.d_in), *d_out = static_cast<uint8_t *>(st.d_out);
-  const uint8_t *h_src = buffer;
-  uint8_t *h_dst = out;
-  if (pinned) {
-    std::memcpy(st.h_in, buffer, in_bytes);
-    h_src = static_cast<const uint8_t *>(st.h_in);
-    h_dst = static_cast<uint8_t *>(st.h_out);
+  const uint32_t block_bytes = icamd::codec_block_bytes(codec);
+  const uint32_t img_block_rows = num_blocks4(height), grid_block_rows = num_blocks4(gh), block_cols = num_blocks4(gw);
+  uint64_t band_rows = std::max<uint64_t>(1, kHostBandBytes / (4u * stride));  // block rows per band
+  if (band_rows * 2 > img_block_rows) band_rows = img_block_rows;               // small images: one band
+  int status = ICAMD_OK;
+  uint32_t band = 0;
+  for (uint64_t r0 = 0; r0 < img_block_rows && status == ICAMD_OK; r0 += band_rows, ++band) {
+    const bool last = r0 + band_rows >= img_block_rows;
+    const uint32_t rows_b = (uint32_t)(last ? img_block_rows - r0 : band_rows);        // block rows with pixels
+    const uint32_t h_b = (uint32_t)std::min<uint64_t>((uint64_t)rows_b * 4u, height - r0 * 4u);
+    const uint32_t grid_rows_b = last ? (uint32_t)(grid_block_rows - r0) : rows_b;     // + the pad rows below the image
+    const size_t src_off = (size_t)r0 * 4u * stride;
+    const size_t src_len = (size_t)(h_b - 1) * stride + (size_t)width * comps;
+    const size_t dst_off = (size_t)r0 * block_cols * block_bytes, dst_len = (size_t)grid_rows_b * block_cols * block_bytes;
+    hipStream_t s = (band & 1u) ? st.stream2 : st.stream;
+    hipError_t e = hipMemcpyAsync(d_in + src_off, buffer + src_off, src_len, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) { status = fail(ICAMD_ERR_HIP, "H2D copy", e); break; }
+    status = icamd_encode_device(codec, etc_strategy, comps, swap, h_b, width, grid_rows_b * 4u, gw, (uint32_t)stride, 1, 0,
+                                 0, d_in + src_off, d_out + dst_off, s);
+    if (status != ICAMD_OK) break;
+    e = hipMemcpyAsync(out + dst_off, d_out + dst_off, dst_len, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) status = fail(ICAMD_ERR_HIP, "D2H copy", e);
   }
-  if (pvrtc) {
-    hipStream_t s = st.stream;
-    ICAMD_HIP(hipMemcpyAsync(d_in, h_src, in_bytes, hipMemcpyHostToDevice, s), "H2D copy");
-    rc = pvrtc_encode_device_impl(4, height, width, width * 4u, 1, 0, 0, d_in, d_out, s, true);
-    if (rc != ICAMD_OK) {
-      (void)hipStreamSynchronize(s);
-      return rc;
-    }
-    ICAMD_HIP(hipMemcpyAsync(h_dst, d_out, out_size, hipMemcpyDeviceToHost, s), "D2H copy");
-    ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
-  } else {
-    const uint32_t block_bytes = icamd::codec_block_bytes(codec);
-    const uint32_t img_block_rows = num_blocks4(height), grid_block_rows = num_blocks4(gh), block_cols = num_blocks4(gw);
-    uint64_t band_rows = std::max<uint64_t>(1, kHostBandBytes / (4u * stride));  // block rows per band
-    if (band_rows * 2 > img_block_rows) band_rows = img_block_rows;               // small images: one band
-    int status = ICAMD_OK;
-    uint32_t band = 0;
-    for (uint64_t r0 = 0; r0 < img_block_rows && status == ICAMD_OK; r0 += band_rows, ++band) {
-      const bool last = r0 + band_rows >= img_block_rows;
-      const uint32_t rows_b = (uint32_t)(last ? img_block_rows - r0 : band_rows);        // block rows with pixels
-      const uint32_t h_b = (uint32_t)std::min<uint64_t>((uint64_t)rows_b * 4u, height - r0 * 4u);
-      const uint32_t grid_rows_b = last ? (uint32_t)(grid_block_rows - r0) : rows_b;     // + the pad rows below the image
-      const size_t src_off = (size_t)r0 * 4u * stride;
-      const size_t src_len = (size_t)(h_b - 1) * stride + (size_t)width * comps;
-      const size_t dst_off = (size_t)r0 * block_cols * block_bytes, dst_len = (size_t)grid_rows_b * block_cols * block_bytes;
-      hipStream_t s = (band & 1u) ? st.stream2 : st.stream;
-      hipError_t e = hipMemcpyAsync(d_in + src_off, h_src + src_off, src_len, hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) { status = fail(ICAMD_ERR_HIP, "H2D copy", e); break; }
-      status = icamd_encode_device(codec, etc_strategy, comps, swap, h_b, width, grid_rows_b * 4u, gw, (uint32_t)stride, 1, 0,
-                                   0, d_in + src_off, d_out + dst_off, s);
-      if (status != ICAMD_OK) break;
-      e = hipMemcpyAsync(h_dst + dst_off, d_out + dst_off, dst_len, hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) status = fail(ICAMD_ERR_HIP, "D2H copy", e);
-    }
-    const hipError_t e1 = hipStreamSynchronize(st.stream), e2 = hipStreamSynchronize(st.stream2);
-    if (status != ICAMD_OK) return status;
-    if (e1 != hipSuccess || e2 != hipSuccess) return fail(ICAMD_ERR_HIP, "stream synchronize", e1 != hipSuccess ? e1 : e2);
-  }
-  if (pinned) std::memcpy(out, st.h_out, out_size);
+  const hipError_t e1 = hipStreamSynchronize(st.stream), e2 = hipStreamSynchronize(st.stream2);
+  if (status != ICAMD_OK) return status;
+  if (e1 != hipSuccess || e2 != hipSuccess) return fail(ICAMD_ERR_HIP, "stream synchronize", e1 != hipSuccess ? e1 : e2);
   return ICAMD_OK;
 }
 
 int icamd_compress(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
                    uint32_t padding_bytes_per_row, const uint8_t *buffer, uint8_t *out, size_t out_size) try {
-  return compress_host_common(tls_staging(), false, false, compressor, etc_strategy, format, height, width, height, width,
+  return compress_host_common(tls_staging(), false, compressor, etc_strategy, format, height, width, height, width,
                               padding_bytes_per_row, buffer, out, out_size);
 } ICAMD_ABI_CATCH
 
 int icamd_compress_and_pad(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
                            uint32_t padded_height, uint32_t padded_width, uint32_t padding_bytes_per_row,
                            const uint8_t *buffer, uint8_t *out, size_t out_size) try {
-  return compress_host_common(tls_staging(), false, true, compressor, etc_strategy, format, height, width, padded_height,
+  return compress_host_common(tls_staging(), true, compressor, etc_strategy, format, height, width, padded_height,
                               padded_width, padding_bytes_per_row, buffer, out, out_size);
 } ICAMD_ABI_CATCH
 
@@ -822,25 +798,18 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     ICAMD_HIP(icamd::launch_bc45_decode(codec, n_images, P, stream), "launch bc4 / bc5 decode");
     return ICAMD_OK;
   }
-  if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4) {
+  const bool pvrtc = codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4;
+  if (pvrtc) {
     // EXTENSION (the reference's PvrtcCompressor::Decompress returns false, pvrtc.cc:669-672; 4 bpp: no such format there at
     // all): the sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650), RGBA8 out, no row padding, one launch per <= 2^30 blocks
     if (!is_pow2(width) || width != height || width < 8 || padding_bytes_per_row != 0) return ICAMD_FALSE;
-    const uint64_t pv_bpi = (uint64_t)(width / (codec == ICAMD_PVRTC2 ? 8 : 4)) * (height / 4);
-    if (pv_bpi >= (1ull << 31)) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
-    const uint64_t per_launch = std::max<uint64_t>(1, ((1ull << 31) - 1) / pv_bpi);
-    for (uint64_t first = 0; first < n_images; first += per_launch) {
-      const uint32_t count = (uint32_t)std::min<uint64_t>(per_launch, n_images - first);
-      rc = decode_launch(codec, 0, height, width, width * 4u, count, src_image_stride_bytes, dst_image_stride_bytes,
-                         blocks + first * src_image_stride_bytes, pixels + first * dst_image_stride_bytes, stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-    return ICAMD_OK;
+    swap_rb = 0;
   }
   const uint32_t block_bytes = icamd::codec_block_bytes(codec);
-  const uint32_t row_stride = width * (codec == ICAMD_DXT5 ? 4u : 3u) + padding_bytes_per_row;
-  const uint64_t block_cols = num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
+  const uint32_t row_stride = width * (codec == ICAMD_DXT5 || pvrtc ? 4u : 3u) + padding_bytes_per_row;
+  const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
   const uint64_t kMaxBlocks = (1ull << 31) - 1;
+  if (pvrtc && bpi > kMaxBlocks) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
   if (bpi <= kMaxBlocks) {  // whole images, as many per launch as the 32-bit block index allows
     const uint64_t per_launch = std::max<uint64_t>(1, kMaxBlocks / bpi);
     for (uint64_t first = 0; first < n_images; first += per_launch) {
@@ -874,22 +843,10 @@ int icamd_decompress(int compressor, int format, uint32_t height, uint32_t width
   if (blocks_size != icamd_encoded_size(codec, height, width)) return ICAMD_FALSE;
   const size_t need = (size_t)height * ((size_t)width * comps + padding_bytes_per_row);
   if (out_size != need) return ICAMD_FALSE;
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
-  Staging &st = tls_staging();
-  rc = st.ensure(blocks_size, need);
-  if (rc != ICAMD_OK) return rc;
-  hipStream_t s = st.stream;
-  ICAMD_HIP(hipMemcpyAsync(st.d_in, blocks, blocks_size, hipMemcpyHostToDevice, s), "H2D copy");
-  if (padding_bytes_per_row) ICAMD_HIP(hipMemsetAsync(st.d_out, 0, need, s), "memset");
-  rc = icamd_decode_device(codec, swap, height, width, padding_bytes_per_row, 1, 0, 0, st.d_in, st.d_out, s);
-  if (rc != ICAMD_OK) {
-    (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  ICAMD_HIP(hipMemcpyAsync(out, st.d_out, need, hipMemcpyDeviceToHost, s), "D2H copy");
-  ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
-  return ICAMD_OK;
+  return staged_blockop(tls_staging(), blocks, blocks_size, out, need, need, false, [&](void *din, void *dout, hipStream_t s) {
+    if (padding_bytes_per_row) ICAMD_HIP(hipMemsetAsync(dout, 0, need, s), "memset");
+    return icamd_decode_device(codec, swap, height, width, padding_bytes_per_row, 1, 0, 0, din, dout, s);
+  });
 } ICAMD_ABI_CATCH
 
 // EXTENSION (parity unpinned, see icamd_decode_device): host-buffer PVRTC 2bpp decode.  Kept apart from
@@ -897,9 +854,10 @@ int icamd_decompress(int compressor, int format, uint32_t height, uint32_t width
 int icamd_pvrtc2_decompress(uint32_t size, const uint8_t *blocks, size_t blocks_size, uint8_t *out, size_t out_size) try {
   if (!blocks || !out || !is_pow2(size) || size < 8) return ICAMD_FALSE;
   if (blocks_size != (size_t)size * size / 4 || out_size != (size_t)size * size * 4) return ICAMD_FALSE;
-  return staged_blockop(blocks, blocks_size, out, out_size, false, [&](void *din, void *dout, hipStream_t s) {
-    return icamd_decode_device(ICAMD_PVRTC2, 0, size, size, 0, 1, 0, 0, din, dout, s);
-  });
+  return staged_blockop(tls_staging(), blocks, blocks_size, out, out_size, out_size, false,
+                        [&](void *din, void *dout, hipStream_t s) {
+                          return icamd_decode_device(ICAMD_PVRTC2, 0, size, size, 0, 1, 0, 0, din, dout, s);
+                        });
 } ICAMD_ABI_CATCH
 
 // ---- compressed-domain operations
@@ -908,7 +866,7 @@ int icamd_pad_batch_device(int compressor, int etc_strategy, int format, uint32_
                            const void *d_blocks, size_t src_image_stride_bytes, uint32_t ph, uint32_t pw, void *d_out,
                            size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream) try {
   int codec;
-  if (!d_blocks || !d_out || !blockop_codec(compressor, format, &codec)) return ICAMD_FALSE;
+  if (!d_blocks || !d_out || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_out) | src_image_stride_bytes | dst_image_stride_bytes) % 4u)
     return fail(ICAMD_ERR_ARG, "block pointers and image strides must be 4-byte aligned");
   icamd::BlockOpParams P;
@@ -920,29 +878,8 @@ int icamd_pad_batch_device(int compressor, int etc_strategy, int format, uint32_
   if (((n_images > 1 || src_image_stride_bytes != 0) && src_image_stride_bytes < icamd_encoded_size(codec, ch, cw)) ||
       ((n_images > 1 || dst_image_stride_bytes != 0) && dst_image_stride_bytes < out_size_per_image))
     return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
-  if (n_images == 0) return ICAMD_OK;
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
-  const uint64_t per = (uint64_t)P.out_rows * P.out_cols;
-  if (per >= (1ull << 31)) return fail(ICAMD_ERR_ARG, "more than 2^31 blocks in one image");
-  P.etc_strategy = (uint32_t)etc_strategy;
-  P.src_height = ch; P.src_width = cw;
-  P.div_out_cols = icamd::make_fastdiv(P.out_cols);
-  P.out_per_image = (uint32_t)per;
-  P.div_out_per_image = icamd::make_fastdiv(P.out_per_image);
-  P.src_image_stride = src_image_stride_bytes;
-  P.dst_image_stride = dst_image_stride_bytes;
-  // as many images per launch as the 32-bit block index allows
-  const uint64_t group = std::max<uint64_t>(1, ((1ull << 31) - 1) / per);
-  for (uint64_t first = 0; first < n_images; first += group) {
-    const uint64_t count = std::min<uint64_t>(group, n_images - first);
-    P.src = static_cast<const uint8_t *>(d_blocks) + first * src_image_stride_bytes;
-    P.dst = static_cast<uint8_t *>(d_out) + first * dst_image_stride_bytes;
-    P.n_images = (uint32_t)count;
-    P.total_out = (uint32_t)(per * count);
-    ICAMD_HIP(icamd::launch_pad(codec, P, static_cast<hipStream_t>(hip_stream)), "launch pad");
-  }
-  return ICAMD_OK;
+  return blockop_batch(icamd::launch_pad, "launch pad", codec, P, etc_strategy, ch, cw, n_images, d_blocks, src_image_stride_bytes,
+                       d_out, dst_image_stride_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_pad_device(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, const void *d_blocks,
@@ -954,7 +891,7 @@ int icamd_downsample_batch_device(int compressor, int etc_strategy, int format, 
                                   const void *d_blocks, size_t src_image_stride_bytes, void *d_out,
                                   size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream) try {
   int codec;
-  if (!d_blocks || !d_out || uh == 0 || uw == 0 || !blockop_codec(compressor, format, &codec)) return ICAMD_FALSE;
+  if (!d_blocks || !d_out || uh == 0 || uw == 0 || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_out) | src_image_stride_bytes | dst_image_stride_bytes) % 4u)
     return fail(ICAMD_ERR_ARG, "block pointers and image strides must be 4-byte aligned");
   icamd::BlockOpParams P;
@@ -970,29 +907,8 @@ int icamd_downsample_batch_device(int compressor, int etc_strategy, int format, 
     return fail(ICAMD_ERR_ARG, "source image stride smaller than an image");
   if ((n_images > 1 || dst_image_stride_bytes != 0) && dst_image_stride_bytes < out_size_per_image)
     return fail(ICAMD_ERR_ARG, "destination image stride smaller than an image");
-  if (n_images == 0) return ICAMD_OK;  // (after the checks: a call the reference would refuse is refused for any count)
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
-  const uint64_t per = (uint64_t)P.out_rows * P.out_cols;
-  if (per >= (1ull << 31)) return fail(ICAMD_ERR_ARG, "more than 2^31 blocks in one image");
-  P.etc_strategy = (uint32_t)etc_strategy;
-  P.src_height = uh; P.src_width = uw;
-  P.div_out_cols = icamd::make_fastdiv(P.out_cols);
-  P.out_per_image = (uint32_t)per;
-  P.div_out_per_image = icamd::make_fastdiv(P.out_per_image);
-  P.src_image_stride = src_image_stride_bytes;
-  P.dst_image_stride = dst_image_stride_bytes;
-  // as many images per launch as the 32-bit block index allows
-  const uint64_t group = std::max<uint64_t>(1, ((1ull << 31) - 1) / per);
-  for (uint64_t first = 0; first < n_images; first += group) {
-    const uint64_t count = std::min<uint64_t>(group, n_images - first);
-    P.src = static_cast<const uint8_t *>(d_blocks) + first * src_image_stride_bytes;
-    P.dst = static_cast<uint8_t *>(d_out) + first * dst_image_stride_bytes;
-    P.n_images = (uint32_t)count;
-    P.total_out = (uint32_t)(per * count);
-    ICAMD_HIP(icamd::launch_downsample(codec, P, static_cast<hipStream_t>(hip_stream)), "launch downsample");
-  }
-  return ICAMD_OK;
+  return blockop_batch(icamd::launch_downsample, "launch downsample", codec, P, etc_strategy, uh, uw, n_images, d_blocks,
+                       src_image_stride_bytes, d_out, dst_image_stride_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_downsample_device(int compressor, int etc_strategy, int format, uint32_t uh, uint32_t uw,
@@ -1018,10 +934,10 @@ int icamd_transcode_dxt1_to_etc1_device(void *d_blocks, size_t n_bytes, void *hi
 int icamd_pad(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, const uint8_t *blocks,
               uint32_t ph, uint32_t pw, uint8_t *out, size_t out_size) try {
   int codec;
-  if (!blocks || !out || !blockop_codec(compressor, format, &codec)) return ICAMD_FALSE;
+  if (!blocks || !out || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   if (num_blocks4(ph) < num_blocks4(ch) || num_blocks4(pw) < num_blocks4(cw)) return ICAMD_FALSE;
   if (out_size != icamd_encoded_size(codec, ph, pw)) return ICAMD_FALSE;
-  return staged_blockop(blocks, icamd_encoded_size(codec, ch, cw), out, out_size, false,
+  return staged_blockop(tls_staging(), blocks, icamd_encoded_size(codec, ch, cw), out, out_size, out_size, false,
                         [&](void *din, void *dout, hipStream_t s) {
                           return icamd_pad_device(compressor, etc_strategy, format, ch, cw, din, ph, pw, dout, out_size, s);
                         });
@@ -1030,11 +946,11 @@ int icamd_pad(int compressor, int etc_strategy, int format, uint32_t ch, uint32_
 int icamd_downsample(int compressor, int etc_strategy, int format, uint32_t uh, uint32_t uw, const uint8_t *blocks,
                      uint8_t *out, size_t out_size) try {
   int codec;
-  if (!blocks || !out || uh == 0 || uw == 0 || !blockop_codec(compressor, format, &codec)) return ICAMD_FALSE;
+  if (!blocks || !out || uh == 0 || uw == 0 || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   const uint32_t r = num_blocks4(uh), c = num_blocks4(uw);
   if ((r > 1 && r % 2) || (c > 1 && c % 2) || (r == 1 && c == 1 && (uh == 3 || uw == 3))) return ICAMD_FALSE;
   if (out_size != icamd_encoded_size(codec, (uh + 1) / 2, (uw + 1) / 2)) return ICAMD_FALSE;
-  return staged_blockop(blocks, icamd_encoded_size(codec, uh, uw), out, out_size, false,
+  return staged_blockop(tls_staging(), blocks, icamd_encoded_size(codec, uh, uw), out, out_size, out_size, false,
                         [&](void *din, void *dout, hipStream_t s) {
                           return icamd_downsample_device(compressor, etc_strategy, format, uh, uw, din, dout, out_size, s);
                         });
@@ -1043,7 +959,8 @@ int icamd_downsample(int compressor, int etc_strategy, int format, uint32_t uh, 
 int icamd_transcode_dxt1_to_etc1(uint8_t *blocks, size_t n_bytes) try {
   if (!blocks) return ICAMD_FALSE;
   if (n_bytes < 8) return ICAMD_OK;
-  return staged_blockop(blocks, n_bytes, blocks, n_bytes - n_bytes % 8, true, [&](void *din, void *, hipStream_t s) {
+  const size_t whole = n_bytes - n_bytes % 8;
+  return staged_blockop(tls_staging(), blocks, n_bytes, blocks, whole, whole, true, [&](void *din, void *, hipStream_t s) {
     return icamd_transcode_dxt1_to_etc1_device(din, n_bytes, s);
   });
 } ICAMD_ABI_CATCH
@@ -1057,61 +974,32 @@ int icamd_compress_batch(int compressor, int etc_strategy, int format, uint32_t 
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
   int visible = 0;
-  ICAMD_HIP(hipGetDeviceCount(&visible), "hipGetDeviceCount");
-  for (int d = 0; d < n_devices; ++d)
-    if (devices[d] < 0 || devices[d] >= visible) return fail(ICAMD_ERR_ARG, "icamd_compress_batch: bad device ordinal");
-  std::vector<int> local(n_images, ICAMD_OK);
-  std::vector<WorkerError> errors((size_t)n_devices);
-  std::vector<std::thread> workers;
-  workers.reserve((size_t)n_devices);
-  int not_started_from = n_devices;  // list entries from here on have no worker (thread creation failed)
-  {
-    JoinAll join_on_every_path_out{workers};
-    for (int d = 0; d < n_devices && (uint32_t)d < n_images; ++d) {
-      try {
-        workers.emplace_back([&, d]() noexcept {
-          auto fail_all = [&](int code, const char *what) {
-            for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = code;
-            if (errors[(size_t)d].empty()) errors[(size_t)d].set(what);
-          };
-          uint64_t reached = (uint64_t)d;  // the image being worked on: what an exception leaves undone starts here
-          try {
-            // each worker owns its device context and a pooled Staging (stream, device buffers, pinned host mirrors)
-            if (hipSetDevice(devices[d]) != hipSuccess) return fail_all(ICAMD_ERR_HIP, "hipSetDevice failed");
-            std::unique_ptr<Staging> st = pool_take(devices[d]);
-            for (; reached < n_images; reached += (uint64_t)n_devices) {
-              const uint32_t i = (uint32_t)reached;
-              local[i] = compress_host_common(*st, kBatchPinnedStaging, false, compressor, etc_strategy, format, height, width, height, width,
-                                              padding_bytes_per_row, buffers[i], outs[i], out_size);
-              if (local[i] < 0 && errors[(size_t)d].empty()) errors[(size_t)d].set(g_last_error);
-            }
-            pool_give(std::move(st));
-          } catch (...) {
-            const int code = abi_exception();
-            for (uint64_t i = reached; i < n_images; i += (uint64_t)n_devices) local[i] = code;
-            if (errors[(size_t)d].empty()) errors[(size_t)d].set(g_last_error);
-          }
-        });
-      } catch (...) {  // std::system_error from the thread's creation (or bad_alloc): the workers started so far finish
-        (void)abi_exception();
-        not_started_from = d;
-        break;
+  rc = check_device_list("icamd_compress_batch", devices, n_devices, &visible);
+  if (rc != ICAMD_OK) return rc;
+  return run_workers("icamd_compress_batch", n_devices, n_images, statuses,
+                     [&](int d, std::vector<int> &local, WorkerError &error) {
+    auto fail_all = [&](int code, const char *what) {
+      for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = code;
+      if (error.empty()) error.set(what);
+    };
+    uint64_t reached = (uint64_t)d;  // the image being worked on: what an exception leaves undone starts here
+    try {
+      // each worker owns its device context and a pooled Staging (streams, device buffers)
+      if (hipSetDevice(devices[d]) != hipSuccess) return fail_all(ICAMD_ERR_HIP, "hipSetDevice failed");
+      std::unique_ptr<Staging> st = pool_take(devices[d]);
+      for (; reached < n_images; reached += (uint64_t)n_devices) {
+        const uint32_t i = (uint32_t)reached;
+        local[i] = compress_host_common(*st, false, compressor, etc_strategy, format, height, width, height, width,
+                                        padding_bytes_per_row, buffers[i], outs[i], out_size);
+        if (local[i] < 0 && error.empty()) error.set(g_last_error);
       }
+      pool_give(std::move(st));
+    } catch (...) {
+      const int code = abi_exception();
+      for (uint64_t i = reached; i < n_images; i += (uint64_t)n_devices) local[i] = code;
+      if (error.empty()) error.set(g_last_error);
     }
-  }  // all started workers joined
-  for (int d = not_started_from; d < n_devices; ++d) {
-    for (uint32_t i = (uint32_t)d; i < n_images; i += (uint32_t)n_devices) local[i] = ICAMD_ERR_ALLOC;
-    errors[(size_t)d].set("icamd_compress_batch: could not start a worker thread");
-  }
-  int first = ICAMD_OK;
-  for (uint32_t i = 0; i < n_images; ++i) {
-    if (statuses) statuses[i] = local[i];
-    if (first == ICAMD_OK && local[i] != ICAMD_OK) first = local[i];
-  }
-  if (first < 0)
-    for (const WorkerError &e : errors)
-      if (!e.empty()) { set_last_error(e.text); break; }
-  return first;
+  });
 } ICAMD_ABI_CATCH
 
 // ---- CreateSolidImage / CopySubimage
@@ -1151,7 +1039,7 @@ uint32_t solid_block(int compressor, int format, const uint8_t *color, uint32_t 
 bool subimage_geometry(int compressor, int format, uint32_t ch, uint32_t cw, uint32_t row, uint32_t col, uint32_t h,
                        uint32_t w, int *block_bytes) {
   int codec;
-  if (!blockop_codec(compressor, format, &codec)) return false;
+  if (!resolve_codec(compressor, format, &codec)) return false;
   *block_bytes = (int)icamd::codec_block_bytes(codec);
   if (row % 4 || col % 4 || h % 4 || w % 4) return false;
   // 64-bit sums: the reference's uint32 start + extent can wrap and then accept a window outside the image
@@ -1298,155 +1186,127 @@ int icamd_encode_batch_sharded_device(int codec, int etc_strategy, int src_compo
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
   int visible = 0;
-  ICAMD_HIP(hipGetDeviceCount(&visible), "hipGetDeviceCount");
-  for (int d = 0; d < n_devices; ++d)
-    if (devices[d] < 0 || devices[d] >= visible) return fail(ICAMD_ERR_ARG, "icamd_encode_batch_sharded_device: bad device ordinal");
+  rc = check_device_list("icamd_encode_batch_sharded_device", devices, n_devices, &visible);
+  if (rc != ICAMD_OK) return rc;
   if (gather && gather_device >= visible) return fail(ICAMD_ERR_ARG, "icamd_encode_batch_sharded_device: bad gather device");
   const size_t out_size = icamd_encoded_size(codec, height, width);
   if (gather && gathered_image_stride_bytes < out_size) return fail(ICAMD_ERR_ARG, "gathered image stride smaller than an image");
   int prev_device = 0;
   (void)hipGetDevice(&prev_device);
-  std::vector<int> local(n_images, ICAMD_OK);
-  std::vector<WorkerError> errors((size_t)n_devices);
-  std::vector<std::thread> workers;
-  workers.reserve((size_t)n_devices);
-  int not_started_from = n_devices;  // list entries from here on have no worker (thread creation failed)
-  {
-  JoinAll join_on_every_path_out{workers};
-  for (int d = 0; d < n_devices && (uint32_t)d < n_images; ++d) {
+  rc = run_workers("icamd_encode_batch_sharded_device", n_devices, n_images, statuses,
+                   [&](int d, std::vector<int> &local, WorkerError &error) {
+    const int dev = devices[d];
+    auto fail_all = [&](int code, const char *what) {
+      for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = code;
+      error.set(what);
+    };
     try {
-    workers.emplace_back([&, d]() noexcept {
-      const int dev = devices[d];
-      auto fail_all = [&](int code, const char *what) {
-        for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = code;
-        errors[(size_t)d].set(what);
-      };
-      try {
-      if (hipSetDevice(dev) != hipSuccess) return fail_all(ICAMD_ERR_HIP, "hipSetDevice failed");
-      if (gather && dev != gather_device) {
-        // direct xGMI copies into the gather buffer: without peer access hipMemcpyPeerAsync bounces through host memory.
-        // Best effort -- "already enabled" and "not supported" both leave a working (if slower) copy path.
-        // (ICAMD_DISABLE_PEER_ACCESS=1: test knob -- take the host-bounced copy path on a box that has peer access)
-        int can = 0;
-        const char *no_peer = getenv("ICAMD_DISABLE_PEER_ACCESS");
-        if (!(no_peer && no_peer[0] == '1') && hipDeviceCanAccessPeer(&can, dev, gather_device) == hipSuccess && can)
-          (void)hipDeviceEnablePeerAccess(gather_device, 0);
-        (void)hipGetLastError();
-      }
-      std::unique_ptr<Staging> st = pool_take(dev);
-      // this worker's images, in order
-      std::vector<uint32_t> mine;
-      for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) mine.push_back((uint32_t)i);
-      auto slot_of = [&](uint32_t i) { return static_cast<uint8_t *>(d_gathered) + (size_t)i * gathered_image_stride_bytes; };
-      // where image i is encoded to: its own buffer, its gather slot (images of the gather device), or scratch (nullptr here)
-      auto target_of = [&](uint32_t i) -> uint8_t * {
-        if (d_dsts && d_dsts[i]) return static_cast<uint8_t *>(d_dsts[i]);
-        return (gather && dev == gather_device) ? slot_of(i) : nullptr;
-      };
-      // Consecutive images of a worker whose sources AND targets are evenly spaced (a batch laid out as one array, the
-      // usual case) go out as ONE launch of up to kRun images: a 1024^2 texture alone fills a quarter of the chip's wave
-      // slots, so one launch per texture leaves an MI355X mostly idle (bench.py single_image: 97 vs 252 Gpix/s for ETC1).
-      const size_t kRun = 64;
-      auto run_length = [&](size_t j, size_t *src_stride, size_t *dst_stride) -> size_t {
-        const uint32_t i0 = mine[j];
-        if (!d_srcs[i0] || j + 1 >= mine.size() || !d_srcs[mine[j + 1]]) return 1;
-        const uint8_t *s0 = static_cast<const uint8_t *>(d_srcs[i0]), *s1 = static_cast<const uint8_t *>(d_srcs[mine[j + 1]]);
-        uint8_t *t0 = target_of(i0), *t1 = target_of(mine[j + 1]);
-        if (s1 <= s0 || (t0 == nullptr) != (t1 == nullptr) || (t0 && t1 <= t0)) return 1;
-        const size_t ss = (size_t)(s1 - s0), ds = t0 ? (size_t)(t1 - t0) : out_size;
-        if (ds < out_size || ss % 16u || ds % 16u) return 1;  // (PVRTC wants 16-byte strides; harmless for the others)
-        size_t len = 2;
-        while (len < kRun && j + len < mine.size()) {
-          const uint32_t in = mine[j + len];
-          const uint8_t *sn = static_cast<const uint8_t *>(d_srcs[in]);
-          uint8_t *tn = target_of(in);
-          if (!sn || sn != s0 + len * ss || (tn == nullptr) != (t0 == nullptr) || (t0 && tn != t0 + len * ds)) break;
-          ++len;
-        }
-        *src_stride = ss;
-        *dst_stride = ds;
-        return len;
-      };
-      // scratch for the images that have no buffer on this device (gather only): two halves, so that the peer copies of
-      // one run overlap the encode of the next (two streams, alternating)
-      size_t scratch_images = 0;
-      for (size_t j = 0; j < mine.size(); ++j)
-        if (gather && target_of(mine[j]) == nullptr) scratch_images = std::min(kRun, std::max<size_t>(scratch_images + 1, 1));
-      const size_t scratch_bytes = scratch_images ? scratch_images * out_size : 1;
-      if (st->ensure(scratch_bytes, scratch_bytes) != ICAMD_OK) {
-        pool_give(std::move(st));
-        return fail_all(ICAMD_ERR_ALLOC, "staging allocation failed");
-      }
-      size_t run_no = 0;
-      for (size_t j = 0; j < mine.size(); ++run_no) {
-        size_t src_stride = 0, dst_stride = 0;
-        size_t len = run_length(j, &src_stride, &dst_stride);
-        const uint32_t i0 = mine[j];
-        hipStream_t s = (run_no & 1u) ? st->stream2 : st->stream;
-        uint8_t *scratch = static_cast<uint8_t *>((run_no & 1u) ? st->d_in : st->d_out);
-        uint8_t *own = target_of(i0);
-        if (!own && gather) len = std::min(len, scratch_images);
-        auto set_all = [&](int code) { for (size_t k = 0; k < len; ++k) local[mine[j + k]] = code; };
-        if (!d_srcs[i0]) { local[i0] = ICAMD_FALSE; j += 1; continue; }
-        if (!own && !gather) {  // nowhere to put this image's blocks
-          local[i0] = ICAMD_ERR_ARG;
-          if (errors[(size_t)d].empty()) errors[(size_t)d].set("icamd_encode_batch_sharded_device: image without an output buffer");
-          j += 1;
-          continue;
-        }
-        uint8_t *target = own ? own : scratch;
-        if (codec == ICAMD_PVRTC2) icamd::pvrtc2_select_workspace((int)(run_no & 1u));  // one scratch buffer per stream
-        const int rc_run = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, height, width,
-                                               row_stride_bytes, (uint32_t)len, len > 1 ? src_stride : 0,
-                                               len > 1 ? (own ? dst_stride : out_size) : 0, d_srcs[i0], target, s);
-        set_all(rc_run);
-        if (rc_run == ICAMD_OK && gather) {
-          for (size_t k = 0; k < len; ++k) {
-            const uint32_t i = mine[j + k];
-            uint8_t *from = own ? own + k * dst_stride : scratch + k * out_size;
-            if (from == slot_of(i)) continue;  // encoded straight into its slot
-            // the encoded image travels device -> device (xGMI between GPUs); no host staging
-            const hipError_t e = dev == gather_device ? hipMemcpyAsync(slot_of(i), from, out_size, hipMemcpyDeviceToDevice, s)
-                                                      : hipMemcpyPeerAsync(slot_of(i), gather_device, from, dev, out_size, s);
-            if (e != hipSuccess) local[i] = fail(ICAMD_ERR_HIP, "gather copy", e);
-          }
-        }
-        for (size_t k = 0; k < len; ++k)
-          if (local[mine[j + k]] < 0 && errors[(size_t)d].empty()) errors[(size_t)d].set(g_last_error);
-        j += len;
-      }
-      icamd::pvrtc2_select_workspace(0);
-      const hipError_t e1 = hipStreamSynchronize(st->stream), e2 = hipStreamSynchronize(st->stream2);
-      if (e1 != hipSuccess || e2 != hipSuccess) fail_all(ICAMD_ERR_HIP, "stream synchronize failed");
-      pool_give(std::move(st));
-      } catch (...) {
-        // what was enqueued may still be running on the worker's streams: this device's images all count as failed
-        const int code = abi_exception();
-        fail_all(code, g_last_error);
-        (void)hipDeviceSynchronize();
-      }
-    });
-    } catch (...) {  // std::system_error from the thread's creation (or bad_alloc): the workers started so far finish
-      (void)abi_exception();
-      not_started_from = d;
-      break;
+    if (hipSetDevice(dev) != hipSuccess) return fail_all(ICAMD_ERR_HIP, "hipSetDevice failed");
+    if (gather && dev != gather_device) {
+      // direct xGMI copies into the gather buffer: without peer access hipMemcpyPeerAsync bounces through host memory.
+      // Best effort -- "already enabled" and "not supported" both leave a working (if slower) copy path.
+      // (ICAMD_DISABLE_PEER_ACCESS=1: test knob -- take the host-bounced copy path on a box that has peer access)
+      int can = 0;
+      const char *no_peer = getenv("ICAMD_DISABLE_PEER_ACCESS");
+      if (!(no_peer && no_peer[0] == '1') && hipDeviceCanAccessPeer(&can, dev, gather_device) == hipSuccess && can)
+        (void)hipDeviceEnablePeerAccess(gather_device, 0);
+      (void)hipGetLastError();
     }
-  }
-  }  // all started workers joined
-  for (int d = not_started_from; d < n_devices; ++d) {
-    for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) local[i] = ICAMD_ERR_ALLOC;
-    errors[(size_t)d].set("icamd_encode_batch_sharded_device: could not start a worker thread");
-  }
+    std::unique_ptr<Staging> st = pool_take(dev);
+    // this worker's images, in order
+    std::vector<uint32_t> mine;
+    for (uint64_t i = (uint64_t)d; i < n_images; i += (uint64_t)n_devices) mine.push_back((uint32_t)i);
+    auto slot_of = [&](uint32_t i) { return static_cast<uint8_t *>(d_gathered) + (size_t)i * gathered_image_stride_bytes; };
+    // where image i is encoded to: its own buffer, its gather slot (images of the gather device), or scratch (nullptr here)
+    auto target_of = [&](uint32_t i) -> uint8_t * {
+      if (d_dsts && d_dsts[i]) return static_cast<uint8_t *>(d_dsts[i]);
+      return (gather && dev == gather_device) ? slot_of(i) : nullptr;
+    };
+    // Consecutive images of a worker whose sources AND targets are evenly spaced (a batch laid out as one array, the
+    // usual case) go out as ONE launch of up to kRun images: a 1024^2 texture alone fills a quarter of the chip's wave
+    // slots, so one launch per texture leaves an MI355X mostly idle (bench.py single_image: 97 vs 252 Gpix/s for ETC1).
+    const size_t kRun = 64;
+    auto run_length = [&](size_t j, size_t *src_stride, size_t *dst_stride) -> size_t {
+      const uint32_t i0 = mine[j];
+      if (!d_srcs[i0] || j + 1 >= mine.size() || !d_srcs[mine[j + 1]]) return 1;
+      const uint8_t *s0 = static_cast<const uint8_t *>(d_srcs[i0]), *s1 = static_cast<const uint8_t *>(d_srcs[mine[j + 1]]);
+      uint8_t *t0 = target_of(i0), *t1 = target_of(mine[j + 1]);
+      if (s1 <= s0 || (t0 == nullptr) != (t1 == nullptr) || (t0 && t1 <= t0)) return 1;
+      const size_t ss = (size_t)(s1 - s0), ds = t0 ? (size_t)(t1 - t0) : out_size;
+      if (ds < out_size || ss % 16u || ds % 16u) return 1;  // (PVRTC wants 16-byte strides; harmless for the others)
+      size_t len = 2;
+      while (len < kRun && j + len < mine.size()) {
+        const uint32_t in = mine[j + len];
+        const uint8_t *sn = static_cast<const uint8_t *>(d_srcs[in]);
+        uint8_t *tn = target_of(in);
+        if (!sn || sn != s0 + len * ss || (tn == nullptr) != (t0 == nullptr) || (t0 && tn != t0 + len * ds)) break;
+        ++len;
+      }
+      *src_stride = ss;
+      *dst_stride = ds;
+      return len;
+    };
+    // scratch for the images that have no buffer on this device (gather only): two halves, so that the peer copies of
+    // one run overlap the encode of the next (two streams, alternating)
+    size_t scratch_images = 0;
+    for (size_t j = 0; j < mine.size(); ++j)
+      if (gather && target_of(mine[j]) == nullptr) scratch_images = std::min(kRun, std::max<size_t>(scratch_images + 1, 1));
+    const size_t scratch_bytes = scratch_images ? scratch_images * out_size : 1;
+    if (st->ensure(scratch_bytes, scratch_bytes) != ICAMD_OK) {
+      pool_give(std::move(st));
+      return fail_all(ICAMD_ERR_ALLOC, "staging allocation failed");
+    }
+    size_t run_no = 0;
+    for (size_t j = 0; j < mine.size(); ++run_no) {
+      size_t src_stride = 0, dst_stride = 0;
+      size_t len = run_length(j, &src_stride, &dst_stride);
+      const uint32_t i0 = mine[j];
+      hipStream_t s = (run_no & 1u) ? st->stream2 : st->stream;
+      uint8_t *scratch = static_cast<uint8_t *>((run_no & 1u) ? st->d_in : st->d_out);
+      uint8_t *own = target_of(i0);
+      if (!own && gather) len = std::min(len, scratch_images);
+      auto set_all = [&](int code) { for (size_t k = 0; k < len; ++k) local[mine[j + k]] = code; };
+      if (!d_srcs[i0]) { local[i0] = ICAMD_FALSE; j += 1; continue; }
+      if (!own && !gather) {  // nowhere to put this image's blocks
+        local[i0] = ICAMD_ERR_ARG;
+        if (error.empty()) error.set("icamd_encode_batch_sharded_device: image without an output buffer");
+        j += 1;
+        continue;
+      }
+      uint8_t *target = own ? own : scratch;
+      if (codec == ICAMD_PVRTC2) icamd::pvrtc2_select_workspace((int)(run_no & 1u));  // one scratch buffer per stream
+      const int rc_run = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, height, width,
+                                             row_stride_bytes, (uint32_t)len, len > 1 ? src_stride : 0,
+                                             len > 1 ? (own ? dst_stride : out_size) : 0, d_srcs[i0], target, s);
+      set_all(rc_run);
+      if (rc_run == ICAMD_OK && gather) {
+        for (size_t k = 0; k < len; ++k) {
+          const uint32_t i = mine[j + k];
+          uint8_t *from = own ? own + k * dst_stride : scratch + k * out_size;
+          if (from == slot_of(i)) continue;  // encoded straight into its slot
+          // the encoded image travels device -> device (xGMI between GPUs); no host staging
+          const hipError_t e = dev == gather_device ? hipMemcpyAsync(slot_of(i), from, out_size, hipMemcpyDeviceToDevice, s)
+                                                    : hipMemcpyPeerAsync(slot_of(i), gather_device, from, dev, out_size, s);
+          if (e != hipSuccess) local[i] = fail(ICAMD_ERR_HIP, "gather copy", e);
+        }
+      }
+      for (size_t k = 0; k < len; ++k)
+        if (local[mine[j + k]] < 0 && error.empty()) error.set(g_last_error);
+      j += len;
+    }
+    icamd::pvrtc2_select_workspace(0);
+    const hipError_t e1 = hipStreamSynchronize(st->stream), e2 = hipStreamSynchronize(st->stream2);
+    if (e1 != hipSuccess || e2 != hipSuccess) fail_all(ICAMD_ERR_HIP, "stream synchronize failed");
+    pool_give(std::move(st));
+    } catch (...) {
+      // what was enqueued may still be running on the worker's streams: this device's images all count as failed
+      const int code = abi_exception();
+      fail_all(code, g_last_error);
+      (void)hipDeviceSynchronize();
+    }
+  });
   (void)hipSetDevice(prev_device);
-  int first = ICAMD_OK;
-  for (uint32_t i = 0; i < n_images; ++i) {
-    if (statuses) statuses[i] = local[i];
-    if (first == ICAMD_OK && local[i] != ICAMD_OK) first = local[i];
-  }
-  if (first < 0)
-    for (const WorkerError &e : errors)
-      if (!e.empty()) { set_last_error(e.text); break; }
-  return first;
+  return rc;
 } ICAMD_ABI_CATCH
 
 // ---- container framing (extension; csrc/containers.h) ----
@@ -1521,20 +1381,17 @@ int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, in
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
   int rc = mip_check_components(codec, src_components, swap_rb);
   if (rc != ICAMD_OK) return rc;
-  if (levels == 0 || levels > mip_max_levels(height, width))
-    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
-  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
-  size_t offsets[33];
-  const size_t chain = icamd_mip_chain_size(codec, height, width, levels, offsets);
-  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)src_components;
-  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < chain))
-    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
+  rc = mip_check_geometry(codec, src_components, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes,
+                          dst_image_stride_bytes);
+  if (rc != ICAMD_OK) return rc;
   const size_t ws_need = mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
   if (ws_need && (!d_workspace || workspace_bytes < ws_need))
     return fail(ICAMD_ERR_ARG, "workspace smaller than icamd_mip_workspace_size");
   if (n_images == 0) return ICAMD_OK;
   rc = require_device();
   if (rc != ICAMD_OK) return rc;
+  size_t offsets[33];
+  (void)icamd_mip_chain_size(codec, height, width, levels, offsets);
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   if (codec == ICAMD_ETC1) {
     // level 0 from the source and every other level from the pixel pyramid in the workspace, each through the ETC1 kernels
@@ -1591,20 +1448,16 @@ int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width
                              const void *d_src, void *d_dst, void *hip_stream) try {
   if (src_components < 1 || src_components > 4) return fail(ICAMD_ERR_ARG, "src_components must be 1 .. 4");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
-  if (levels == 0 || levels > mip_max_levels(height, width))
-    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
-  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  int rc = mip_check_geometry(icamd::kMipPyramidMode, src_components, height, width, row_stride_bytes, levels, n_images,
+                              src_image_stride_bytes, dst_image_stride_bytes);
+  if (rc != ICAMD_OK) return rc;
+  if (n_images == 0) return ICAMD_OK;
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (levels == 1) return ICAMD_OK;
   size_t poff[34];  // poff[l]: bytes of levels 1 .. l-1 (level l's offset in one image's output)
   poff[1] = 0;
   for (uint32_t l = 1; l < levels; ++l) poff[l + 1] = poff[l] + mip_level_pixels(height, width, l, src_components);
-  const size_t per = mip_pyramid_bytes(height, width, levels, src_components);
-  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)src_components;
-  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < per))
-    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
-  if (n_images == 0) return ICAMD_OK;
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
-  if (levels == 1) return ICAMD_OK;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   uint8_t *dst = static_cast<uint8_t *>(d_dst);
   for (const MipPass &p : mip_plan(height, width, levels, true)) {
@@ -1637,26 +1490,14 @@ int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t h
   if (out_size != icamd_mip_chain_size(codec, height, width, levels, nullptr)) return ICAMD_FALSE;
   const size_t stride = (size_t)width * comps + padding_bytes_per_row;
   if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
-  int rc = require_device();
-  if (rc != ICAMD_OK) return rc;
   const size_t in_bytes = (size_t)(height - 1) * stride + (size_t)width * comps;
   const size_t ws_off = (out_size + 255u) & ~(size_t)255u;
   const size_t ws = mip_workspace_bytes(codec, height, width, levels, comps, 1);
-  Staging &st = tls_staging();
-  rc = st.ensure(in_bytes, ws_off + ws);
-  if (rc != ICAMD_OK) return rc;
-  hipStream_t s = st.stream;
-  uint8_t *d_out = static_cast<uint8_t *>(st.d_out);
-  ICAMD_HIP(hipMemcpyAsync(st.d_in, buffer, in_bytes, hipMemcpyHostToDevice, s), "H2D copy");
-  rc = icamd_encode_mips_device(codec, etc_strategy, comps, swap, height, width, (uint32_t)stride, levels, 1, 0, 0, st.d_in,
-                                d_out, ws ? d_out + ws_off : nullptr, ws, s);
-  if (rc != ICAMD_OK) {
-    (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  ICAMD_HIP(hipMemcpyAsync(out, d_out, out_size, hipMemcpyDeviceToHost, s), "D2H copy");
-  ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
-  return ICAMD_OK;
+  return staged_blockop(tls_staging(), buffer, in_bytes, out, out_size, ws_off + ws, false, [&](void *din, void *dout, hipStream_t s) {
+    uint8_t *d_out = static_cast<uint8_t *>(dout);
+    return icamd_encode_mips_device(codec, etc_strategy, comps, swap, height, width, (uint32_t)stride, levels, 1, 0, 0, din,
+                                    d_out, ws ? d_out + ws_off : nullptr, ws, s);
+  });
 } ICAMD_ABI_CATCH
 
 #pragma GCC visibility pop
