@@ -6,42 +6,7 @@
 #include "ic_launch.h"
 #include "ic_amd.h"
 
-// Calm waves take the instantiation WITHOUT the mixed tier: with it (and pruning) smooth content measured 1.466 -> 1.505 ms
-// and flat 1.35 -> 1.42 ms (r03, profiles/r03_ab_etc1_mixed_tier.log) -- there the tier's register pressure costs more than
-// its arithmetic saves.
-#ifndef ICAMD_ETC1_CALM_TIER
-#define ICAMD_ETC1_CALM_TIER false
-#endif
-
 namespace icamd {
-
-// STRATEGY is a compile-time constant: one kernel per EtcCompressor::CompressionStrategy, so that the straight-line
-// code of kSmallerError (two partitions x two sub-blocks x eight codewords, unrolled) does not carry the single-partition
-// and heuristic paths along -- the kernel is bound by instruction issue AND sensitive to its code footprint
-// (profiles/r03_ab_etc1_*.log).  The default: label of etc_compressor.cc:575-584 makes every other value kSmallerError.
-// The part of etc1_encode_one after the block is in registers: the per-wave choice of instantiation.  constant / busy are
-// per-lane properties of the block (one colour; sums r + g + b spread by ICAMD_ETC1_BUSY_SPREAD or more).
-template <int STRATEGY>
-__device__ __forceinline__ Out8 etc1_encode_classified(const uint32_t px[16], bool constant, bool busy) {
-  Out8 c;
-  // One-colour blocks are encoded by a form of their own (one pixel against the 32 candidates).  A wave of nothing else
-  // skips the searches altogether; inside a mixed wave those lanes neither vote in the searches' wave-uniform
-  // decisions nor count for the content probe, and their results are replaced afterwards.
-  if (wave_all(!constant)) {  // (the common case: exactly the code of a build without the one-colour forms)
-    if (wave_count(busy) >= 48u) c = encode_etc1_block<true, false>(px, (uint32_t)STRATEGY);  // busy wave: mixed tier, no pruning
-    else c = encode_etc1_block<ICAMD_ETC1_CALM_TIER, true>(px, (uint32_t)STRATEGY);           // calm wave: pruning (+ tier?)
-  } else if (wave_all(constant)) {
-    c = encode_etc1_constant_block(px[0], (uint32_t)STRATEGY);
-  } else {
-    if (4u * wave_count(!constant && busy) >= 3u * wave_count(!constant))
-      c = encode_etc1_block<true, false, true>(px, (uint32_t)STRATEGY, constant);
-    else c = encode_etc1_block<ICAMD_ETC1_CALM_TIER, true, true>(px, (uint32_t)STRATEGY, constant);
-    const Out8 cc = encode_etc1_constant_block(px[0], (uint32_t)STRATEGY);
-    c.lo = constant ? cc.lo : c.lo;
-    c.hi = constant ? cc.hi : c.hi;
-  }
-  return c;
-}
 
 // STRATEGY is a compile-time constant: one kernel per EtcCompressor::CompressionStrategy, so that the straight-line
 // code of kSmallerError (two partitions x two sub-blocks x eight codewords, unrolled) does not carry the single-partition

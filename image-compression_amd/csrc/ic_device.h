@@ -153,7 +153,14 @@ ICAMD_DEV int32_t imax(int32_t a, int32_t b) { return max(a, b); }
 #endif
 
 // True iff the predicate holds in every active lane of the wave (the emulation has one "lane").
-#if defined(ICAMD_HOST_EMULATION)
+#if defined(ICAMD_HOST_EMULATION) && defined(ICAMD_EMUL_WAVE)
+// tests/host_emul/wave_emul.cc: the lanes of an emulated wave run as host threads and vote together; a vote's site is
+// its source line (the optimiser may duplicate the code around it)
+bool wave_all_at(bool p, const char *file, int line);
+uint32_t wave_count_at(bool p, const char *file, int line);
+#define wave_all(p) wave_all_at((p), __FILE__, __LINE__)
+#define wave_count(p) wave_count_at((p), __FILE__, __LINE__)
+#elif defined(ICAMD_HOST_EMULATION)
 ICAMD_DEV bool wave_all(bool p) { return p; }
 ICAMD_DEV uint32_t wave_count(bool p) { return p ? 64u : 0u; }
 #else

@@ -1,0 +1,257 @@
+// TEST INFRASTRUCTURE ONLY.  A lockstep 64-lane wave for the host emulation of the per-block device math
+// (image-compression_amd/csrc/*_block.h).  emul.cc runs every block alone, so there wave_all(p) = p and a block that
+// qualifies for a wave-uniform shortcut always takes it; the code a lane runs when a neighbour vetoes never runs.  Here
+// the blocks of one wave run as host threads, one per lane, and wave_all / wave_count are a barrier plus a reduction over
+// the lanes of the wave -- the semantics of __all / __ballot on gfx950.
+//
+// Build: g++ -std=c++20 -pthread -DICAMD_HOST_EMULATION -DICAMD_EMUL_WAVE (ic_device.h then only declares the two votes).
+//
+// A vote's site is its source line (ic_device.h passes __FILE__ / __LINE__).  The emulator checks lockstep instead of
+// assuming it:
+//  * every lane waiting at a vote must wait at the SAME site (two sites at once = a vote in divergent flow);
+//  * STRICT waves: no lane may finish while others wait at a vote (it skipped that vote);
+//  * a wait that passes the deadline ends the wave.
+// Any of these makes the entry point return 0 and wemul_error() name the site.  The other lanes are then released -- every later vote returns its own predicate -- so the threads end.
+// RELAXED waves model a lane that returned early (GPU: it leaves the EXEC mask): finished lanes no longer count, as in the
+// DXT colour encoder, whose index-search vote sits in the branch of blocks with two distinct endpoints.
+#if !defined(ICAMD_HOST_EMULATION) || !defined(ICAMD_EMUL_WAVE)
+#error "build with -DICAMD_HOST_EMULATION -DICAMD_EMUL_WAVE"
+#endif
+#include <chrono>
+#include <condition_variable>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "blockops_block.h"
+
+using namespace icamd;
+
+namespace {
+
+constexpr int kLanes = 64;
+constexpr auto kDeadline = std::chrono::seconds(120);
+
+struct Wave {
+  std::mutex m;
+  std::condition_variable cv;
+  int lanes = 0;         // lanes started
+  bool strict = true;
+  int finished = 0;      // lanes that returned from the block function
+  int waiting = 0;       // lanes inside the current vote
+  const char *file = nullptr;  // the current vote's site
+  int line = 0;
+  uint32_t count = 0;    // lanes of the current vote whose predicate holds
+  uint32_t result = 0, result_active = 0;
+  uint64_t generation = 0;
+  uint64_t votes = 0;    // resolved votes (diagnostics)
+  bool broken = false;
+  std::string error;
+};
+
+thread_local Wave *tl_wave = nullptr;
+std::mutex g_error_mutex;
+std::string g_error;
+
+std::string site_name(const char *file, int line) {
+  const char *slash = file ? strrchr(file, '/') : nullptr;
+  return std::string(slash ? slash + 1 : file ? file : "?") + ":" + std::to_string(line);
+}
+
+// caller holds w.m
+void fail(Wave &w, const std::string &why) {
+  if (!w.broken) w.error = why;
+  w.broken = true;
+  ++w.generation;
+  w.cv.notify_all();
+}
+
+// caller holds w.m: the vote completes once every lane is either in it or (relaxed waves) finished
+void try_resolve(Wave &w) {
+  if (w.waiting == 0 || w.waiting + w.finished < w.lanes) return;
+  if (w.finished > 0 && w.strict) {
+    fail(w, std::to_string(w.finished) + " lane(s) finished without the vote at " + site_name(w.file, w.line));
+    return;
+  }
+  w.result = w.count;
+  w.result_active = (uint32_t)w.waiting;
+  w.waiting = 0;
+  w.count = 0;
+  w.file = nullptr;
+  ++w.votes;
+  ++w.generation;
+  w.cv.notify_all();
+}
+
+// returns {lanes whose predicate holds, lanes taking part}
+std::pair<uint32_t, uint32_t> vote(bool p, const char *file, int line) {
+  Wave *wp = tl_wave;
+  if (!wp) return { p ? 1u : 0u, 1u };  // called outside a wave: one lane
+  Wave &w = *wp;
+  std::unique_lock<std::mutex> lk(w.m);
+  if (w.broken) return { p ? 1u : 0u, 1u };
+  if (w.waiting == 0) {
+    w.file = file;
+    w.line = line;
+  } else if (w.line != line || strcmp(w.file, file) != 0) {
+    fail(w, "lanes wait at two votes at once (divergent flow): " + site_name(w.file, w.line) + " and " + site_name(file, line));
+    return { p ? 1u : 0u, 1u };
+  }
+  ++w.waiting;
+  w.count += p ? 1u : 0u;
+  const uint64_t gen = w.generation;
+  try_resolve(w);
+  if (!w.cv.wait_until(lk, std::chrono::steady_clock::now() + kDeadline, [&] { return w.generation != gen; })) {
+    fail(w, "deadline passed at " + site_name(file, line) + ": a lane never reached this vote");
+  }
+  if (w.broken) return { p ? 1u : 0u, 1u };
+  return { w.result, w.result_active };
+}
+
+// Runs fn(lane) for lanes 0..n-1 as one wave.  Returns 1, or 0 after a lockstep violation (message in g_error).
+int run_wave(int n, bool strict, const std::function<void(int)> &fn) {
+  if (n < 1 || n > kLanes) {
+    std::lock_guard<std::mutex> g(g_error_mutex);
+    g_error = "a wave holds 1 to 64 lanes";
+    return 0;
+  }
+  Wave w;
+  w.lanes = n;
+  w.strict = strict;
+  std::vector<std::thread> threads;
+  threads.reserve(n);
+  for (int lane = 0; lane < n; ++lane)
+    threads.emplace_back([&w, &fn, lane] {
+      tl_wave = &w;
+      fn(lane);
+      std::lock_guard<std::mutex> lk(w.m);
+      ++w.finished;
+      try_resolve(w);
+      tl_wave = nullptr;
+    });
+  for (auto &t : threads) t.join();
+  std::lock_guard<std::mutex> g(g_error_mutex);
+  g_error = w.error;
+  return w.broken ? 0 : 1;
+}
+
+inline void put8(uint32_t *out, const Out8 &o) { out[0] = o.lo; out[1] = o.hi; }
+
+// ETC1 exactly as etc1_encode_one: kHeuristic straight, the searching strategies through the classifier
+template <int S>
+void etc1_one(const uint32_t *p, uint32_t *o) {
+  if (S == 3) {
+    put8(o, encode_etc1_block<false>(p, 3u));
+  } else {
+    const uint32_t spread = etc1_block_spread(p);
+    put8(o, etc1_encode_classified<S>(p, etc1_constant_block(p, spread), spread >= ICAMD_ETC1_BUSY_SPREAD));
+  }
+}
+
+}  // namespace
+
+namespace icamd {
+// the votes ic_device.h declares under ICAMD_EMUL_WAVE
+bool wave_all_at(bool p, const char *file, int line) {
+  const auto r = vote(p, file, line);
+  return r.first == r.second;
+}
+uint32_t wave_count_at(bool p, const char *file, int line) { return vote(p, file, line).first; }
+}  // namespace icamd
+
+extern "C" {
+
+const char *wemul_error() { return g_error.c_str(); }
+
+// ---- encoders.  px: n x 16 pixel dwords (the kernels' load format), out: n x 2 (DXT1 / ETC1) or n x 4 (DXT5) dwords.
+
+// DXT1 (codec 0) / DXT5 (codec 1), as dxt_encode_one / dxt_encode_two per block
+int wemul_dxt(int codec, int swap, int n, const uint32_t *px, uint32_t *out) {
+  return run_wave(n, false, [=](int i) {
+    const uint32_t *p = px + 16 * i;
+    BlockStash stash;
+    if (codec == 1) {
+      put8(out + 4 * i, encode_dxt5_alpha_block(p, false));
+      put8(out + 4 * i + 2, encode_dxt_color_block(p, swap != 0, true, stash));
+    } else {
+      put8(out + 2 * i, encode_dxt_color_block(p, swap != 0, false, stash));
+    }
+  });
+}
+
+int wemul_etc1(int strategy, int n, const uint32_t *px, uint32_t *out) {
+  static void (*const forms[4])(const uint32_t *, uint32_t *) = { etc1_one<0>, etc1_one<1>, etc1_one<2>, etc1_one<3> };
+  if (strategy < 0 || strategy > 3) return 0;
+  return run_wave(n, true, [=](int i) { forms[strategy](px + 16 * i, out + 2 * i); });
+}
+
+// The wave's classification as the classifier sees it: flags[i] bit 0 = busy, bit 1 = one colour; returns the lane count
+int wemul_etc1_classify(int n, const uint32_t *px, uint32_t *flags) {
+  return run_wave(n, true, [=](int i) {
+    const uint32_t spread = etc1_block_spread(px + 16 * i);
+    flags[i] = (spread >= ICAMD_ETC1_BUSY_SPREAD ? 1u : 0u) | (etc1_constant_block(px + 16 * i, spread) ? 2u : 0u);
+  });
+}
+
+// One explicit encode_etc1_block<TIER, PRUNE, SKIP> instantiation; skip[i] = the lane's result is not used (SKIP forms)
+int wemul_etc1_inst(int tier, int prune, int skip_form, int strategy, int n, const uint32_t *px, const uint8_t *skip,
+                    uint32_t *out) {
+  typedef Out8 (*Enc)(const uint32_t *, uint32_t, bool);
+  static const Enc forms[8] = {
+    encode_etc1_block<false, false, false>, encode_etc1_block<false, false, true>,
+    encode_etc1_block<false, true, false>,  encode_etc1_block<false, true, true>,
+    encode_etc1_block<true, false, false>,  encode_etc1_block<true, false, true>,
+    encode_etc1_block<true, true, false>,   encode_etc1_block<true, true, true> };
+  const Enc f = forms[(tier ? 4 : 0) | (prune ? 2 : 0) | (skip_form ? 1 : 0)];
+  return run_wave(n, true, [=](int i) { put8(out + 2 * i, f(px + 16 * i, (uint32_t)strategy, skip[i] != 0)); });
+}
+
+// ---- block operations.  words: n blocks of 2 (DXT1 / ETC1) or 4 (DXT5) dwords.
+
+// decode_block_rows (the decode kernels; palette / alpha planes): out = n x 16 pixel dwords, RGB888 (byte 3 = 0) or RGBA8
+int wemul_decode(int codec, int n, const uint32_t *words, uint32_t *out) {
+  return run_wave(n, true, [=](int i) {
+    uint32_t rows[4][4];
+    if (codec == 1) decode_block_rows<1>(words + 4 * i, false, rows);
+    else if (codec == 0) decode_block_rows<0>(words + 2 * i, false, rows);
+    else decode_block_rows<2>(words + 2 * i, false, rows);
+    uint8_t *o = reinterpret_cast<uint8_t *>(out + 16 * i);
+    memset(o, 0, 64);
+    const int comps = codec == 1 ? 4 : 3;
+    for (int y = 0; y < 4; ++y)
+      for (int x = 0; x < 4; ++x) memcpy(o + 4 * (4 * y + x), reinterpret_cast<const uint8_t *>(rows[y]) + comps * x, comps);
+  });
+}
+
+// Downsample of 2 x 2 block grids: lane i takes words[4 i .. 4 i + 3] (block rows 0, 0, 1, 1; columns 0, 1, 0, 1),
+// the palette-domain 2x2 average and encode_any, as the one-lane downsample kernel
+int wemul_downsample(int codec, int strategy, int n, const uint32_t *words, uint32_t *out) {
+  const int W = codec == 1 ? 4 : 2;
+  return run_wave(n, codec == 2, [=](int i) {
+    const uint32_t *b = words + 4 * W * i;
+    const uint32_t *const s4[2][2] = { { b, b + W }, { b + 2 * W, b + 3 * W } };
+    uint32_t px[16];
+    BlockStash stash;
+    if (codec == 2) { etc1_downsample_2x2(s4, px); encode_any<2>(px, (uint32_t)strategy, stash, out + 2 * i); }
+    else if (codec == 1) { dxt_downsample_2x2<1>(s4, px); encode_any<1>(px, 0u, stash, out + 4 * i); }
+    else { dxt_downsample_2x2<0>(s4, px); encode_any<0>(px, 0u, stash, out + 2 * i); }
+  });
+}
+
+int wemul_transcode(int n, const uint32_t *words, uint32_t *out) {
+  return run_wave(n, true, [=](int i) { put8(out + 2 * i, transcode_dxt1_block_to_etc1(words[2 * i], words[2 * i + 1])); });
+}
+
+// ETC1 Pad border, one lane per pad block (the ICAMD_PAD_BORDER_QUAD=0 form): lane i re-encodes words[2 i..] as pad kind
+// kinds[i] (0 column, 1 row, 2 corner).  Corner lanes return without searching, as in the kernel.
+int wemul_etc1_pad(int strategy, int n, const uint32_t *words, const uint8_t *kinds, uint32_t *out) {
+  return run_wave(n, false, [=](int i) {
+    put8(out + 2 * i, etc1_pad_block(words[2 * i], words[2 * i + 1], (int)kinds[i], (uint32_t)strategy));
+  });
+}
+
+}  // extern "C"
