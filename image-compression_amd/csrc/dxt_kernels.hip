@@ -13,7 +13,9 @@
 
 namespace icamd {
 
-template <int COMPS, bool DXT5, bool WIDE>
+// THROUGH (DXT1): the 8-byte blocks are written through to memory (store_through8), which needs an 8-byte aligned output;
+// launch_dxt takes the non-temporal form (store_stream8) for any other output pointer or image stride.
+template <int COMPS, bool DXT5, bool WIDE, bool THROUGH = false>
 __device__ __forceinline__ void dxt_encode_one(const GridParams &P) {
   const TileCoord t = locate_tile<WIDE>(P);
   if (!t.valid) return;
@@ -32,14 +34,15 @@ __device__ __forceinline__ void dxt_encode_one(const GridParams &P) {
     store_stream16(tile_dst<16>(P, t), a.lo, a.hi, c.lo, c.hi);
   } else {
     const Out8 c = encode_dxt_color_block(px, swap, false, stash);
-    store_stream8(tile_dst<8>(P, t), c.lo, c.hi);
+    if (THROUGH) store_through8(tile_dst<8>(P, t), c.lo, c.hi);
+    else store_stream8(tile_dst<8>(P, t), c.lo, c.hi);
   }
 }
 
 // Two vertically adjacent blocks per lane (256 x 2-block tiles): all eight row loads are issued before the first
 // block is encoded (twice the bytes in flight per wave: the 12-byte-per-lane loads of a 3-byte source keep a quarter
 // less in flight than RGBA8's), and the tile prologue (coordinates, 64-bit bases) is paid once for two blocks.
-template <int COMPS, bool DXT5>
+template <int COMPS, bool DXT5, bool THROUGH>
 __device__ __forceinline__ void dxt_encode_two(const GridParams &P) {
   const TileCoord t = locate_tile<true, 2>(P);
   __shared__ uint32_t lds_px[4][kThreadsPerWorkgroup][4];
@@ -66,7 +69,8 @@ __device__ __forceinline__ void dxt_encode_two(const GridParams &P) {
       store_stream16(tile_dst<16>(P, tr[r]), a.lo, a.hi, c.lo, c.hi);
     } else {
       const Out8 c = encode_dxt_color_block(px[r], swap, false, stash);
-      store_stream8(tile_dst<8>(P, tr[r]), c.lo, c.hi);
+      if (THROUGH) store_through8(tile_dst<8>(P, tr[r]), c.lo, c.hi);
+      else store_stream8(tile_dst<8>(P, tr[r]), c.lo, c.hi);
     }
   }
 }
@@ -79,16 +83,20 @@ extern "C" {
 // 3-byte sources only (r02 A/B, 16 x 4096^2, ms per launch, one block vs two blocks per lane): RGB888 0.183 -> 0.175
 // (noise), 0.190 -> 0.183 (flat), 0.174 -> 0.172 (smooth); RGBA8 0.190 -> 0.201 and DXT5 0.253 -> 0.259 got slower
 // (67-71 VGPRs instead of 51-54) and keep one block per lane.
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgb888_x2_kernel(GridParams P) { dxt_encode_two<3, false>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgb888_x2_kernel(GridParams P) { dxt_encode_two<3, false, true>(P); }
 #if defined(ICAMD_DXT1_RGBA8_X2_SMALL)
 // A/B only (r04, VERDICT r03 item 6: "fewer, fatter workgroups for <= 64 MiB launches so that a launch is one residency round"):
 // one 4096^2 image per call 16.0 -> 17.1 us with an event pair, 13.9 -> 15.2 us back to back -- slower, not shipped
 // (profiles/r04_single_image_timeline.txt, section c)
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_x2_kernel(GridParams P) { dxt_encode_two<4, false>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_x2_kernel(GridParams P) { dxt_encode_two<4, false, false>(P); }
 #endif
 
-// *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_kernel(GridParams P) { dxt_encode_one<4, false, true>(P); }
+// *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape.  The wide DXT1
+// kernels write through (store_through8); *_nt_kernel: the same with non-temporal stores, for outputs not 8-byte aligned.
+// (r07 A/B, 16 x 4096^2, ms per step: RGBA8 0.195 -> 0.187, RGB888 0.158 -> 0.144; profiles/r07_ab_dxt1_store_policy.log)
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_kernel(GridParams P) { dxt_encode_one<4, false, true, true>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_nt_kernel(GridParams P) { dxt_encode_one<4, false, true>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgb888_x2_nt_kernel(GridParams P) { dxt_encode_two<3, false, false>(P); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt5_rgba8_kernel(GridParams P) { dxt_encode_one<4, true, true>(P); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_narrow_kernel(GridParams P) { dxt_encode_one<4, false, false>(P); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgb888_narrow_kernel(GridParams P) { dxt_encode_one<3, false, false>(P); }
@@ -110,8 +118,12 @@ hipError_t launch_dxt(int codec, int comps, const GridParams &P, hipStream_t str
   if (comps == 4 && (uint64_t)P.n_images * P.block_rows * P.block_cols <= (1ull << 20))  // one 4096^2 image or less
     return launch_tiled(icamd_dxt1_rgba8_x2_kernel, icamd_dxt1_rgba8_narrow_kernel, P, stream, 8, 2);
 #endif
-  if (comps == 4) return launch_tiled(icamd_dxt1_rgba8_kernel, icamd_dxt1_rgba8_narrow_kernel, P, stream);
-  return launch_tiled(icamd_dxt1_rgb888_x2_kernel, icamd_dxt1_rgb888_narrow_kernel, P, stream, 8, 2);
+  // every block is 8-byte aligned iff the output base and the image stride are (block offsets are multiples of 8)
+  const bool through = (((uintptr_t)P.dst | P.dst_image_stride) & 7u) == 0;
+  if (comps == 4)
+    return launch_tiled(through ? icamd_dxt1_rgba8_kernel : icamd_dxt1_rgba8_nt_kernel, icamd_dxt1_rgba8_narrow_kernel, P, stream);
+  return launch_tiled(through ? icamd_dxt1_rgb888_x2_kernel : icamd_dxt1_rgb888_x2_nt_kernel, icamd_dxt1_rgb888_narrow_kernel, P,
+                      stream, 8, 2);
 }
 
 }  // namespace icamd

@@ -1,7 +1,9 @@
 // r05 micro-benchmark (gfx950): what the HBM delivers to the plainest streaming kernels over 1 GiB -- read only (non-temporal and
 // plain dwordx4 loads, 16 B per lane and instruction, 1 / 4 loads in flight per lane), write only (non-temporal / plain), copy
 // (float4, the figure MI355X_MICROARCH.md quotes), and a read : write mix of 8 : 1 like DXT1 from RGBA8 -- the ceiling the
-// roofline fractions of the memory-bound encoders should be read against.
+// roofline fractions of the memory-bound encoders should be read against.  r07 adds the parts of that mix (no stores, a linear read,
+// 16-byte stores, XCD-consecutive tiles, one workgroup per block-row span) and store cache policies, each also timed with an event
+// in front of every launch as bench.py does (profiles/r07_ab_dxt1_store_policy.log).
 // Build: hipcc --offload-arch=gfx950 -O3 scripts/ubench_hbm.hip -o scripts/scratch/ubench_hbm
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -63,6 +65,77 @@ template <int MODE> __global__ void __launch_bounds__(256) k_mix_quad(const u4 *
   }
   if (t == 0u) __builtin_nontemporal_store((u2){ x, y }, dst + k);
 }
+
+// ---- r07: splitting the "mix 8 : 1" shape into its parts (16 x 4096^2 RGBA8 = 1 GiB in, 8 B per 4 x 4 block out) ----
+// XCD: workgroup b runs on XCD b % 8; XCD_SWZ hands XCD x the x-th eighth of the tiles in order, so the workgroups resident on one
+// XCD at the same time read consecutive tiles (n_wg % 8 == 0)
+template <bool XCD_SWZ> __device__ inline uint32_t wg_id(uint32_t n_wg) {
+  const uint32_t b = blockIdx.x;
+  return XCD_SWZ ? (b & 7u) * (n_wg >> 3) + (b >> 3) : b;
+}
+// WT: the store's cache policy.  0: non-temporal (nt, store_stream8); 1: written through to memory (sc0 sc1, a system-scope relaxed
+// store); 2: sc1 (an agent-scope relaxed store); 3 / 4: buffer stores with sc0 sc1 nt / sc0 set through the builtin's policy operand
+template <int WT> __device__ inline void st8(u2 *p, u2 v) {
+  if (WT == 1) __hip_atomic_store(reinterpret_cast<uint64_t *>(p), (uint64_t)v.x | (uint64_t)v.y << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  else if (WT == 2) __hip_atomic_store(reinterpret_cast<uint64_t *>(p), (uint64_t)v.x | (uint64_t)v.y << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if (WT >= 3) {
+    // workgroup-uniform base (the workgroup's 2 KiB of output), lane offset in bytes
+    u2 *base = p - threadIdx.x;
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)(threadIdx.x * 8u), 0, WT == 3 ? 19 : 1);
+  } else __builtin_nontemporal_store(v, p);
+}
+// the mix shape (k_mix, 4096-pixel rows); STORE = 0: no stores (kept loads), 1: 8 B per lane, 2: 16 B from every even lane (its block
+// and its neighbour's), WT / XCD_SWZ as above
+template <int STORE, int WT, bool XCD_SWZ> __global__ void __launch_bounds__(256) k_mix2(const u4 *src, u2 *dst, uint32_t n_blocks) {
+  const uint32_t k = wg_id<XCD_SWZ>(gridDim.x) * 256u + threadIdx.x, row16 = 1024u;
+  const uint32_t brow = k >> 10, bcol = k & 1023u;
+  const u4 *p = src + (size_t)brow * 4u * row16 + bcol;
+  u4 a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + row16), c = __builtin_nontemporal_load(p + 2 * row16),
+     d = __builtin_nontemporal_load(p + 3 * row16);
+  a ^= b; c ^= d; a ^= c;
+  const u2 v = { a.x ^ a.y, a.z ^ a.w };
+  if (STORE == 0) { if ((v.x ^ v.y) == 0x12345678u) dst[k] = v; }
+  else if (STORE == 1) st8<WT>(dst + k, v);
+  else {
+    const uint32_t nx = (uint32_t)__shfl_xor((int)v.x, 1), ny = (uint32_t)__shfl_xor((int)v.y, 1);
+    if ((threadIdx.x & 1u) == 0u) __builtin_nontemporal_store((u4){ v.x, v.y, nx, ny }, reinterpret_cast<u4 *>(dst + k));
+  }
+}
+// linear read (a workgroup streams 16 KiB: 4 x 4 KiB, k_read<true, 4>) + an 8-byte store per lane
+__global__ void __launch_bounds__(256) k_lin_st8(const u4 *src, u2 *dst, uint32_t n_blocks) {
+  const uint32_t base = blockIdx.x * 1024u + threadIdx.x;
+  u4 a = __builtin_nontemporal_load(src + base), b = __builtin_nontemporal_load(src + base + 256u),
+     c = __builtin_nontemporal_load(src + base + 512u), d = __builtin_nontemporal_load(src + base + 768u);
+  a ^= b; c ^= d; a ^= c;
+  __builtin_nontemporal_store((u2){ a.x ^ a.y, a.z ^ a.w }, dst + blockIdx.x * 256u + threadIdx.x);
+}
+// one workgroup per 64 KiB block row of a 4096-pixel texture (1 024 blocks): load 4 r + q (q = 0..3) of lane l is pixel row r of
+// block q * 256 + l, so the workgroup reads its span linearly (16 x 4 KiB) with no transpose, and writes 4 x 2 KiB = 8 KiB
+// contiguously.  PIPE: the blocks are taken one at a time (4 loads, then the store) instead of all 16 loads first.
+template <bool XCD_SWZ, bool PIPE> __global__ void __launch_bounds__(256) k_span(const u4 *src, u2 *dst, uint32_t n_blocks) {
+  const uint32_t brow = wg_id<XCD_SWZ>(gridDim.x), l = threadIdx.x;
+  const u4 *p = src + (size_t)brow * 4096u + l;
+  u2 *q = dst + (size_t)brow * 1024u + l;
+  if (PIPE) {
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      u4 a = __builtin_nontemporal_load(p + 256 * j), b = __builtin_nontemporal_load(p + 1024 + 256 * j),
+         c = __builtin_nontemporal_load(p + 2048 + 256 * j), d = __builtin_nontemporal_load(p + 3072 + 256 * j);
+      a ^= b; c ^= d; a ^= c;
+      __builtin_nontemporal_store((u2){ a.x ^ a.y, a.z ^ a.w }, q + 256 * j);
+    }
+  } else {
+    u4 v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = __builtin_nontemporal_load(p + 256 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      u4 a = v[j] ^ v[4 + j] ^ v[8 + j] ^ v[12 + j];
+      __builtin_nontemporal_store((u2){ a.x ^ a.y, a.z ^ a.w }, q + 256 * j);
+    }
+  }
+}
 template <typename F> double timeit(F f, int reps = 30) {
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 10; ++i) f();
@@ -70,6 +143,17 @@ template <typename F> double timeit(F f, int reps = 30) {
   for (int i = 0; i < reps; ++i) f();
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
+  return ms / reps;
+}
+// bench.py's way: an event recorded in front of every launch (the step time includes the gap between launches)
+template <typename F> double timeit_ev(F f, int reps = 30) {
+  hipEvent_t ev[31];
+  for (int i = 0; i <= reps; ++i) hipEventCreate(&ev[i]);
+  for (int i = 0; i < 10; ++i) f();
+  for (int i = 0; i < reps; ++i) { hipEventRecord(ev[i]); f(); }
+  hipEventRecord(ev[reps]); hipEventSynchronize(ev[reps]);
+  float ms; hipEventElapsedTime(&ms, ev[0], ev[reps]);
+  for (int i = 0; i <= reps; ++i) hipEventDestroy(ev[i]);
   return ms / reps;
 }
 int main() {
@@ -96,5 +180,24 @@ int main() {
     RUN("mix 8 : 1, rows padded by 32 B", 72.0 * nbq, hipLaunchKernelGGL(k_mix, dim3(nbq / 256), dim3(256), 0, 0, a, (u2 *)b, nbq, row16, pad2))
     RUN("mix 8 : 1, 8192 px rows", 1.125 * bytes, hipLaunchKernelGGL(k_mix, dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb, 2048u, 2048u))
     RUN("mix 8 : 1, 1024 px rows", 1.125 * bytes, hipLaunchKernelGGL(k_mix, dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb, 256u, 256u)) }
+  // r07: the parts of the mix shape, and the shapes and store policies the issue asked about (all on 4096-pixel rows)
+  { const uint32_t nb = n16 / 4;
+#define RUN2(label, bytes_moved, ...) { double ms = timeit([&] { __VA_ARGS__; }), me = timeit_ev([&] { __VA_ARGS__; }); \
+      printf("%-40s %.4f ms  %7.1f GB/s   event per launch %.4f ms\n", label, ms, (bytes_moved) / ms / 1e6, me); }
+    for (int rep = 0; rep < 2; ++rep) {
+      RUN2("r07 mix 8 : 1 (k_mix2, 8 B stores)", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 0, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, no stores", 1.0 * bytes, hipLaunchKernelGGL((k_mix2<0, 0, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 linear read + 8 B stores", 1.125 * bytes, hipLaunchKernelGGL(k_lin_st8, dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, 16 B stores / 2 lanes", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<2, 0, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, XCD-consecutive tiles", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 0, true>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, write-through stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 1, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, sc1 stores (agent)", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 2, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, sc0 sc1 nt buffer stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 3, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 mix shape, sc0 buffer stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 4, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 block-row span, 16 loads first", 1.125 * bytes, hipLaunchKernelGGL((k_span<false, false>), dim3(nb / 1024), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 block-row span, block by block", 1.125 * bytes, hipLaunchKernelGGL((k_span<false, true>), dim3(nb / 1024), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 block-row span + XCD-consecutive", 1.125 * bytes, hipLaunchKernelGGL((k_span<true, false>), dim3(nb / 1024), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r07 span + XCD-consecutive, by block", 1.125 * bytes, hipLaunchKernelGGL((k_span<true, true>), dim3(nb / 1024), dim3(256), 0, 0, a, (u2 *)b, nb))
+    } }
   return 0;
 }
