@@ -194,7 +194,7 @@ __device__ __forceinline__ void downsample_one(const BlockOpParams &P, uint32_t 
 
 // Lanes per workgroup: the kernels that run an ETC1 codeword SEARCH per output block (Downsample and the Pad border with
 // kSplitHorizontally / kSplitVertically / kSmallerError) are launched as one-wave workgroups like the encoders (r05,
-// etc1_kernels.hip ICAMD_ETC1_WAVE_WORKGROUPS: the search's cost depends on the content, and a four-wave workgroup holds its
+// etc1_kernels.hip etc1_wave_workgroups: the search's cost depends on the content, and a four-wave workgroup holds its
 // slots until its slowest wave is done); everything else keeps 256.
 constexpr int blockop_lanes(int codec, int strategy, int part) {
   return (codec == ICAMD_ETC1 && strategy != 3 && part != 1) ? 64 : kThreadsPerWorkgroup;
@@ -274,7 +274,7 @@ extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_to
   blocks[k] = make_uint2(o.lo, o.hi);
 }
 
-// A/B switch (ICAMD_PAD_BORDER_QUAD=0: one lane per pad block, the r04 form); read once
+// ICAMD_PAD_BORDER_QUAD=0: one lane per pad block, the r04 form; read once.  Kept: the GPU tests run both forms through it.
 static bool pad_border_quad() {
   static const bool on = [] { const char *e = getenv("ICAMD_PAD_BORDER_QUAD"); return !(e && e[0] == '0'); }();
   return on;
@@ -317,9 +317,8 @@ hipError_t launch_pad(int codec, const BlockOpParams &P, hipStream_t stream) {
 hipError_t launch_downsample(int codec, const BlockOpParams &P, hipStream_t stream) {
   if (P.total_out == 0) return hipSuccess;
   const dim3 grid((P.total_out + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), block(kThreadsPerWorkgroup);
-  // row tiles where a row fills a workgroup (ICAMD_DOWNSAMPLE_ROW_TILES=0 keeps the linear launch for the A/B)
-  static const bool row_tiles_on = [] { const char *e = getenv("ICAMD_DOWNSAMPLE_ROW_TILES"); return !(e && e[0] == '0'); }();
-  const bool rows = row_tiles_on && P.in_rows > 1 && P.in_cols > 1 && P.out_cols >= (uint32_t)kThreadsPerWorkgroup &&
+  // row tiles where a row fills a workgroup (small grids keep the linear launch)
+  const bool rows = P.in_rows > 1 && P.in_cols > 1 && P.out_cols >= (uint32_t)kThreadsPerWorkgroup &&
                     P.out_rows <= 65535u && P.n_images <= 65535u;
   const dim3 rgrid((P.out_cols + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup, P.out_rows, P.n_images);
   if (codec == ICAMD_DXT1) {

@@ -84,12 +84,8 @@ extern "C" {
 // (noise), 0.190 -> 0.183 (flat), 0.174 -> 0.172 (smooth); RGBA8 0.190 -> 0.201 and DXT5 0.253 -> 0.259 got slower
 // (67-71 VGPRs instead of 51-54) and keep one block per lane.
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgb888_x2_kernel(GridParams P) { dxt_encode_two<3, false, true>(P); }
-#if defined(ICAMD_DXT1_RGBA8_X2_SMALL)
-// A/B only (r04, VERDICT r03 item 6: "fewer, fatter workgroups for <= 64 MiB launches so that a launch is one residency round"):
-// one 4096^2 image per call 16.0 -> 17.1 us with an event pair, 13.9 -> 15.2 us back to back -- slower, not shipped
-// (profiles/r04_single_image_timeline.txt, section c)
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_rgba8_x2_kernel(GridParams P) { dxt_encode_two<4, false, false>(P); }
-#endif
+// (r04: the same two-block form for RGBA8 launches of one 4096^2 image or less was 1.1-1.3 us slower per call, not shipped;
+// profiles/r04_single_image_timeline.txt, section c)
 
 // *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape.  The wide DXT1
 // kernels write through (store_through8); *_nt_kernel: the same with non-temporal stores, for outputs not 8-byte aligned.
@@ -114,10 +110,6 @@ hipError_t launch_dxt(int codec, int comps, const GridParams &P, hipStream_t str
     if (comps != 4) return hipErrorInvalidValue;
     return launch_tiled(icamd_dxt5_rgba8_kernel, icamd_dxt5_rgba8_narrow_kernel, P, stream);
   }
-#if defined(ICAMD_DXT1_RGBA8_X2_SMALL)
-  if (comps == 4 && (uint64_t)P.n_images * P.block_rows * P.block_cols <= (1ull << 20))  // one 4096^2 image or less
-    return launch_tiled(icamd_dxt1_rgba8_x2_kernel, icamd_dxt1_rgba8_narrow_kernel, P, stream, 8, 2);
-#endif
   // every block is 8-byte aligned iff the output base and the image stride are (block offsets are multiples of 8)
   const bool through = (((uintptr_t)P.dst | P.dst_image_stride) & 7u) == 0;
   if (comps == 4)

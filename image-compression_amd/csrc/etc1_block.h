@@ -24,7 +24,8 @@
 namespace icamd {
 
 // Diagnostics build only (-DICAMD_ETC1_STATS, never in libic_amd.so as shipped): per-wave counts of which evaluation each
-// codeword of each search took, read back with icamd_debug_etc1_stats (scripts/etc1_path_stats.py).
+// codeword of each search took, read back with icamd_debug_etc1_stats (scripts/etc1_path_stats.py).  Kept: an instrument, not a
+// variant -- the ETC1 pre-screens still planned are judged with it.
 #if defined(ICAMD_ETC1_STATS) && !defined(ICAMD_HOST_EMULATION)
 __device__ unsigned int g_etc1_stats[16];
 #define ICAMD_ETC1_COUNT(i) do { if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_etc1_stats[i], 1u); } while (0)
@@ -197,12 +198,6 @@ ICAMD_DEV int32_t eval_codeword_mixed(const uint32_t px[16], const uint32_t abs2
 // veto the shortcut, the tier or a pruning step for everyone (a saturated flat colour, typically) no longer does.
 // (SKIP is a template parameter so that waves without such lanes run exactly the code they ran before: r03 A/B, a run-time
 // flag alone cost noise content 5 %.)
-// ICAMD_ETC1_NO_PSUM (A/B only): recompute 2 (r + g + b) of a pixel where it is used instead of keeping 16 of them live
-#if defined(ICAMD_ETC1_NO_PSUM)
-#define ICAMD_PSUM(q) udot4(px[q], 0x00020202u, 0u)
-#else
-#define ICAMD_PSUM(q) psum[q]
-#endif
 template <int FLIP, int S, bool TIER, bool PRUNE, bool SKIP = false>
 ICAMD_DEV EtcSubResult search_codewords(const uint32_t px[16], const uint32_t psum[16], const EtcBase &base,
                                         const uint32_t bch[3], const uint32_t sub_sum[3], bool skip_lane = false) {
@@ -224,7 +219,7 @@ ICAMD_DEV EtcSubResult search_codewords(const uint32_t px[16], const uint32_t ps
   if (fast) {
     ICAMD_UNROLL
     for (int j = 0; j < 8; ++j) {
-      abs2[j] = sad_u32(ICAMD_PSUM((sub_pixel<FLIP, S>(j))), bsum2, 0u);
+      abs2[j] = sad_u32(psum[sub_pixel<FLIP, S>(j)], bsum2, 0u);
       s2 += abs2[j];
     }
     // Sum_j E0 = 2 * (base . sub_sum) - 8 |base|^2 : puts the shortcut's scores on the scale of eval_codeword
@@ -259,7 +254,7 @@ ICAMD_DEV EtcSubResult search_codewords(const uint32_t px[16], const uint32_t ps
     ICAMD_UNROLL
     for (int j = 0; j < 8; ++j) {
       const uint32_t q = sub_pixel<FLIP, S>(j);
-      const int32_t neg = (int32_t)(ICAMD_PSUM(q) - bsum2) >> 31;  // -1 iff s < 0
+      const int32_t neg = (int32_t)(psum[q] - bsum2) >> 31;  // -1 iff s < 0
       k0[j] = (int32_t)(udot4(px[q], base_px, 0u) << 6) + c3 + 2 * neg;
     }
   }
@@ -354,7 +349,7 @@ ICAMD_DEV EtcSubResult search_codewords(const uint32_t px[16], const uint32_t ps
     uint32_t acc = 0;
     ICAMD_UNROLL
     for (int j = 7; j >= 0; --j) {
-      acc = alignbit(acc, ICAMD_PSUM((sub_pixel<FLIP, S>(j))) - bsum2, 31);  // s < 0
+      acc = alignbit(acc, psum[sub_pixel<FLIP, S>(j)] - bsum2, 31);  // s < 0
       acc = alignbit(acc, thr - abs2[j], 31);                          // 2|s| > 3 (a + b): magnitude b
     }
     r.fields = won_fast ? ~acc << 16 : r.fields;
@@ -496,9 +491,8 @@ ICAMD_DEV uint32_t assemble_indices(uint32_t f0, uint32_t f1, bool flip) {
 // (register pressure), so a wave of mostly calm blocks takes the one without.  Only a performance choice: both produce
 // the same bytes.
 // (threshold sweep 564 / 200 / 100 / 50: profiles/r03_ab_etc1_mixed_tier.log, P)
-#ifndef ICAMD_ETC1_BUSY_SPREAD
-#define ICAMD_ETC1_BUSY_SPREAD (4u * 141u)
-#endif
+// (a constant, not a switch: it keeps the name tests/host_emul/wave_emul.cc reads it by; a -D of that name no longer compiles)
+constexpr uint32_t ICAMD_ETC1_BUSY_SPREAD = 4u * 141u;
 ICAMD_DEV uint32_t etc1_block_spread(const uint32_t px[16]) {
   uint32_t lo = 0xffffffffu, hi = 0u;
   ICAMD_UNROLL
@@ -688,9 +682,6 @@ ICAMD_DEV Out8 encode_etc1_block(const uint32_t px[16], uint32_t strategy, bool 
 // Calm waves take the instantiation WITHOUT the mixed tier: with it (and pruning) smooth content measured 1.466 -> 1.505 ms
 // and flat 1.35 -> 1.42 ms (r03, profiles/r03_ab_etc1_mixed_tier.log) -- there the tier's register pressure costs more than
 // its arithmetic saves.
-#ifndef ICAMD_ETC1_CALM_TIER
-#define ICAMD_ETC1_CALM_TIER false
-#endif
 
 // The part of etc1_encode_one after the block is in registers: the per-wave choice of instantiation.  constant / busy are
 // per-lane properties of the block (one colour; sums r + g + b spread by ICAMD_ETC1_BUSY_SPREAD or more).
@@ -702,13 +693,13 @@ ICAMD_DEV Out8 etc1_encode_classified(const uint32_t px[16], bool constant, bool
   // decisions nor count for the content probe, and their results are replaced afterwards.
   if (wave_all(!constant)) {  // (the common case: exactly the code of a build without the one-colour forms)
     if (wave_count(busy) >= 48u) c = encode_etc1_block<true, false>(px, (uint32_t)STRATEGY);  // busy wave: mixed tier, no pruning
-    else c = encode_etc1_block<ICAMD_ETC1_CALM_TIER, true>(px, (uint32_t)STRATEGY);           // calm wave: pruning (+ tier?)
+    else c = encode_etc1_block<false, true>(px, (uint32_t)STRATEGY);                              // calm wave: pruning, no tier
   } else if (wave_all(constant)) {
     c = encode_etc1_constant_block(px[0], (uint32_t)STRATEGY);
   } else {
     if (4u * wave_count(!constant && busy) >= 3u * wave_count(!constant))
       c = encode_etc1_block<true, false, true>(px, (uint32_t)STRATEGY, constant);
-    else c = encode_etc1_block<ICAMD_ETC1_CALM_TIER, true, true>(px, (uint32_t)STRATEGY, constant);
+    else c = encode_etc1_block<false, true, true>(px, (uint32_t)STRATEGY, constant);
     const Out8 cc = encode_etc1_constant_block(px[0], (uint32_t)STRATEGY);
     c.lo = constant ? cc.lo : c.lo;
     c.hi = constant ? cc.hi : c.hi;

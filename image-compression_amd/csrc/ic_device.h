@@ -154,7 +154,7 @@ ICAMD_DEV int32_t imax(int32_t a, int32_t b) { return max(a, b); }
 
 // True iff the predicate holds in every active lane of the wave (the emulation has one "lane").
 #if defined(ICAMD_HOST_EMULATION) && defined(ICAMD_EMUL_WAVE)
-// tests/host_emul/wave_emul.cc: the lanes of an emulated wave run as host threads and vote together; a vote's site is
+// ICAMD_EMUL_WAVE (tests/host_emul/wave_emul.cc): the lanes of an emulated wave run as host threads and vote together; a vote's site is
 // its source line (the optimiser may duplicate the code around it)
 bool wave_all_at(bool p, const char *file, int line);
 uint32_t wave_count_at(bool p, const char *file, int line);

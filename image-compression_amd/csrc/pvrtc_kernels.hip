@@ -40,10 +40,7 @@ namespace {
 
 constexpr int kMorphLanes = 256;
 constexpr int kEncodeLanes = 256;
-#ifndef ICAMD_PVRTC_FULL_CHIP_WAVES
-#define ICAMD_PVRTC_FULL_CHIP_WAVES 2u
-#endif
-constexpr uint32_t kFullChipLanes = 256u * 4u * 64u * ICAMD_PVRTC_FULL_CHIP_WAVES;  // two waves on each of the 1 024 SIMDs
+constexpr uint32_t kFullChipLanes = 256u * 4u * 64u * 2u;  // two waves on each of the 1 024 SIMDs
 
 __device__ __forceinline__ void load_block32(const uint32_t *p, uint32_t n, uint32_t px[32]) {
 #pragma unroll
@@ -396,7 +393,7 @@ __device__ __forceinline__ void pvrtc2_encode(const PvrtcLaunch &L, uint32_t wg,
     // pixel row r of the strip -> slot r % kRowRing.  The walk ends at row 4 K (the first row below the strip); the three
     // requests past it keep the wait counts uniform but re-fetch row 4 K (an L2 hit) instead of 3 / 32 more HBM bytes.
     const uint32_t last_row = 4u << sb;
-#if defined(ICAMD_PVRTC_SCALAR_ROW)  // r04's failing experiment, kept reproducible (profiles/r04_ab_pvrtc_scalar_ring.log)
+#if defined(ICAMD_PVRTC_SCALAR_ROW)  // kept: tests/test_isa_guards.py builds it (r04's experiment, profiles/r04_ab_pvrtc_scalar_ring.log)
     const uint32_t by0_dma = (uint32_t)__builtin_amdgcn_readfirstlane((int)by0);
 #else
     const uint32_t by0_dma = by0;
@@ -411,48 +408,6 @@ __device__ __forceinline__ void pvrtc2_encode(const PvrtcLaunch &L, uint32_t wg,
 #pragma unroll
       for (uint32_t r = 0; r + 1 < kRowRing; ++r) dma_row(r);
     }
-#if defined(ICAMD_PVRTC_FUSION_PROBE)
-    // r04 measurement aid, NEVER in the shipped library: what would one pass over the pixels cost in situ?  Every pixel row the
-    // strip consumes also feeds the morph reduction of its block (the five axes' first-min / first-max keys); every fourth row
-    // the block is finished like pvrtc_extremes does it (ten data-dependent pixel look-ups -- here from the row ring --, five
-    // v_sad_u8, the best-axis scan, the brightness order, two channel reductions).  The results are only kept alive, not used:
-    // the encode kernel's output is unchanged, its time shows the VALU / register price of fusing the morph in.
-    uint32_t pr_lmin = 0xffffffffu, pr_lmax = 0u, pr_rbmin = 0xffffffffu, pr_rbmax = 0u, pr_gamin = 0xffffffffu, pr_gamax = 0u, pr_acc = 0u;
-    auto probe_row = [&](uint32_t r, const uint32_t *pixels) {
-      const uint32_t q = r & 3u;
-#pragma unroll
-      for (int x = 0; x < 8; ++x) {
-        const uint32_t c = pixels[x], i = (uint32_t)(x & 3);
-        const uint32_t idx4 = (8u * q + (uint32_t)(x & 4)) * 0x01010101u + 0x03020100u;
-        const uint32_t up1 = 31u - 2u * (8u * q + (uint32_t)x), up = up1 * 0x00010001u;
-        const uint32_t kl = perm(udot4(c, 0x001c964du, 0u), idx4, 0x0c0c0500u | i);
-        const uint32_t k_rb = perm(c, idx4, 0x06000400u | i | i << 16), k_ga = perm(c, idx4, 0x07000500u | i | i << 16);
-        pr_rbmin = pk_min_u16(pr_rbmin, k_rb); pr_gamin = pk_min_u16(pr_gamin, k_ga);
-        pr_rbmax = pk_max_u16(pr_rbmax, k_rb + up); pr_gamax = pk_max_u16(pr_gamax, k_ga + up);
-        pr_lmin = umin(pr_lmin, kl); pr_lmax = umax(pr_lmax, kl + up1);
-      }
-      if (q == 3u) {
-        const uint32_t kmin[5] = { pr_lmin, pr_rbmin & 0xffffu, pr_gamin & 0xffffu, pr_rbmin >> 16, pr_gamin >> 16 };
-        const uint32_t kmax[5] = { pr_lmax, pr_rbmax & 0xffffu, pr_gamax & 0xffffu, pr_rbmax >> 16, pr_gamax >> 16 };
-        uint32_t best_diff = 0, best_lo = 0, best_hi = 0;
-#pragma unroll
-        for (int a = 0; a < 5; ++a) {
-          uint32_t lo, hi;
-          const uint32_t i0 = kmin[a] & 31u, i1 = 31u - (kmax[a] & 31u);
-          const uint32_t a0 = ring_lane_byte + (i0 >> 3) * 2048u + ((i0 >> 2) & 1u) * 1024u + (i0 & 3u) * 4u;
-          const uint32_t a1 = ring_lane_byte + (i1 >> 3) * 2048u + ((i1 >> 2) & 1u) * 1024u + (i1 & 3u) * 4u;
-          asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(lo), "=&v"(hi) : "v"(a0), "v"(a1) : "memory");
-          hi = (kmax[a] >> 8) == 0u ? img[0] * 0u + lo : hi;
-          const uint32_t d = sad_u8(lo, hi, 0u);
-          const bool better = (a == 0) || d > best_diff;
-          best_lo = better ? lo : best_lo; best_hi = better ? hi : best_hi; best_diff = better ? d : best_diff;
-        }
-        const bool swap = udot4(best_hi, 0x01010101u, 0u) < udot4(best_lo, 0x01010101u, 0u);
-        pr_acc ^= channel_reduce(swap ? best_hi : best_lo, false) + channel_reduce(swap ? best_lo : best_hi, true);
-        pr_lmin = pr_rbmin = pr_gamin = 0xffffffffu; pr_lmax = pr_rbmax = pr_gamax = 0u;
-      }
-    };
-#endif
     auto load_px = [&](uint32_t r, uint32_t *pixels, uint32_t *right_px) {
       if (DMA) {
         // rows r + 1 and r + 2 (four DMA instructions) may still be in flight; row r and everything older has landed
@@ -464,9 +419,6 @@ __device__ __forceinline__ void pvrtc2_encode(const PvrtcLaunch &L, uint32_t wg,
         pixels[4] = v1.x; pixels[5] = v1.y; pixels[6] = v1.z; pixels[7] = v1.w;
         // the slot of row r - 1 (read one call ago, its ds_reads long complete) takes row r + 3
         dma_row(r + kRowRing - 1u);
-#if defined(ICAMD_PVRTC_FUSION_PROBE)
-        probe_row(r, pixels);
-#endif
         return;
       }
       // n = 2^log2_n <= 32 768: the pixel index fits 32 bits -- a shift, not a 64-bit multiply
@@ -537,9 +489,6 @@ __device__ __forceinline__ void pvrtc2_encode(const PvrtcLaunch &L, uint32_t wg,
       return wave_end ? edge_row[j] : from_lane;
     };
     pvrtc_encode_strip<EXCHANGE>(1u << sb, load_px, load_colours, store, right_of);
-#if defined(ICAMD_PVRTC_FUSION_PROBE)
-    asm volatile("" :: "v"(pr_acc));
-#endif
   }
   if (!L.stage_stores) return;
   // Write-out: every lane stores 16 bytes (two Z-adjacent blocks) per round; 32 lanes cover one 512-byte run (sb = 3).
@@ -566,14 +515,9 @@ __device__ __forceinline__ void pvrtc2_encode(const PvrtcLaunch &L, uint32_t wg,
 extern "C" __global__ void __launch_bounds__(kEncodeLanes) icamd_pvrtc2_encode_kernel(PvrtcLaunch L) {
   __shared__ uint32_t lds[kStageSlots * 2];
   __shared__ uint32_t lds_edge[4 * 8];  // per wave: 32 bytes = the values right of its last lane's strip
-#if !defined(ICAMD_PVRTC_NO_ROW_DMA)  // (the register-path build, for A/B runs: -DICAMD_PVRTC_NO_ROW_DMA)
+#if !defined(ICAMD_PVRTC_NO_ROW_DMA)  // kept: tests/test_isa_guards.py builds the register path (-DICAMD_PVRTC_NO_ROW_DMA)
   __shared__ __attribute__((aligned(16))) uint32_t lds_rows[4 * kRowRing * 512];  // per wave: kRowRing row slots of 2 KiB
-#if defined(ICAMD_PVRTC_XCD_REMAP)
-  const uint32_t nwg = gridDim.x, wg = (nwg & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nwg >> 3) + (blockIdx.x >> 3);
-  pvrtc2_encode<true, true>(L, wg, lds, lds_edge, lds_rows);
-#else
   pvrtc2_encode<true, true>(L, blockIdx.x, lds, lds_edge, lds_rows);
-#endif
 #else
   pvrtc2_encode<true>(L, blockIdx.x, lds, lds_edge);
 #endif
@@ -788,12 +732,10 @@ __device__ __forceinline__ void pvrtc2_onepass_body(const PvrtcLaunch &L, uint32
   };
   pvrtc_onepass_strip(K, image0, tick, lookup10, exchange, store);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row requests past the end of the strip
-#if !defined(ICAMD_PVRTC_ONEPASS_NO_VGPR_CLAIM)
   // Claim 176 VGPRs (the walk uses ~120): LDS already limits a CU to 8 waves, and with at most two waves per SIMD the
   // dispatcher cannot stack the one- and two-wave workgroups of 512^2 / 1024^2 textures three or four deep on one SIMD while
   // another idles once workgroups retire out of step (r05 A/B, 256 x 1024^2 in 16-block strips: 0.534 -> 0.425 ms).
   asm volatile("" ::: "v175");
-#endif
 }
 
 extern "C" __global__ void __launch_bounds__(512) icamd_pvrtc2_onepass_kernel(PvrtcLaunch L) {
