@@ -48,6 +48,7 @@ EXPORTS = [
     "icamd_rccl_available", "icamd_rccl_get_unique_id", "icamd_rccl_comm_init", "icamd_rccl_comm_destroy", "icamd_gather_blocks_rccl",
     "icamd_mip_max_levels", "icamd_mip_chain_size", "icamd_mip_workspace_size", "icamd_encode_mips_device",
     "icamd_mip_pyramid_device", "icamd_compress_mips",
+    "icamd_measure_error_device", "icamd_measure_error", "icamd_metric_kernel_name",
 ]
 RCCL_UNIQUE_ID_BYTES = 128
 CONTAINER_DDS, CONTAINER_KTX, CONTAINER_PKM, CONTAINER_PVR = 0, 1, 2, 3
@@ -176,6 +177,14 @@ def lib():
             L.icamd_mip_pyramid_device.argtypes = [_ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
             L.icamd_compress_mips.restype = _ci
             L.icamd_compress_mips.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
+        if not LIB_OVERRIDDEN or hasattr(L, "icamd_measure_error_device"):  # quality-metric entry points
+            L.icamd_measure_error_device.restype = _ci
+            L.icamd_measure_error_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp,
+                                                     _vp]
+            L.icamd_measure_error.restype = _ci
+            L.icamd_measure_error.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _vp]
+            L.icamd_metric_kernel_name.restype = ctypes.c_char_p
+            L.icamd_metric_kernel_name.argtypes = [_ci, _ci]
         L.icamd_device_count.restype = _ci
         L.icamd_last_error.restype = ctypes.c_char_p
         L.icamd_version.restype = ctypes.c_char_p
@@ -785,3 +794,66 @@ def compress_mips_host(compressor, fmt, buffer, height, width, *, levels=None, p
     if not _check(st, "icamd_compress_mips"):
         return None
     return out[:out_size].tobytes()
+
+
+# ---- quality metric (icamd_measure_error_device): compressed blocks against their source pixels
+
+ERROR_STATS_BYTES = 48  # sizeof(icamd_error_stats): uint64 sse[4], uint32 max_abs[4]
+
+
+def metric_kernel_name(codec, src_components):
+    return lib().icamd_metric_kernel_name(codec, src_components).decode()
+
+
+def _split_stats(raw):
+    """[n, 48] uint8 records -> ([n, 4] int64 sse, [n, 4] int32 max_abs); same device, no synchronisation."""
+    return raw[:, :32].contiguous().view(torch.int64), raw[:, 32:].contiguous().view(torch.int32)
+
+
+def measure_error_device(codec, src, blocks, height, width, src_components, *, swap_rb=False, grid_height=None,
+                         grid_width=None, row_stride_bytes=None, n_images=1, src_image_stride_bytes=None,
+                         blocks_image_stride_bytes=None, out=None, stream=None):
+    """icamd_measure_error_device: the error of `blocks` (torch.uint8 CUDA tensor, laid out as encode_device writes them for
+    the grid) against the pixels `src` (as encode_device reads them), per image and channel.  Returns ([n, 4] int64 sums of
+    squared differences, [n, 4] int32 largest absolute differences) as device tensors, or None where the call answers false.
+    `out`: a caller-owned [n_images, 48] uint8 device tensor for the raw records (e.g. under graph capture).  No
+    synchronisation; the records are overwritten by stream-ordered work of the call."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    gh = height if grid_height is None else grid_height
+    gw = width if grid_width is None else grid_width
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    blk_stride = encoded_size(codec, max(gh, height), max(gw, width)) if blocks_image_stride_bytes is None \
+        else blocks_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, ERROR_STATS_BYTES), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, ERROR_STATS_BYTES, "measure_error_device")
+    st = lib().icamd_measure_error_device(codec, src_components, int(swap_rb), height, width, gh, gw, stride, n_images,
+                                          img_stride, blk_stride, ctypes.c_void_p(src.data_ptr()),
+                                          ctypes.c_void_p(blocks.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                          _stream_handle(stream))
+    if not _check(st, "icamd_measure_error_device"):
+        return None
+    return _split_stats(out)
+
+
+def measure_error_host(compressor, fmt, buffer, blocks, height, width, *, padding_bytes_per_row=0):
+    """icamd_measure_error (host buffers): (sse, max_abs) as two numpy arrays of 4, or None where the call answers false."""
+    import numpy as np
+    src = np.ascontiguousarray(np.frombuffer(buffer, dtype=np.uint8) if not isinstance(buffer, np.ndarray) else buffer)
+    b = np.frombuffer(bytes(blocks), np.uint8)
+    rec = np.zeros(ERROR_STATS_BYTES, np.uint8)
+    st = lib().icamd_measure_error(compressor, fmt, height, width, padding_bytes_per_row, src.ctypes.data, b.ctypes.data,
+                                   b.size, rec.ctypes.data)
+    if not _check(st, "icamd_measure_error"):
+        return None
+    return rec[:32].view(np.uint64).astype(np.int64), rec[32:].view(np.uint32).astype(np.int64)
+
+
+def psnr_from_stats(sse, n_pixels, n_channels):
+    """10 log10(255^2 N C / SSE) for the summed squared error of N pixels x C channels; inf for a perfect match."""
+    import math
+    total = float(sse.sum()) if hasattr(sse, "sum") else float(sum(sse))
+    return math.inf if total == 0 else 10.0 * math.log10(255.0 ** 2 * n_pixels * n_channels / total)

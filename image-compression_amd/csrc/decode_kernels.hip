@@ -5,6 +5,7 @@
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
+#include "pvrtc_decode_tile.h"
 
 namespace icamd {
 
@@ -117,61 +118,16 @@ __device__ __forceinline__ void pvrtc_decode_generic(const DecodeParams &P) {
     }
   }
 }
-// The same for block grids of at least 32 x 8: one workgroup per TILE of 32 x 8 blocks.  Every lane expands its own block's
-// colour word once (the packed-field -> channel-pair expansion is a quarter of the per-block work when each lane does it for all
-// nine neighbours), the 84 blocks of the one-block ring around the tile are expanded by the first 84 lanes, the pairs (16 B per
-// block) meet in LDS, one barrier.  The modulation / mode words of the four orthogonal neighbours (2 bpp only: its unstored
-// pixels look at them) still come from memory (L1 hits).
-constexpr uint32_t kPvrtcTileW = 32, kPvrtcTileH = 8;
+// The same for block grids of at least 32 x 8: one workgroup per TILE of 32 x 8 blocks (pvrtc_decode_tile.h gathers the lane's
+// neighbourhood through LDS); the decoded pixel rows are stored from here.
 template <int BPP>
 __device__ __forceinline__ void pvrtc_decode_tile(const DecodeParams &P, U4 *pairs, U4 (*turn)[128]) {
-  const uint32_t log2_cols = 31u - (uint32_t)__builtin_clz(P.block_cols), log2_rows = 31u - (uint32_t)__builtin_clz(P.block_rows);
-  const uint32_t tiles_x = P.block_cols >> 5, log2_tx = log2_cols - 5u, log2_tiles = log2_tx + log2_rows - 3u;
-  const uint32_t img = blockIdx.x >> log2_tiles, tile = blockIdx.x & ((1u << log2_tiles) - 1u);
-  const uint32_t bx0 = (tile & (tiles_x - 1u)) << 5, by0 = (tile >> log2_tx) << 3;
-  const uint32_t cmask = P.block_cols - 1u, rmask = P.block_rows - 1u;
-  const U2 *blocks = reinterpret_cast<const U2 *>(P.blocks + (size_t)img * P.src_image_stride);
-  const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
-  const uint32_t bx = bx0 + lx, by = by0 + ly;
-  auto word_at = [&](uint32_t x, uint32_t y) { return blocks[spread_bits16(x & cmask) << 1 | spread_bits16(y & rmask)]; };
-  // the four orthogonal neighbours step in the Z-order domain itself: x lives on the odd bits, y on the even ones; filling
-  // the other coordinate's bits with ones lets a carry run across them, zeros let a borrow, and the spread grid mask wraps
-  const uint32_t mx = spread_bits16(cmask) << 1, my = spread_bits16(rmask);
-  auto publish = [&](uint32_t cell, uint32_t colour_word) {
-    uint32_t e[4];
-    pvrtc_expand_colors(colour_word, e);
-    const U4 v = { e[0], e[1], e[2], e[3] };
-    pairs[cell] = v;
-  };
-  const uint32_t sx = spread_bits16(bx) << 1, sy = spread_bits16(by);
-  const U2 own = blocks[sx | sy];
-  publish((ly + 1u) * (kPvrtcTileW + 2u) + lx + 1u, own.y);
-  if (threadIdx.x < 2u * (kPvrtcTileW + 2u) + 2u * kPvrtcTileH) {  // the ring: top row, bottom row, left column, right column
-    const uint32_t t = threadIdx.x;
-    uint32_t cx, cy;  // cell coordinates in the (W + 2) x (H + 2) array
-    if (t < kPvrtcTileW + 2u) { cx = t; cy = 0u; }
-    else if (t < 2u * (kPvrtcTileW + 2u)) { cx = t - (kPvrtcTileW + 2u); cy = kPvrtcTileH + 1u; }
-    else if (t < 2u * (kPvrtcTileW + 2u) + kPvrtcTileH) { cx = 0u; cy = t - 2u * (kPvrtcTileW + 2u) + 1u; }
-    else { cx = kPvrtcTileW + 1u; cy = t - 2u * (kPvrtcTileW + 2u) - kPvrtcTileH + 1u; }
-    publish(cy * (kPvrtcTileW + 2u) + cx, word_at(bx0 + cx - 1u, by0 + cy - 1u).y);
-  }
-  uint32_t mod[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, col[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  mod[4] = own.x; col[4] = own.y;
-  if (BPP == 2) {
-    { const U2 w = blocks[sx | ((sy - 1u) & my)]; mod[1] = w.x; col[1] = w.y; }
-    { const U2 w = blocks[((sx - 2u) & mx) | sy]; mod[3] = w.x; col[3] = w.y; }
-    { const U2 w = blocks[(((sx | 0x55555555u) + 2u) & mx) | sy]; mod[5] = w.x; col[5] = w.y; }
-    { const U2 w = blocks[sx | (((sy | 0xaaaaaaaau) + 1u) & my)]; mod[7] = w.x; col[7] = w.y; }
-  }
-  __syncthreads();
-  uint32_t C[3][3][4];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const U4 v = pairs[(ly + (uint32_t)r) * (kPvrtcTileW + 2u) + lx + (uint32_t)c];
-      C[r][c][0] = v.x; C[r][c][1] = v.y; C[r][c][2] = v.z; C[r][c][3] = v.w;
-    }
+  PvrtcTileLane L;
+  pvrtc_tile_neighbourhood<BPP>(P.blocks, P.src_image_stride, P.block_cols, P.block_rows, pairs, L);
+  const uint32_t img = L.img, bx0 = L.bx0, by0 = L.by0, bx = L.bx, by = L.by;
+  const U2 own = L.own;
+  const uint32_t (&mod)[9] = L.mod, (&col)[9] = L.col;
+  const uint32_t (&C)[3][3][4] = L.C;
   const size_t row_stride = P.row_stride;
   if (BPP == 4) {
     // a lane's 16 bytes of a pixel row are one store: lanes 0-31 / 32-63 of a wave write 512 contiguous bytes (whole lines) of
@@ -209,12 +165,12 @@ extern "C" {
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pvrtc2_decode_kernel(DecodeParams P) { pvrtc_decode_generic<2>(P); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pvrtc4_decode_kernel(DecodeParams P) { pvrtc_decode_generic<4>(P); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pvrtc2_decode_tile_kernel(DecodeParams P) {
-  __shared__ U4 pairs[(kPvrtcTileH + 2) * (kPvrtcTileW + 2)];
+  __shared__ U4 pairs[kPvrtcTilePairs];
   __shared__ U4 turn[kThreadsPerWorkgroup / 64][128];
   pvrtc_decode_tile<2>(P, pairs, turn);
 }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pvrtc4_decode_tile_kernel(DecodeParams P) {
-  __shared__ U4 pairs[(kPvrtcTileH + 2) * (kPvrtcTileW + 2)];
+  __shared__ U4 pairs[kPvrtcTilePairs];
   pvrtc_decode_tile<4>(P, pairs, nullptr);
 }
 }  // extern "C"

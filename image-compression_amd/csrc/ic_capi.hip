@@ -860,6 +860,129 @@ int icamd_pvrtc2_decompress(uint32_t size, const uint8_t *blocks, size_t blocks_
                         });
 } ICAMD_ABI_CATCH
 
+// ---- quality metric (extension, include/ic_amd.h): blocks against source pixels
+
+// One launch: fewer than 2^31 blocks over the images' own block grids (height x width is the part of the image this launch
+// covers; grid_cols the pitch of a block row of the stored grid).
+static int metric_launch(int codec, int comps, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_cols,
+                         uint32_t row_stride, uint32_t n_images, size_t src_image_stride, size_t blocks_image_stride,
+                         const uint8_t *src, const uint8_t *blocks, uint8_t *stats, hipStream_t stream) {
+  icamd::MetricParams P;
+  P.src = src;
+  P.blocks = blocks;
+  P.stats = stats;
+  P.src_image_stride = src_image_stride;
+  P.blocks_image_stride = blocks_image_stride;
+  P.height = height;
+  P.width = width;
+  P.block_rows = num_blocks4(height);
+  P.block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width);  // PVRTC 2 bpp: 8x4-pixel blocks
+  P.grid_cols = grid_cols;
+  P.row_stride = row_stride;
+  P.blocks_per_image = P.block_rows * P.block_cols;
+  P.total_blocks = P.blocks_per_image * n_images;
+  P.swap_rb = swap_rb ? 1u : 0u;
+  P.force_gather = (uint64_t)row_stride * 3u + 8192u >= (1ull << 32) ? 1u : 0u;  // as launch_tiled
+  P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
+  P.div_cols = icamd::make_fastdiv(P.block_cols);
+  ICAMD_HIP(icamd::launch_metric(codec, comps, P, stream), "launch metric");
+  return ICAMD_OK;
+}
+
+int icamd_measure_error_device(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width,
+                               uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                               size_t src_image_stride_bytes, size_t blocks_image_stride_bytes, const void *d_src,
+                               const void *d_blocks, void *d_stats, void *hip_stream) try {
+  if (!d_src || !d_blocks || !d_stats || height == 0 || width == 0) return ICAMD_FALSE;
+  const bool pvrtc = codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4;
+  if (!pvrtc && !codec_accepts_components(codec, 4)) return fail(ICAMD_ERR_ARG, "unknown codec");  // (every codec takes 4)
+  if (pvrtc ? src_components != 4 : !codec_accepts_components(codec, src_components))
+    return fail(ICAMD_ERR_ARG, "the codec does not encode from that many source components");
+  if (swap_rb && src_components < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (grid_height < height || grid_width < width) return fail(ICAMD_ERR_ARG, "block grid smaller than the image");
+  if (reinterpret_cast<uintptr_t>(d_stats) % 8u) return fail(ICAMD_ERR_ARG, "d_stats must be 8-byte aligned");
+  if ((uint64_t)height * width > (1ull << 47)) return fail(ICAMD_ERR_ARG, "more than 2^47 pixels in one image");
+  const uint64_t kMaxBlocks = (1ull << 31) - 1;
+  const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
+  if (pvrtc) {  // what the PVRTC decoders need (icamd_decode_device), and the encoder's row rule
+    if (!is_pow2(width) || width != height || width < 8 || grid_height != height || grid_width != width ||
+        row_stride_bytes != width * 4u)
+      return ICAMD_FALSE;
+    if (bpi > kMaxBlocks) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
+    swap_rb = 0;
+  }
+  if (n_images == 0) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
+  uint8_t *stats = static_cast<uint8_t *>(d_stats);
+  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
+  const uint32_t grid_cols = num_blocks4(grid_width), block_bytes = icamd::codec_block_bytes(codec);
+  if (bpi <= kMaxBlocks) {  // whole images, as many per launch as the 32-bit block index allows
+    const uint64_t per_launch = std::max<uint64_t>(1, kMaxBlocks / bpi);
+    for (uint64_t first = 0; first < n_images; first += per_launch) {
+      const uint32_t count = (uint32_t)std::min<uint64_t>(per_launch, n_images - first);
+      rc = metric_launch(codec, src_components, swap_rb, height, width, grid_cols, row_stride_bytes, count,
+                         src_image_stride_bytes, blocks_image_stride_bytes, src + first * src_image_stride_bytes,
+                         blocks + first * blocks_image_stride_bytes, stats + first * sizeof(icamd_error_stats), stream);
+      if (rc != ICAMD_OK) return rc;
+    }
+    return ICAMD_OK;
+  }
+  // a single image of 2^31 blocks or more: bands of block rows, all adding to the image's one record
+  const uint32_t band = (uint32_t)(kMaxBlocks / block_cols);
+  for (uint32_t i = 0; i < n_images; ++i)
+    for (uint64_t r0 = 0; r0 < num_blocks4(height); r0 += band) {
+      const uint32_t rows = (uint32_t)std::min<uint64_t>((uint64_t)band * 4u, (uint64_t)height - r0 * 4u);
+      rc = metric_launch(codec, src_components, swap_rb, rows, width, grid_cols, row_stride_bytes, 1, 0, 0,
+                         src + i * src_image_stride_bytes + r0 * 4u * row_stride_bytes,
+                         blocks + i * blocks_image_stride_bytes + r0 * grid_cols * block_bytes,
+                         stats + (size_t)i * sizeof(icamd_error_stats), stream);
+      if (rc != ICAMD_OK) return rc;
+    }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+int icamd_measure_error(int compressor, int format, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
+                        const uint8_t *buffer, const uint8_t *blocks, size_t blocks_size, icamd_error_stats *out) try {
+  if (!buffer || !blocks || !out || height == 0 || width == 0) return ICAMD_FALSE;
+  int codec = ICAMD_PVRTC2, comps = 4;
+  bool swap = false;
+  if (compressor == ICAMD_COMPRESSOR_PVRTC) {  // pvrtc.cc:607-609, 636-667: kRGBA, no row padding
+    if (format != ICAMD_RGBA || !pvrtc_compress_ok(height, width, padding_bytes_per_row, blocks_size)) return ICAMD_FALSE;
+  } else {
+    if (!resolve_codec(compressor, format, &codec, &comps, &swap)) return ICAMD_FALSE;
+    if (blocks_size != icamd_encoded_size(codec, height, width)) return ICAMD_FALSE;
+  }
+  const size_t stride = (size_t)width * comps + padding_bytes_per_row;
+  if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
+  const size_t in_bytes = (size_t)(height - 1) * stride + (size_t)width * comps;  // as icamd_compress: no padding after the last row
+  const size_t blocks_at = (in_bytes + 15u) & ~(size_t)15u;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  Staging &st = tls_staging();
+  rc = st.ensure(blocks_at + blocks_size, sizeof(icamd_error_stats));
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t s = st.stream;
+  uint8_t *d_in = static_cast<uint8_t *>(st.d_in);
+  ICAMD_HIP(hipMemcpyAsync(d_in, buffer, in_bytes, hipMemcpyHostToDevice, s), "H2D copy");
+  ICAMD_HIP(hipMemcpyAsync(d_in + blocks_at, blocks, blocks_size, hipMemcpyHostToDevice, s), "H2D copy");
+  rc = icamd_measure_error_device(codec, comps, swap, height, width, height, width, (uint32_t)stride, 1, 0, 0, d_in,
+                                  d_in + blocks_at, st.d_out, s);
+  if (rc != ICAMD_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  ICAMD_HIP(hipMemcpyAsync(out, st.d_out, sizeof(icamd_error_stats), hipMemcpyDeviceToHost, s), "D2H copy");
+  ICAMD_HIP(hipStreamSynchronize(s), "stream synchronize");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_metric_kernel_name(int codec, int src_components) { return icamd::metric_kernel_name(codec, src_components); }
+
 // ---- compressed-domain operations
 
 int icamd_pad_batch_device(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, uint32_t n_images,

@@ -120,6 +120,23 @@ struct DecodeParams {
 };
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
 
+// Quality metric (metric_kernels.hip): n_images block grids against their source pixels, one launch of fewer than 2^31
+// blocks.  block_rows x block_cols are the blocks that cover the IMAGE (blocks of a padded grid beyond it are never visited);
+// grid_cols is the pitch of a block row in blocks (block codecs; PVRTC blocks sit in Z order and the grid is the image).
+// stats: n_images records of icamd_error_stats (include/ic_amd.h), zeroed before the launch; the kernels add to them.
+struct MetricParams {
+  const uint8_t *src, *blocks;
+  uint8_t *stats;
+  uint64_t src_image_stride, blocks_image_stride;
+  uint32_t height, width, block_rows, block_cols, grid_cols, row_stride;
+  uint32_t blocks_per_image, total_blocks, swap_rb;
+  uint32_t force_gather;  // rows too long for 32-bit row offsets: every block gathers with 64-bit addresses
+  FastDiv div_bpi, div_cols;
+};
+hipError_t launch_metric(int codec, int comps, const MetricParams &P, hipStream_t stream);
+hipError_t launch_metric_clear(void *stats, uint64_t n_images, hipStream_t stream);  // zeroes n_images records (8-byte aligned)
+const char *metric_kernel_name(int codec, int comps);
+
 // BC4 / BC5 (extension, bc45_kernels.hip).  Encode: GridParams as for DXT, comps = 1..4 (BC4) / 2..4 (BC5).  Decode: n_images
 // block grids of block_rows x block_cols, R8 / RG8 rows of row_stride bytes; log2_tile_cols / tile_row0 are the launcher's.
 struct Bc45DecodeParams {

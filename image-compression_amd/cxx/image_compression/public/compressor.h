@@ -93,6 +93,11 @@ class Compressor {
 //                          Compress writes for level l's pixels (padding_bytes_per_row for level 0, 0 below); owned or
 //                          external storage as Compress.  false for PVRTC, a format Compress refuses, levels outside
 //                          1 .. floor(log2(max(height, width))) + 1     -> icamd_compress_mips
+//   MeasureErrorDevice     the error of the blocks Compress wrote for an image against that image's pixels, both device
+//                          resident: d_stats receives one icamd_error_stats record (include/ic_amd.h: per-channel sums of
+//                          squared differences and largest absolute differences; 48 bytes, 8-byte aligned), written by
+//                          stream-ordered work.  blocks_size must be ComputeCompressedDataSize(); false as Compress, and
+//                          for a misaligned d_stats                     -> icamd_measure_error_device
 #define ICAMD_DECLARE_DEVICE_EXTENSION()                                                                              \
   bool CompressDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,     \
                       const void *d_buffer, void *d_out, size_t out_size, void *hip_stream);                         \
@@ -103,6 +108,8 @@ class Compressor {
                            uint32 n_images, const void *d_buffer, size_t src_image_stride_bytes, void *d_out,        \
                            size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream);              \
   bool CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,     \
-                        const uint8 *buffer, uint32 levels, CompressedImage *images)
+                        const uint8 *buffer, uint32 levels, CompressedImage *images);                                \
+  bool MeasureErrorDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,   \
+                          const void *d_buffer, const void *d_blocks, size_t blocks_size, void *d_stats, void *hip_stream)
 
 #endif  // IMAGE_COMPRESSION_PUBLIC_COMPRESSOR_H_

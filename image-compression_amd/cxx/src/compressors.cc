@@ -365,6 +365,21 @@ bool DeviceBatch(int compressor, int etc_strategy, CompressedImage::Format forma
                                           src_image_stride_bytes, dst_image_stride_bytes, d_buffer, d_out, hip_stream),
                       "icamd_encode_device");
 }
+// One image's blocks against its pixels (icamd_measure_error_device); codec / components as DeviceBatch maps the format.
+bool MeasureDevice(int compressor, CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,
+                   const void *d_buffer, const void *d_blocks, size_t blocks_size, void *d_stats, void *hip_stream) {
+  if (!d_buffer || !d_blocks || !d_stats || height == 0 || width == 0) return false;
+  if (!icamd_supports_format(compressor, format) && compressor != ICAMD_COMPRESSOR_PVRTC) return false;
+  if (blocks_size != icamd_compute_compressed_data_size(compressor, format, height, width)) return false;
+  const int comps = compressor == ICAMD_COMPRESSOR_PVRTC ? 4 : (int)GetNumFormatComponents(format);
+  const int codec = compressor == ICAMD_COMPRESSOR_PVRTC ? ICAMD_PVRTC2
+                    : compressor == ICAMD_COMPRESSOR_ETC ? ICAMD_ETC1 : (comps == 3 ? ICAMD_DXT1 : ICAMD_DXT5);
+  const int swap = (format == CompressedImage::kBGR || format == CompressedImage::kBGRA) ? 1 : 0;
+  const uint32 stride = width * (uint32)comps + padding_bytes_per_row;
+  return ReportStatus(icamd_measure_error_device(codec, comps, swap, height, width, height, width, stride, 1, 0, 0, d_buffer,
+                                                 d_blocks, d_stats, hip_stream),
+                      "icamd_measure_error_device");
+}
 // Levels 0 .. levels-1 of the mip chain in one fused device pass (icamd_compress_mips), split into one CompressedImage per
 // level with the metadata Compress4x4 gives that level's pixels.
 bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImage::Format format, uint32 height, uint32 width,
@@ -413,6 +428,12 @@ bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImag
   bool CLASS::CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,      \
                                const uint8 *buffer, uint32 levels, CompressedImage *images) {                                  \
     return MipChain(COMPRESSOR, STRATEGY, NAME, format, height, width, padding_bytes_per_row, buffer, levels, images);       \
+  }                                                                                                                            \
+  bool CLASS::MeasureErrorDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,    \
+                                 const void *d_buffer, const void *d_blocks, size_t blocks_size, void *d_stats,                \
+                                 void *hip_stream) {                                                                           \
+    return MeasureDevice(COMPRESSOR, format, height, width, padding_bytes_per_row, d_buffer, d_blocks, blocks_size, d_stats,   \
+                         hip_stream);                                                                                          \
   }
 ICAMD_DEFINE_DEVICE_EXTENSION(DxtcCompressor, ICAMD_COMPRESSOR_DXTC, 0, "dxtc")
 ICAMD_DEFINE_DEVICE_EXTENSION(EtcCompressor, ICAMD_COMPRESSOR_ETC, compression_strategy_, "etc")

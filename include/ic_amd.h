@@ -403,6 +403,47 @@ int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t h
                         uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
                         size_t out_size);
 
+/* ---- quality metric (EXTENSION: the reference has no such function): the error of compressed blocks against source pixels ----
+ * For image i, let D be the pixels that icamd_decode_device(codec, swap_rb, ...) yields for the blocks at
+ * d_blocks + i * blocks_image_stride_bytes, laid out as icamd_encode_device writes them for that grid_height x grid_width
+ * (block codecs: row-major; PVRTC: Z order, grid equal to the image), and S the source pixels, addressed as
+ * icamd_encode_device addresses them (rows of row_stride_bytes, image i at d_src + i * src_image_stride_bytes).  Then, for
+ * every compared channel k,
+ *     stats[i].sse[k]     = sum over y < height, x < width of (S[y][x][k] - D[y][x][k])^2
+ *     stats[i].max_abs[k] = the largest |S[y][x][k] - D[y][x][k]| over the same pixels.
+ * Pixels of edge blocks outside the image do not count, nor do blocks of a padded grid wholly outside it (they are not read).
+ * The compared channels are the decoder's output channels; the others are 0 in both arrays:
+ *     DXT1, ETC1            bytes 0..2 of the source pixel   src_components 3 or 4 (alpha ignored, sse[3] = 0)
+ *     DXT5, PVRTC2, PVRTC4  bytes 0..3                        src_components 4
+ *     BC4                   k = 0 is R                        src_components 1..4  (R, G located by the rules at ICAMD_BC4:
+ *     BC5                   k = 0, 1 are R, G                 src_components 2..4   R = byte 0, or byte 2 with swap_rb)
+ * Everything is integer arithmetic: the result is exact and the same from run to run.  PSNR over N pixels and C channels is
+ * 10 log10(255^2 N C / sum of sse).
+ * Arguments: source rules as icamd_encode_device, codec by codec (swap_rb only with 3 or 4 components; PVRTC ignores it, as
+ * its encoder and decoder do); PVRTC needs what its decoders need -- a square power of two of at least 8, grid equal to the
+ * image, row_stride_bytes == width * 4 -- and answers ICAMD_FALSE otherwise.  Any pointers and strides are accepted for
+ * d_src and d_blocks; d_stats (n_images records) must be 8-byte aligned and is overwritten.  ICAMD_FALSE for null pointers or
+ * an empty image.  ICAMD_ERR_ARG for an unknown codec, a codec / component / swap combination the encoder refuses, a row
+ * stride smaller than a row, a grid smaller than the image, a misaligned d_stats, or (uint64)height * width > 2^47 (a
+ * squared byte difference is below 2^16, so every sum stays below 2^63).  All of these are answered before a device is
+ * needed; ICAMD_ERR_NO_DEVICE without a GPU (there is no CPU path).  No allocation and no synchronisation: the zeroing of
+ * d_stats is stream-ordered work of the call itself, so a captured graph can be replayed.  Geometries beyond one launch are
+ * chunked like the decoders'. */
+typedef struct { uint64_t sse[4]; uint32_t max_abs[4]; } icamd_error_stats;   /* 48 bytes */
+int icamd_measure_error_device(int codec, int src_components, int swap_rb,
+                               uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
+                               uint32_t row_stride_bytes, uint32_t n_images,
+                               size_t src_image_stride_bytes, size_t blocks_image_stride_bytes,
+                               const void *d_src, const void *d_blocks, void *d_stats, void *hip_stream);
+/* Host buffers, Compressor + format as icamd_decompress and its ICAMD_FALSE conventions (null pointers, an empty image, a
+ * format the compressor refuses, blocks_size != the image's compressed size): `buffer` is the image as icamd_compress reads
+ * it, `blocks` what icamd_compress wrote for it, *out one record.  ICAMD_COMPRESSOR_PVRTC (kRGBA, sizes as icamd_compress)
+ * is measured through the PVRTC 2 bpp decoder extension. */
+int icamd_measure_error(int compressor, int format, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
+                        const uint8_t *buffer, const uint8_t *blocks, size_t blocks_size, icamd_error_stats *out);
+/* Name of the __global__ kernel icamd_measure_error_device launches for a configuration ("" if it refuses it). */
+const char *icamd_metric_kernel_name(int codec, int src_components);
+
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
 const char *icamd_last_error(void);       /* thread-local message for the last negative status */

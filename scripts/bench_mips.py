@@ -9,7 +9,8 @@ Legs: every codec at 16 x 4096^2 RGBA8 (BC4 / BC5 read bytes 0 / 0-1 of the same
 Method as scripts/bench_bc45.py: untimed warm-up calls, device events around K back-to-back calls, repeated; the median and
 min / max of ms per call.  Algorithmic bytes = source read once + every level's blocks written once, against 8 TB/s.
 Parity: image 0 of (a) against (c) (every level), which the GPU tier pins to the oracle.  PSNR of (a)'s levels against the
-pixel pyramid, and of the compressed-domain chain (icamd_downsample_device per level, DXT1 / DXT5 / ETC1), reported only.
+pixel pyramid, and of the compressed-domain chain (icamd_downsample_device per level, DXT1 / DXT5 / ETC1), reported only; both
+come from the device metric (icamd_measure_error_device: no decoded image, no host reduction).
 
   python scripts/bench_mips.py [--k 10] [--reps 5] [--legs dxt1,dxt5,etc1,bc4,bc5,etc1_1024,dxt1_16384] [--no-psnr]
 One JSON line per leg; exit status 1 if any parity check fails."""
@@ -54,9 +55,11 @@ def time_calls(fn, k, reps, warmup):
     return out
 
 
-def psnr(a, b):
-    mse = float(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2))
-    return 99.0 if mse == 0 else 10 * math.log10(255.0 ** 2 / mse)
+def psnr(codec, pixels, blocks, lh, lw, ch):
+    """PSNR over the first `ch` channels of an lh x lw level: RGBA8 `pixels` against `blocks` (device tensors), 99 if equal."""
+    sse, _ = pkg.measure_error_device(codec, pixels, blocks, lh, lw, 4)
+    total = int(sse[0, :ch].sum().item())
+    return 99.0 if total == 0 else 10 * math.log10(255.0 ** 2 * lh * lw * ch / total)
 
 
 def main():
@@ -122,17 +125,12 @@ def main():
         rec["fused_over_level0"] = round(res["fused"][0] / res["level0"][0], 3)
         rec["unfused_over_fused"] = round(res["unfused"][0] / res["fused"][0], 3)
         if not a.no_psnr:
-            chain = out[0].cpu().numpy()
-            pyramid = [img0]
-            for l in range(1, levels):
-                pyramid.append(pyr[0, poffs[l - 1]:poffs[l]].cpu().numpy().reshape(*pkg.mip_level_shape(s, s, l), comps))
+            pyramid = [src[:img_bytes]] + [pyr[0, poffs[l - 1]:poffs[l]] for l in range(1, levels)]  # image 0, RGBA8 levels
             ch = 1 if codec == pkg.BC4 else 2 if codec == pkg.BC5 else 4 if codec == pkg.DXT5 else 3
             rec["psnr_fused"] = []
             for l in range(levels):
                 lh, lw = pkg.mip_level_shape(s, s, l)
-                blk = torch.from_numpy(chain[offs[l]:offs[l + 1]].copy()).to(dev)
-                dec = pkg.decode_device(codec, blk, lh, lw).cpu().numpy().reshape(lh, lw, -1)
-                rec["psnr_fused"].append(round(psnr(dec[..., :ch], pyramid[l][..., :ch]), 2))
+                rec["psnr_fused"].append(round(psnr(codec, pyramid[l], out[0, offs[l]:offs[l + 1]], lh, lw, ch), 2))
             if codec in (pkg.DXT1, pkg.DXT5, pkg.ETC1):
                 comp, fmt = (pkg.COMPRESSOR_ETC, pkg.RGB) if codec == pkg.ETC1 else (pkg.COMPRESSOR_DXTC, pkg.RGB if codec == pkg.DXT1 else pkg.RGBA)
                 c3 = 4 if codec == pkg.DXT5 else 3
@@ -145,8 +143,7 @@ def main():
                         cur = pkg.downsample_device(comp, fmt, cur.view(1, -1), *pkg.mip_level_shape(s, s, l - 1))
                         if cur is None:
                             break
-                    dec = pkg.decode_device(codec, cur.reshape(-1).contiguous(), lh, lw).cpu().numpy().reshape(lh, lw, -1)
-                    rec["psnr_compressed_domain"].append(round(psnr(dec[..., :ch], pyramid[l][..., :ch]), 2))
+                    rec["psnr_compressed_domain"].append(round(psnr(codec, pyramid[l], cur.reshape(-1).contiguous(), lh, lw, ch), 2))
         print(json.dumps(rec), flush=True)
         del src, out, ws, pyr, out_c
         torch.cuda.empty_cache()

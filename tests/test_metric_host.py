@@ -1,0 +1,232 @@
+"""CPU tier for the quality metric (include/ic_amd.h, icamd_measure_error_device).
+
+* The per-block accumulation of image-compression_amd/csrc/metric_block.h, compiled for the host
+  (tests/host_emul/metric_emul.cc, -DICAMD_HOST_EMULATION), equals the definition computed with the oracle's decoders
+  (tests/metric_oracle.py) exactly, on encoder output and on random block words.
+* The C ABI's argument rules, all answered before a device is needed.
+* The record's layout, the header as plain C, and the new kernels' build (no scratch)."""
+import ctypes
+import importlib
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import bc45_oracle as B
+import ic_testlib as T
+import metric_oracle as M
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+EMUL_DIR = os.path.join(HERE, "host_emul")
+CSRC = os.path.join(T.ROOT, "image-compression_amd", "csrc")
+pkg = importlib.import_module("image-compression_amd")
+
+OK, FALSE, ERR_NO_DEVICE, ERR_ARG = 0, 1, -1, -4
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("metric") / "libmetric_emul.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DICAMD_HOST_EMULATION", "-I" + CSRC, "-o", so,
+                           os.path.join(EMUL_DIR, "metric_emul.cc")])
+    L = ctypes.CDLL(so)
+    L.metric_emul_measure.restype = ctypes.c_int
+    L.metric_emul_measure.argtypes = [T.ci, T.ci, T.ci, T.ci, T.u32, T.u32, T.u32, T.u32, T.u32, T.vp, T.vp, T.vp, T.vp]
+    return L
+
+
+def emul_measure(L, codec, flat, blocks, h, w, comps, swap=0, gh=None, gw=None, stride=None, gather=0):
+    gh = h if gh is None else gh
+    gw = w if gw is None else gw
+    stride = w * comps if stride is None else stride
+    src = np.ascontiguousarray(flat, dtype=np.uint8).reshape(-1)
+    b = np.frombuffer(bytes(blocks), np.uint8).copy()
+    sse, mx = np.zeros(4, np.uint64), np.zeros(4, np.uint32)
+    assert L.metric_emul_measure(codec, comps, swap, gather, h, w, gh, gw, stride, src.ctypes.data, b.ctypes.data,
+                                 sse.ctypes.data, mx.ctypes.data)
+    return sse.astype(np.int64), mx.astype(np.int64)
+
+
+def encode(codec, src, h, w, comps, swap, gh=None, gw=None):
+    if codec in (M.BC4, M.BC5):
+        return B.oracle_encode(codec, src, h, w, comps, swap, gh=gh, gw=gw)
+    return T.oracle_encode(codec, src, h, w, comps, swap, strategy=T.HEURISTIC, gh=gh, gw=gw)
+
+
+def random_words(codec, gh, gw, seed):
+    if codec in (M.BC4, M.BC5):
+        return B.random_words(codec, gh, gw, seed)
+    return T.random_blocks(codec, gh, gw, seed)
+
+
+def same(got, want):
+    return (got[0] == want[0]).all() and (got[1] == want[1]).all()
+
+
+@pytest.mark.parametrize("gen", sorted(T.GENERATORS))
+def test_block_accumulation_equals_the_definition_on_every_shape_and_layout(emul, gen):
+    for i, (h, w, pad) in enumerate(B.SHAPES):
+        img = B.image(gen, h, w, 4, index=i)
+        for codec, comps, swap in M.BLOCK_LAYOUTS:
+            src = np.ascontiguousarray(img[..., :comps])
+            flat = T.with_row_padding(src, pad)
+            for blocks in (encode(codec, src, h, w, comps, swap), random_words(codec, h, w, 500 + i)):
+                want = M.measure(codec, src, blocks, h, w, comps, swap)
+                for gather in (0, 1):
+                    got = emul_measure(emul, codec, flat, blocks, h, w, comps, swap, stride=w * comps + pad, gather=gather)
+                    assert same(got, want), (gen, h, w, pad, codec, comps, swap, gather, got, want)
+
+
+@pytest.mark.parametrize("h,w,gh,gw", [(30, 30, 40, 48), (5, 3, 16, 16), (1, 1, 9, 13), (64, 61, 64, 64), (17, 33, 24, 48)])
+def test_block_accumulation_on_padded_grids(emul, h, w, gh, gw):
+    img = B.image("mixed", h, w, 4, index=h + w)
+    for codec, comps, swap in M.BLOCK_LAYOUTS:
+        src = np.ascontiguousarray(img[..., :comps])
+        for blocks in (encode(codec, src, h, w, comps, swap, gh=gh, gw=gw), random_words(codec, gh, gw, 900 + h)):
+            assert len(blocks) == M.grid_bytes(codec, gh, gw)
+            want = M.measure(codec, src, blocks, h, w, comps, swap, gh=gh, gw=gw)
+            got = emul_measure(emul, codec, src, blocks, h, w, comps, swap, gh=gh, gw=gw)
+            assert same(got, want), (h, w, gh, gw, codec, comps, swap, got, want)
+
+
+def test_largest_differences_reach_the_record(emul):
+    """0 against 255 in every compared channel: the squared differences at the top of their range, summed over an image."""
+    h, w = 64, 64
+    for codec, comps, swap in M.BLOCK_LAYOUTS:
+        src = np.zeros((h, w, comps), np.uint8)
+        white = np.full((h, w, comps), 255, np.uint8)
+        blocks = encode(codec, white, h, w, comps, swap)
+        want = M.measure(codec, src, blocks, h, w, comps, swap)
+        assert want[1].max() >= 247  # (ETC1 / 565 quantisation may stop a little short of 255)
+        assert same(emul_measure(emul, codec, src, blocks, h, w, comps, swap), want), (codec, comps, swap)
+
+
+# ---- the C ABI's argument rules (no device work: every check below returns before the GPU is touched)
+
+def call(codec, comps, swap, h, w, gh, gw, stride, n=1, src=16, blocks=16, stats=16):
+    vp = ctypes.c_void_p
+    return pkg.lib().icamd_measure_error_device(codec, comps, swap, h, w, gh, gw, stride, n, 0, 0, vp(src), vp(blocks),
+                                                vp(stats), None)
+
+
+def test_false_for_null_pointers_and_empty_images():
+    assert call(0, 4, 0, 8, 8, 8, 8, 32, src=None) == FALSE
+    assert call(0, 4, 0, 8, 8, 8, 8, 32, blocks=None) == FALSE
+    assert call(0, 4, 0, 8, 8, 8, 8, 32, stats=None) == FALSE
+    assert call(0, 4, 0, 0, 8, 8, 8, 32) == FALSE
+    assert call(0, 4, 0, 8, 0, 8, 8, 32) == FALSE
+    # PVRTC: what its decoders refuse (not a square power of two of at least 8, a grid other than the image, row padding)
+    for codec in (M.PVRTC2, M.PVRTC4):
+        assert call(codec, 4, 0, 8, 16, 8, 16, 64) == FALSE
+        assert call(codec, 4, 0, 4, 4, 4, 4, 16) == FALSE
+        assert call(codec, 4, 0, 24, 24, 24, 24, 96) == FALSE
+        assert call(codec, 4, 0, 16, 16, 32, 32, 64) == FALSE
+        assert call(codec, 4, 0, 16, 16, 16, 16, 68) == FALSE
+
+
+@pytest.mark.parametrize("codec,comps,swap", [
+    (-1, 4, 0), (7, 4, 0),                                     # unknown codecs
+    (0, 2, 0), (0, 5, 0), (2, 1, 0), (2, 0, 0),                # DXT1 / ETC1: 3 or 4
+    (1, 3, 0), (3, 3, 0), (4, 3, 0),                           # DXT5 / PVRTC: 4
+    (5, 0, 0), (5, 5, 0), (6, 1, 0), (6, 5, 0),                # BC4 1..4, BC5 2..4
+    (5, 1, 1), (5, 2, 1), (6, 2, 1)])                          # swap_rb only with 3 or 4 components
+def test_err_arg_for_what_the_encoder_refuses(codec, comps, swap):
+    assert call(codec, comps, swap, 8, 8, 8, 8, 8 * max(comps, 1)) == ERR_ARG
+
+
+def test_err_arg_for_geometry_and_alignment():
+    assert call(0, 4, 0, 8, 8, 4, 8, 32) == ERR_ARG          # grid lower than the image
+    assert call(0, 4, 0, 8, 8, 8, 7, 32) == ERR_ARG          # grid narrower than the image
+    assert call(0, 4, 0, 8, 8, 8, 8, 31) == ERR_ARG          # row stride smaller than a row
+    assert call(0, 4, 0, 8, 8, 8, 8, 32, stats=20) == ERR_ARG  # d_stats not 8-byte aligned
+    assert b"8-byte" in pkg.lib().icamd_last_error()
+    # more than 2^47 pixels: 2^24 x (2^23 + 1)
+    assert call(5, 1, 0, 1 << 24, (1 << 23) + 1, 1 << 24, (1 << 23) + 1, (1 << 23) + 1) == ERR_ARG
+    assert call(5, 1, 0, 1 << 24, 1 << 23, 1 << 24, 1 << 23, 1 << 23, n=0) == OK  # exactly 2^47 passes; no image, no work
+
+
+def test_valid_calls_need_a_device():
+    if pkg.lib().icamd_device_count() > 0:
+        pytest.skip("a GPU is present")
+    for codec, comps, swap in M.BLOCK_LAYOUTS:
+        assert call(codec, comps, swap, 61, 59, 64, 64, 59 * comps + 3) == ERR_NO_DEVICE, (codec, comps, swap)
+    for codec in (M.PVRTC2, M.PVRTC4):
+        assert call(codec, 4, 0, 64, 64, 64, 64, 256) == ERR_NO_DEVICE
+    assert b"no HIP device" in pkg.lib().icamd_last_error()
+    # the host-buffer form: the reference's `false` first, then the device
+    img = T.s_noise(8, 8, 3)
+    blocks = np.zeros(32, np.uint8)
+    rec = np.zeros(48, np.uint8)
+    host = pkg.lib().icamd_measure_error
+    assert host(T.DXTC, T.RGB, 8, 8, 0, img.ctypes.data, blocks.ctypes.data, 31, rec.ctypes.data) == FALSE
+    assert host(T.ETC, T.RGBA, 8, 8, 0, img.ctypes.data, blocks.ctypes.data, 32, rec.ctypes.data) == FALSE
+    assert host(T.DXTC, T.RGB, 8, 8, 0, None, blocks.ctypes.data, 32, rec.ctypes.data) == FALSE
+    assert host(T.PVRTC, T.RGBA, 8, 12, 0, img.ctypes.data, blocks.ctypes.data, 24, rec.ctypes.data) == FALSE
+    assert host(T.DXTC, T.RGB, 8, 8, 0, img.ctypes.data, blocks.ctypes.data, 32, rec.ctypes.data) == ERR_NO_DEVICE
+    with pytest.raises(pkg.BackendError):
+        pkg.measure_error_host(T.DXTC, T.RGB, img, blocks, 8, 8)
+
+
+def test_kernel_names():
+    assert pkg.metric_kernel_name(M.DXT1, 4) == "icamd_metric_dxt1_rgba8_kernel"
+    assert pkg.metric_kernel_name(M.PVRTC2, 4) == "icamd_metric_pvrtc2_tile_kernel"
+    assert pkg.metric_kernel_name(M.BC5, 1) == "" and pkg.metric_kernel_name(M.DXT5, 3) == ""
+
+
+def test_psnr_from_stats():
+    assert pkg.psnr_from_stats(np.zeros(4, np.int64), 64, 3) == float("inf")
+    assert abs(pkg.psnr_from_stats(np.array([255 * 255 * 64, 0, 0, 0]), 64, 1)) < 1e-12
+    assert abs(pkg.psnr_from_stats(np.array([30, 40, 30, 0]), 100, 3) - M.psnr([30, 40, 30, 0], 100, 3)) < 1e-12
+
+
+# ---- the record's layout and the header as plain C
+
+def test_struct_layout_and_plain_c_header(tmp_path):
+    src = tmp_path / "stats_c99.c"
+    src.write_text(r'''
+#include <stddef.h>
+#include <stdio.h>
+#include "ic_amd.h"
+int main(void) {
+  icamd_error_stats s;
+  int rc;
+  s.sse[3] = 1; s.max_abs[3] = 2;
+  /* a refused call needs no device */
+  rc = icamd_measure_error_device(ICAMD_DXT1, 4, 0, 0, 8, 8, 8, 32, 1, 0, 0, &s, &s, &s, NULL);
+  printf("%lu %lu %lu %d\n", (unsigned long)sizeof(icamd_error_stats), (unsigned long)offsetof(icamd_error_stats, sse),
+         (unsigned long)offsetof(icamd_error_stats, max_abs), rc);
+  return 0;
+}
+''')
+    exe = tmp_path / "stats_c99"
+    libdir = os.path.dirname(pkg.LIB_PATH)
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(T.ROOT, "include"),
+                           "-o", str(exe), str(src), "-L" + libdir, "-lic_amd", "-Wl,-rpath," + libdir,
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    assert subprocess.check_output([str(exe)]).split() == [b"48", b"0", b"32", b"1"]
+    assert pkg.ERROR_STATS_BYTES == 48
+
+
+# ---- build check: the new kernels keep everything in registers
+
+def test_metric_kernels_use_no_scratch(tmp_path):
+    if not shutil.which("hipcc"):
+        pytest.skip("hipcc not available")
+    out = os.path.join(str(tmp_path), "k.s")
+    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(T.ROOT, "include"),
+                           "-I" + CSRC, "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "metric_kernels.hip")],
+                          stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    metas = {}
+    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, re.S):
+        blk = m.group(0)
+        metas[re.search(r"\.name:\s+(\S+)", blk).group(1)] = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
+    names = [pkg.metric_kernel_name(c, n) for c, n, _ in M.BLOCK_LAYOUTS + M.PVRTC_LAYOUTS]
+    names += ["icamd_metric_pvrtc2_kernel", "icamd_metric_pvrtc4_kernel"]
+    for n in sorted(set(names)):
+        assert n in metas, n
+        assert metas[n] == 0, "%s uses %d bytes of scratch" % (n, metas[n])
+    assert not re.search(r"\bscratch_", text)
