@@ -48,9 +48,14 @@ EXPORTS = [
     "icamd_rccl_available", "icamd_rccl_get_unique_id", "icamd_rccl_comm_init", "icamd_rccl_comm_destroy", "icamd_gather_blocks_rccl",
     "icamd_mip_max_levels", "icamd_mip_chain_size", "icamd_mip_workspace_size", "icamd_encode_mips_device",
     "icamd_mip_pyramid_device", "icamd_compress_mips",
+    "icamd_encode_mips_filtered_device", "icamd_mip_pyramid_filtered_device", "icamd_compress_mips_filtered",
+    "icamd_mip_kernel_name",
     "icamd_measure_error_device", "icamd_measure_error", "icamd_metric_kernel_name",
 ]
 RCCL_UNIQUE_ID_BYTES = 128
+# mip filters (bits; include/ic_amd.h, "mip filters"): 0 is the box filter of the plain mip entry points
+MIP_FILTER_BOX, MIP_FILTER_SRGB, MIP_FILTER_ALPHA_WEIGHTED = 0, 1, 2
+MIP_PYRAMID = -1  # `codec` of mip_kernel_name for the pixel pyramid
 CONTAINER_DDS, CONTAINER_KTX, CONTAINER_PKM, CONTAINER_PVR = 0, 1, 2, 3
 
 _u32, _sz, _vp, _ci = ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
@@ -177,6 +182,16 @@ def lib():
             L.icamd_mip_pyramid_device.argtypes = [_ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
             L.icamd_compress_mips.restype = _ci
             L.icamd_compress_mips.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
+        if not LIB_OVERRIDDEN or hasattr(L, "icamd_encode_mips_filtered_device"):  # mip-filter entry points
+            L.icamd_encode_mips_filtered_device.restype = _ci
+            L.icamd_encode_mips_filtered_device.argtypes = [_ci, _ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp,
+                                                            _vp, _sz, _vp]
+            L.icamd_mip_pyramid_filtered_device.restype = _ci
+            L.icamd_mip_pyramid_filtered_device.argtypes = [_ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
+            L.icamd_compress_mips_filtered.restype = _ci
+            L.icamd_compress_mips_filtered.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
+            L.icamd_mip_kernel_name.restype = ctypes.c_char_p
+            L.icamd_mip_kernel_name.argtypes = [_ci, _ci, _ci]
         if not LIB_OVERRIDDEN or hasattr(L, "icamd_measure_error_device"):  # quality-metric entry points
             L.icamd_measure_error_device.restype = _ci
             L.icamd_measure_error_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp,
@@ -709,8 +724,9 @@ def mip_level_shape(height, width, level):
 
 def encode_mips_device(codec, src, height, width, src_components, *, levels=None, swap_rb=False,
                        etc_strategy=ETC_SMALLER_ERROR, n_images=1, row_stride_bytes=None, src_image_stride_bytes=None,
-                       dst_image_stride_bytes=None, out=None, workspace=None, stream=None):
-    """Fused mip-chain encode (icamd_encode_mips_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes).
+                       dst_image_stride_bytes=None, out=None, workspace=None, stream=None, mip_filter=0):
+    """Fused mip-chain encode (icamd_encode_mips_device; with mip_filter -- MIP_FILTER_SRGB | MIP_FILTER_ALPHA_WEIGHTED -- other
+    than 0, icamd_encode_mips_filtered_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes).
     Returns (flat, views): flat is [n_images, dst_image_stride] (device), views[l] = flat[:, offset[l]:offset[l + 1]], the
     blocks of level l.  The workspace is allocated here unless the caller passes one (a uint8 CUDA tensor of at least
     mip_workspace_size bytes).  No synchronisation."""
@@ -731,9 +747,12 @@ def encode_mips_device(codec, src, height, width, src_components, *, levels=None
         raise ValueError("encode_mips_device: workspace must be a contiguous uint8 CUDA tensor")
     ws_ptr = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
     ws_len = workspace.numel() if workspace is not None else 0
-    st = lib().icamd_encode_mips_device(codec, etc_strategy, src_components, int(swap_rb), height, width, stride, levels,
-                                        n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
-                                        ctypes.c_void_p(out.data_ptr()), ws_ptr, ws_len, _stream_handle(stream))
+    tail = (height, width, stride, levels, n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), ws_ptr, ws_len, _stream_handle(stream))
+    if mip_filter == 0:
+        st = lib().icamd_encode_mips_device(codec, etc_strategy, src_components, int(swap_rb), *tail)
+    else:
+        st = lib().icamd_encode_mips_filtered_device(codec, etc_strategy, src_components, int(swap_rb), mip_filter, *tail)
     if not _check(st, "icamd_encode_mips_device"):
         return None
     return out, [out[:, offs[l]:offs[l + 1]] for l in range(levels)]
@@ -751,9 +770,9 @@ def mip_pyramid_size(src_components, height, width, levels=None):
 
 
 def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_images=1, row_stride_bytes=None,
-                       src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, stream=None):
-    """The pixel pyramid alone (icamd_mip_pyramid_device).  Returns (flat, views): views[l - 1] is level l as a
-    [n_images, h_l, w_l, src_components] view, for l = 1 .. levels-1."""
+                       src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, stream=None, mip_filter=0):
+    """The pixel pyramid alone (icamd_mip_pyramid_device; icamd_mip_pyramid_filtered_device with mip_filter other than 0).
+    Returns (flat, views): views[l - 1] is level l as a [n_images, h_l, w_l, src_components] view, for l = 1 .. levels-1."""
     assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
     if levels is None:
         levels = mip_max_levels(height, width)
@@ -764,9 +783,12 @@ def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_ima
     if out is None:
         out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
     _check_out(out, n_images, per, "mip_pyramid_device")
-    st = lib().icamd_mip_pyramid_device(src_components, height, width, stride, levels, n_images, img_stride, per,
-                                        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                        _stream_handle(stream))
+    tail = (height, width, stride, levels, n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
+    if mip_filter == 0:
+        st = lib().icamd_mip_pyramid_device(src_components, *tail)
+    else:
+        st = lib().icamd_mip_pyramid_filtered_device(src_components, mip_filter, *tail)
     if not _check(st, "icamd_mip_pyramid_device"):
         return None
     views = []
@@ -777,9 +799,9 @@ def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_ima
 
 
 def compress_mips_host(compressor, fmt, buffer, height, width, *, levels=None, padding_bytes_per_row=0,
-                       etc_strategy=ETC_SMALLER_ERROR, out_size=None):
-    """Host-buffer mip chain (icamd_compress_mips): bytes of the whole chain, or None where the reference's conventions
-    return false."""
+                       etc_strategy=ETC_SMALLER_ERROR, out_size=None, mip_filter=0):
+    """Host-buffer mip chain (icamd_compress_mips; icamd_compress_mips_filtered with mip_filter other than 0): bytes of the
+    whole chain, or None where the reference's conventions return false."""
     import numpy as np
     if levels is None:
         levels = mip_max_levels(height, width)
@@ -789,11 +811,19 @@ def compress_mips_host(compressor, fmt, buffer, height, width, *, levels=None, p
                  (COMPRESSOR_DXTC, BGRA): DXT5, (COMPRESSOR_ETC, RGB): ETC1}.get((compressor, fmt))
         out_size = mip_chain_size(codec, height, width, levels)[0] if codec is not None else 0
     out = np.empty(max(out_size, 1), dtype=np.uint8)
-    st = lib().icamd_compress_mips(compressor, etc_strategy, fmt, height, width, padding_bytes_per_row, levels,
-                                   src.ctypes.data, out.ctypes.data, out_size)
+    tail = (height, width, padding_bytes_per_row, levels, src.ctypes.data, out.ctypes.data, out_size)
+    if mip_filter == 0:
+        st = lib().icamd_compress_mips(compressor, etc_strategy, fmt, *tail)
+    else:
+        st = lib().icamd_compress_mips_filtered(compressor, etc_strategy, fmt, mip_filter, *tail)
     if not _check(st, "icamd_compress_mips"):
         return None
     return out[:out_size].tobytes()
+
+
+def mip_kernel_name(codec, src_components, mip_filter=0):
+    """Name of the mip kernel a configuration launches ("" if refused); codec MIP_PYRAMID: the pixel pyramid's."""
+    return lib().icamd_mip_kernel_name(codec, src_components, mip_filter).decode()
 
 
 # ---- quality metric (icamd_measure_error_device): compressed blocks against their source pixels

@@ -469,6 +469,18 @@ int mip_check_components(int codec, int comps, int swap_rb) {
   if (swap_rb && comps < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
   return ICAMD_OK;
 }
+// The filter rules of the filtered mip entry points (ICAMD_MIP_FILTER_*; codec may be icamd::kMipPyramidMode): colour only.
+int mip_check_filter(int codec, int comps, int filter) {
+  if (filter < 0 || filter > (ICAMD_MIP_FILTER_SRGB | ICAMD_MIP_FILTER_ALPHA_WEIGHTED))
+    return fail(ICAMD_ERR_ARG, "mip filter must be a combination of ICAMD_MIP_FILTER_SRGB and ICAMD_MIP_FILTER_ALPHA_WEIGHTED");
+  if (filter == ICAMD_MIP_FILTER_BOX) return ICAMD_OK;
+  if (codec == ICAMD_BC4 || codec == ICAMD_BC5)
+    return fail(ICAMD_ERR_ARG, "BC4 / BC5 hold data channels: only ICAMD_MIP_FILTER_BOX applies");
+  if (comps != 3 && comps != 4) return fail(ICAMD_ERR_ARG, "mip filters other than the box need a 3- or 4-component source");
+  if ((filter & ICAMD_MIP_FILTER_ALPHA_WEIGHTED) && comps != 4)
+    return fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_ALPHA_WEIGHTED needs a 4-component source");
+  return ICAMD_OK;
+}
 // The geometry checks of the mip entry points: the level count, the row stride, and (n_images > 1) the image strides
 // against one image's source and output -- its encoded chain, or its pixel pyramid when codec is icamd::kMipPyramidMode.
 int mip_check_geometry(int codec, int comps, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
@@ -1494,15 +1506,18 @@ size_t icamd_mip_workspace_size(int codec, int src_components, uint32_t height, 
   return mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
 }
 
-int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, int swap_rb, uint32_t height, uint32_t width,
-                             uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
-                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
-                             size_t workspace_bytes, void *hip_stream) try {
+// icamd_encode_mips_device / icamd_encode_mips_filtered_device (the former is filter 0)
+static int encode_mips(int codec, int etc_strategy, int src_components, int swap_rb, int filter, uint32_t height, uint32_t width,
+                       uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                       size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
+                       size_t workspace_bytes, void *hip_stream) {
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
   int rc = mip_check_components(codec, src_components, swap_rb);
+  if (rc != ICAMD_OK) return rc;
+  rc = mip_check_filter(codec, src_components, filter);
   if (rc != ICAMD_OK) return rc;
   rc = mip_check_geometry(codec, src_components, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes,
                           dst_image_stride_bytes);
@@ -1524,8 +1539,8 @@ int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, in
     rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, height, width, row_stride_bytes, n_images,
                              src_image_stride_bytes, dst_image_stride_bytes, d_src, dst, hip_stream);
     if (rc == ICAMD_OK && levels > 1)
-      rc = icamd_mip_pyramid_device(src_components, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes, pyr,
-                                    d_src, ws, hip_stream);
+      rc = icamd_mip_pyramid_filtered_device(src_components, filter, height, width, row_stride_bytes, levels, n_images,
+                                             src_image_stride_bytes, pyr, d_src, ws, hip_stream);
     size_t poff = 0;
     for (uint32_t l = 1; l < levels && rc == ICAMD_OK; ++l) {
       const uint32_t lh = mip_dim(height, l), lw = mip_dim(width, l);
@@ -1561,17 +1576,36 @@ int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, in
       in_row_stride = mip_dim(width, p.l0 + 6u) * (uint32_t)src_components;
       ws += per * n_images;
     }
-    ICAMD_HIP(icamd::launch_mip_pass(codec, src_components, P, n_images, stream), "launch mip chain");
+    ICAMD_HIP(icamd::launch_mip_filter_pass(codec, src_components, filter, P, n_images, stream), "launch mip chain");
   }
   return ICAMD_OK;
+}
+
+int icamd_encode_mips_device(int codec, int etc_strategy, int src_components, int swap_rb, uint32_t height, uint32_t width,
+                             uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
+                             size_t workspace_bytes, void *hip_stream) try {
+  return encode_mips(codec, etc_strategy, src_components, swap_rb, ICAMD_MIP_FILTER_BOX, height, width, row_stride_bytes, levels,
+                     n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, d_workspace, workspace_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
-int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
-                             uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
-                             const void *d_src, void *d_dst, void *hip_stream) try {
+int icamd_encode_mips_filtered_device(int codec, int etc_strategy, int src_components, int swap_rb, int filter, uint32_t height,
+                                      uint32_t width, uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                                      size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,
+                                      void *d_dst, void *d_workspace, size_t workspace_bytes, void *hip_stream) try {
+  return encode_mips(codec, etc_strategy, src_components, swap_rb, filter, height, width, row_stride_bytes, levels, n_images,
+                     src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, d_workspace, workspace_bytes, hip_stream);
+} ICAMD_ABI_CATCH
+
+// icamd_mip_pyramid_device / icamd_mip_pyramid_filtered_device (the former is filter 0)
+static int mip_pyramid(int src_components, int filter, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                       uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,
+                       void *d_dst, void *hip_stream) {
   if (src_components < 1 || src_components > 4) return fail(ICAMD_ERR_ARG, "src_components must be 1 .. 4");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
-  int rc = mip_check_geometry(icamd::kMipPyramidMode, src_components, height, width, row_stride_bytes, levels, n_images,
+  int rc = mip_check_filter(icamd::kMipPyramidMode, src_components, filter);
+  if (rc != ICAMD_OK) return rc;
+  rc = mip_check_geometry(icamd::kMipPyramidMode, src_components, height, width, row_stride_bytes, levels, n_images,
                               src_image_stride_bytes, dst_image_stride_bytes);
   if (rc != ICAMD_OK) return rc;
   if (n_images == 0) return ICAMD_OK;
@@ -1594,20 +1628,44 @@ int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width
     P.pix_image_stride = dst_image_stride_bytes;
     for (uint32_t j = 1; j < p.n; ++j) P.pix_off[j] = poff[p.l0 + j];
     P.pix_mask = ((1u << p.n) - 1u) & ~1u;
-    ICAMD_HIP(icamd::launch_mip_pass(icamd::kMipPyramidMode, src_components, P, n_images, stream), "launch mip pyramid");
+    ICAMD_HIP(icamd::launch_mip_filter_pass(icamd::kMipPyramidMode, src_components, filter, P, n_images, stream), "launch mip pyramid");
   }
   return ICAMD_OK;
+}
+
+int icamd_mip_pyramid_device(int src_components, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                             uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, void *hip_stream) try {
+  return mip_pyramid(src_components, ICAMD_MIP_FILTER_BOX, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes,
+                     dst_image_stride_bytes, d_src, d_dst, hip_stream);
 } ICAMD_ABI_CATCH
 
-int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
-                        uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
-                        size_t out_size) try {
+int icamd_mip_pyramid_filtered_device(int src_components, int filter, uint32_t height, uint32_t width, uint32_t row_stride_bytes,
+                                      uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                                      size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *hip_stream) try {
+  return mip_pyramid(src_components, filter, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes,
+                     dst_image_stride_bytes, d_src, d_dst, hip_stream);
+} ICAMD_ABI_CATCH
+
+const char *icamd_mip_kernel_name(int codec, int src_components, int filter) {
+  if (filter < 0 || filter > 3) return "";
+  const bool pyramid = codec == ICAMD_MIP_PYRAMID || codec == ICAMD_ETC1;  // ETC1 chains: the pyramid kernel, then the ETC1 kernels
+  if (!pyramid && !mip_codec(codec)) return "";
+  if (codec == ICAMD_ETC1 && src_components != 3 && src_components != 4) return "";
+  return icamd::mip_kernel_name(pyramid ? icamd::kMipPyramidMode : codec, src_components, filter);
+}
+
+// icamd_compress_mips / icamd_compress_mips_filtered (the former is filter 0)
+static int compress_mips(int compressor, int etc_strategy, int format, int filter, uint32_t height, uint32_t width,
+                         uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out, size_t out_size) {
   if (compressor == ICAMD_COMPRESSOR_PVRTC)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!buffer || !out || height == 0 || width == 0) return ICAMD_FALSE;
   int codec = 0, comps = 0;
   bool swap = false;
   if (!resolve_codec(compressor, format, &codec, &comps, &swap)) return ICAMD_FALSE;  // dxtc.cc:735-750, etc.cc:747-758
+  const int frc = mip_check_filter(codec, comps, filter);
+  if (frc != ICAMD_OK) return frc;
   if (levels == 0 || levels > mip_max_levels(height, width))
     return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
   if (out_size != icamd_mip_chain_size(codec, height, width, levels, nullptr)) return ICAMD_FALSE;
@@ -1618,9 +1676,22 @@ int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t h
   const size_t ws = mip_workspace_bytes(codec, height, width, levels, comps, 1);
   return staged_blockop(tls_staging(), buffer, in_bytes, out, out_size, ws_off + ws, false, [&](void *din, void *dout, hipStream_t s) {
     uint8_t *d_out = static_cast<uint8_t *>(dout);
-    return icamd_encode_mips_device(codec, etc_strategy, comps, swap, height, width, (uint32_t)stride, levels, 1, 0, 0, din,
-                                    d_out, ws ? d_out + ws_off : nullptr, ws, s);
+    return encode_mips(codec, etc_strategy, comps, swap, filter, height, width, (uint32_t)stride, levels, 1, 0, 0, din, d_out,
+                       ws ? d_out + ws_off : nullptr, ws, s);
   });
+}
+
+int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,
+                        uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
+                        size_t out_size) try {
+  return compress_mips(compressor, etc_strategy, format, ICAMD_MIP_FILTER_BOX, height, width, padding_bytes_per_row, levels, buffer,
+                       out, out_size);
+} ICAMD_ABI_CATCH
+
+int icamd_compress_mips_filtered(int compressor, int etc_strategy, int format, int filter, uint32_t height, uint32_t width,
+                                 uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
+                                 size_t out_size) try {
+  return compress_mips(compressor, etc_strategy, format, filter, height, width, padding_bytes_per_row, levels, buffer, out, out_size);
 } ICAMD_ABI_CATCH
 
 #pragma GCC visibility pop

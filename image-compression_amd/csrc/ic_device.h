@@ -108,7 +108,8 @@ ICAMD_DEV uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
 ICAMD_DEV uint32_t bfe(uint32_t v, uint32_t off, uint32_t w) { return (v >> off) & ((1u << w) - 1u); }
 ICAMD_DEV uint32_t bit_mask(uint32_t v, uint32_t bit) { return (v >> bit) & 1u ? 0xffffffffu : 0u; }
 ICAMD_DEV int32_t imad24(int32_t a, int32_t b, int32_t c) { return a * b + c; }
-ICAMD_DEV uint32_t umad24(uint32_t a, uint32_t b, uint32_t c) { return a * b + c; }
+// (the low 24 bits of each operand, as v_mad_u32_u24 takes them: an operand out of range shows in the host tier too)
+ICAMD_DEV uint32_t umad24(uint32_t a, uint32_t b, uint32_t c) { return (a & 0xffffffu) * (b & 0xffffffu) + c; }
 ICAMD_DEV uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 ICAMD_DEV uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 ICAMD_DEV int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }

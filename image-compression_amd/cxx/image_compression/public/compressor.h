@@ -93,6 +93,10 @@ class Compressor {
 //                          Compress writes for level l's pixels (padding_bytes_per_row for level 0, 0 below); owned or
 //                          external storage as Compress.  false for PVRTC, a format Compress refuses, levels outside
 //                          1 .. floor(log2(max(height, width))) + 1     -> icamd_compress_mips
+//   CompressMipChainFiltered  the same with a mip filter (include/ic_amd.h, ICAMD_MIP_FILTER_*: 1 = average the light the
+//                          sRGB codes stand for, 2 = weight colour by alpha, 3 = both; 0 is CompressMipChain).  false also
+//                          for a filter outside 0 .. 3 and for the alpha-weighted filter with kRGB / kBGR
+//                                                                        -> icamd_compress_mips_filtered
 //   MeasureErrorDevice     the error of the blocks Compress wrote for an image against that image's pixels, both device
 //                          resident: d_stats receives one icamd_error_stats record (include/ic_amd.h: per-channel sums of
 //                          squared differences and largest absolute differences; 48 bytes, 8-byte aligned), written by
@@ -109,6 +113,9 @@ class Compressor {
                            size_t dst_image_stride_bytes, size_t out_size_per_image, void *hip_stream);              \
   bool CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,     \
                         const uint8 *buffer, uint32 levels, CompressedImage *images);                                \
+  bool CompressMipChainFiltered(CompressedImage::Format format, uint32 height, uint32 width,                         \
+                                uint32 padding_bytes_per_row, const uint8 *buffer, int filter, uint32 levels,        \
+                                CompressedImage *images);                                                            \
   bool MeasureErrorDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,   \
                           const void *d_buffer, const void *d_blocks, size_t blocks_size, void *d_stats, void *hip_stream)
 

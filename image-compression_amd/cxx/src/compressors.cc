@@ -383,7 +383,7 @@ bool MeasureDevice(int compressor, CompressedImage::Format format, uint32 height
 // Levels 0 .. levels-1 of the mip chain in one fused device pass (icamd_compress_mips), split into one CompressedImage per
 // level with the metadata Compress4x4 gives that level's pixels.
 bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImage::Format format, uint32 height, uint32 width,
-              uint32 padding_bytes_per_row, const uint8 *buffer, uint32 levels, CompressedImage *images) {
+              uint32 padding_bytes_per_row, const uint8 *buffer, int filter, uint32 levels, CompressedImage *images) {
   if (!buffer || !images || height == 0 || width == 0) return false;
   if (compressor == ICAMD_COMPRESSOR_PVRTC || !icamd_supports_format(compressor, format)) return false;
   if (levels == 0 || levels > icamd_mip_max_levels(height, width)) return false;
@@ -397,9 +397,12 @@ bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImag
     if (!PrepareImage(metadata, offsets[l + 1] - offsets[l], &images[l])) return false;
   }
   std::vector<uint8> chain(total);
-  if (!ReportStatus(icamd_compress_mips(compressor, etc_strategy, format, height, width, padding_bytes_per_row, levels, buffer,
-                                        chain.data(), total),
-                    "icamd_compress_mips"))
+  if (!(filter == 0 ? ReportStatus(icamd_compress_mips(compressor, etc_strategy, format, height, width, padding_bytes_per_row, levels,
+                                                       buffer, chain.data(), total),
+                                   "icamd_compress_mips")
+                    : ReportStatus(icamd_compress_mips_filtered(compressor, etc_strategy, format, filter, height, width,
+                                                                padding_bytes_per_row, levels, buffer, chain.data(), total),
+                                   "icamd_compress_mips_filtered")))
     return false;
   for (uint32 l = 0; l < levels; ++l)
     std::memcpy(images[l].GetMutableData(), chain.data() + offsets[l], offsets[l + 1] - offsets[l]);
@@ -427,7 +430,12 @@ bool MipChain(int compressor, int etc_strategy, const char *name, CompressedImag
   }                                                                                                                            \
   bool CLASS::CompressMipChain(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,      \
                                const uint8 *buffer, uint32 levels, CompressedImage *images) {                                  \
-    return MipChain(COMPRESSOR, STRATEGY, NAME, format, height, width, padding_bytes_per_row, buffer, levels, images);       \
+    return MipChain(COMPRESSOR, STRATEGY, NAME, format, height, width, padding_bytes_per_row, buffer, 0, levels, images);      \
+  }                                                                                                                            \
+  bool CLASS::CompressMipChainFiltered(CompressedImage::Format format, uint32 height, uint32 width,                            \
+                                       uint32 padding_bytes_per_row, const uint8 *buffer, int filter, uint32 levels,           \
+                                       CompressedImage *images) {                                                              \
+    return MipChain(COMPRESSOR, STRATEGY, NAME, format, height, width, padding_bytes_per_row, buffer, filter, levels, images); \
   }                                                                                                                            \
   bool CLASS::MeasureErrorDevice(CompressedImage::Format format, uint32 height, uint32 width, uint32 padding_bytes_per_row,    \
                                  const void *d_buffer, const void *d_blocks, size_t blocks_size, void *d_stats,                \

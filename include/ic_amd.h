@@ -403,6 +403,43 @@ int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t h
                         uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
                         size_t out_size);
 
+/* ---- mip filters (EXTENSION: opt-in; filter 0 is byte for byte the chain above) ----
+ * The geometry, the cascade (level l+1 from the 8-bit level l), the four source pixels p_0..p_3 (rows 2y and
+ * min(2y + 1, h_l - 1), columns alike), the per-level encode and the packing stay as above; only how P_{l+1} is made from
+ * P_l changes.  `filter` is a combination of the bits below.  Integer arithmetic only; the result is exact.
+ *   T[s] = floor(65535 * f(s / 255) + 0.5), f the sRGB transfer function (c / 12.92 for c <= 0.04045, else
+ *          ((c + 0.055) / 1.055)^2.4): csrc/srgb_table.inc, generated by scripts/gen_srgb_table.py; strictly increasing.
+ *   M[k] = (T[k-1] + T[k] + 1) >> 1 for k = 1..255;  inv(v) = the number of k with M[k] <= v (the nearest code; inv(T[s]) = s).
+ * For each colour byte k in {0, 1, 2} (all three alike, so swap_rb still commutes):
+ *   x_i = p_i[k] without ICAMD_MIP_FILTER_SRGB, T[p_i[k]] with it;   a_i = byte 3 of p_i;   A = a_0 + a_1 + a_2 + a_3
+ *   unweighted   v = (x_0 + x_1 + x_2 + x_3) >> 2 without SRGB (the rule above), (x_0 + x_1 + x_2 + x_3 + 2) >> 2 with it
+ *   weighted     (ICAMD_MIP_FILTER_ALPHA_WEIGHTED and A > 0)  v = (a_0 x_0 + a_1 x_1 + a_2 x_2 + a_3 x_3 + (A >> 1)) / A,
+ *                integer division (the numerator is below 2^27); with A == 0 the unweighted value of the same filter
+ *   output byte  v without SRGB, inv(v) with it.
+ * Byte 3 is the truncating (a_0 + a_1 + a_2 + a_3) >> 2 under every filter: the alpha half of a DXT5 chain does not depend
+ * on the filter.  A flat image stays flat under every filter, and a 0 / 255 checkerboard becomes 188 under SRGB (127 under
+ * BOX).  Codecs: DXT1, DXT5, ETC1 (any strategy) and the pixel pyramid; a filter other than 0 needs src_components 3 or 4,
+ * ALPHA_WEIGHTED 4.  ICAMD_ERR_ARG -- before a device is needed -- for BC4 / BC5 (data channels) with a filter other than 0,
+ * a filter outside 0..3 and those component counts; every other rule, status and the workspace size (which does not depend
+ * on the filter) as for the entry point without `_filtered`, which is the same call with filter 0. */
+enum { ICAMD_MIP_FILTER_BOX = 0, ICAMD_MIP_FILTER_SRGB = 1, ICAMD_MIP_FILTER_ALPHA_WEIGHTED = 2 };  /* bits; 3 = both */
+int icamd_encode_mips_filtered_device(int codec, int etc_strategy, int src_components, int swap_rb, int filter,
+                                      uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                                      uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                      const void *d_src, void *d_dst, void *d_workspace, size_t workspace_bytes,
+                                      void *hip_stream);
+int icamd_mip_pyramid_filtered_device(int src_components, int filter, uint32_t height, uint32_t width,
+                                      uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                                      size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,
+                                      void *d_dst, void *hip_stream);
+int icamd_compress_mips_filtered(int compressor, int etc_strategy, int format, int filter, uint32_t height, uint32_t width,
+                                 uint32_t padding_bytes_per_row, uint32_t levels, const uint8_t *buffer, uint8_t *out,
+                                 size_t out_size);
+/* Name of the __global__ mip kernel a configuration launches ("" if it is refused); codec ICAMD_MIP_PYRAMID asks for the
+ * pixel pyramid's, which is also what ETC1 chains launch before the ETC1 kernels. */
+enum { ICAMD_MIP_PYRAMID = -1 };
+const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
+
 /* ---- quality metric (EXTENSION: the reference has no such function): the error of compressed blocks against source pixels ----
  * For image i, let D be the pixels that icamd_decode_device(codec, swap_rb, ...) yields for the blocks at
  * d_blocks + i * blocks_image_stride_bytes, laid out as icamd_encode_device writes them for that grid_height x grid_width

@@ -12,7 +12,14 @@ Parity: image 0 of (a) against (c) (every level), which the GPU tier pins to the
 pixel pyramid, and of the compressed-domain chain (icamd_downsample_device per level, DXT1 / DXT5 / ETC1), reported only; both
 come from the device metric (icamd_measure_error_device: no decoded image, no host reduction).
 
-  python scripts/bench_mips.py [--k 10] [--reps 5] [--legs dxt1,dxt5,etc1,bc4,bc5,etc1_1024,dxt1_16384] [--no-psnr]
+--filter F (1 = sRGB, 2 = alpha-weighted, 3 = both; include/ic_amd.h "mip filters") times the filtered chain instead: legs dxt1,
+dxt5, etc1 and `pyramid` (icamd_mip_pyramid_filtered_device alone), with per leg
+  (a)  fused     the filtered chain through icamd_encode_mips_filtered_device (pyramid leg: the filtered pyramid)
+  (a0) box       the same call with the box filter, in the same session
+  (c)  unfused   level 0 through icamd_encode_device, the filtered pyramid, then icamd_encode_device per level (not for `pyramid`)
+and the ratios a / a0 and c / a.  Parity: image 0 of (a) against (c).
+
+  python scripts/bench_mips.py [--k 10] [--reps 5] [--legs dxt1,dxt5,etc1,bc4,bc5,etc1_1024,dxt1_16384] [--no-psnr] [--filter F]
 One JSON line per leg; exit status 1 if any parity check fails."""
 import argparse
 import json
@@ -62,6 +69,72 @@ def psnr(codec, pixels, blocks, lh, lw, ch):
     return 99.0 if total == 0 else 10 * math.log10(255.0 ** 2 * lh * lw * ch / total)
 
 
+def bench_filtered(a, dev):
+    """--filter: (a) / (a0) / (c) per leg, one JSON line each; True if every parity check held."""
+    lib = pkg.lib()
+    ok = True
+    legs = a.legs.split(",") if a.legs != ",".join(LEGS) else ["dxt1", "dxt5", "pyramid"]
+    for leg in legs:
+        codec, n, s = (None, 16, 4096) if leg == "pyramid" else LEGS[leg]
+        comps, f = 4, a.filter
+        levels = pkg.mip_max_levels(s, s)
+        img0 = T.s_mixed(s, s, comps, index=1).reshape(s, s, comps).copy()
+        rng = np.random.default_rng(1)
+        alpha = rng.integers(0, 256, (s, s), dtype=np.uint8)  # runs of 0, runs of 255 and noise: every branch of the weighting
+        band = (np.arange(s)[:, None] // 8 + np.arange(s)[None, :] // 8) % 3
+        alpha[band == 0] = 0
+        alpha[band == 1] = 255
+        img0[..., 3] = alpha
+        src = torch.from_numpy(img0.reshape(-1).copy()).to(dev).repeat(n)
+        pyr_per, poffs = pkg.mip_pyramid_size(comps, s, s, levels)
+        pyr = torch.empty((n, pyr_per), dtype=torch.uint8, device=dev)
+        st = pkg._stream_handle()
+        img_bytes = s * s * comps
+        rec = {"leg": leg, "filter": f, "n_images": n, "size": s, "levels": levels, "lib": pkg.LIB_PATH}
+        if codec is None:
+            variants = (("fused", lambda: pkg.mip_pyramid_device(src, s, s, comps, n_images=n, out=pyr, mip_filter=f)),
+                        ("box", lambda: pkg.mip_pyramid_device(src, s, s, comps, n_images=n, out=pyr)))
+            rec["kernel"] = pkg.mip_kernel_name(pkg.MIP_PYRAMID, comps, f)
+        else:
+            total, offs = pkg.mip_chain_size(codec, s, s)
+            out = torch.empty((n, total), dtype=torch.uint8, device=dev)
+            out_c = torch.empty((n, total), dtype=torch.uint8, device=dev)
+            ws = torch.empty((max(1, pkg.mip_workspace_size(codec, comps, s, s, levels, n)),), dtype=torch.uint8, device=dev)
+
+            def unfused():
+                lib.icamd_encode_device(codec, 2, comps, 0, s, s, s, s, s * comps, n, img_bytes, total, src.data_ptr(),
+                                        out_c.data_ptr(), st)
+                lib.icamd_mip_pyramid_filtered_device(comps, f, s, s, s * comps, levels, n, img_bytes, pyr_per, src.data_ptr(),
+                                                      pyr.data_ptr(), st)
+                for l in range(1, levels):
+                    lh, lw = pkg.mip_level_shape(s, s, l)
+                    lib.icamd_encode_device(codec, 2, comps, 0, lh, lw, lh, lw, lw * comps, n, pyr_per, total,
+                                            pyr.data_ptr() + poffs[l - 1], out_c.data_ptr() + offs[l], st)
+
+            variants = (("fused", lambda: pkg.encode_mips_device(codec, src, s, s, comps, n_images=n, out=out, workspace=ws, mip_filter=f)),
+                        ("box", lambda: pkg.encode_mips_device(codec, src, s, s, comps, n_images=n, out=out, workspace=ws)),
+                        ("unfused", unfused))
+            rec["kernel"] = pkg.mip_kernel_name(codec, comps, f)
+        res = {}
+        for name, fn in variants:
+            t = time_calls(fn, a.k, a.reps, a.warmup)
+            res[name] = statistics.median(t)
+            rec[name + "_ms"] = round(res[name], 4)
+            rec[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+        rec["fused_over_box"] = round(res["fused"] / res["box"], 3)
+        if codec is not None:
+            variants[0][1]()
+            unfused()
+            torch.cuda.synchronize()
+            rec["parity_fused_vs_unfused"] = bool(torch.equal(out[0], out_c[0]))
+            ok &= rec["parity_fused_vs_unfused"]
+            rec["unfused_over_fused"] = round(res["unfused"] / res["fused"], 3)
+        print(json.dumps(rec), flush=True)
+        del src, pyr
+        torch.cuda.empty_cache()
+    return ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, default=10)
@@ -69,9 +142,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--no-psnr", action="store_true")
+    ap.add_argument("--filter", type=int, default=0, choices=[0, 1, 2, 3])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if a.filter:
+        return 0 if bench_filtered(a, dev) else 1
     lib = pkg.lib()
     bad = False
     for leg in a.legs.split(","):
