@@ -1,8 +1,18 @@
-// pvrtc_kernels.hip -- PVRTC1 2bpp encoder for gfx950 (MI355X): two barrier-free kernels.
+// pvrtc_kernels.hip -- PVRTC1 encoders for gfx950 (MI355X): the kernels, and the code that launches them.
 //
 // The reference runs three whole-image passes (Morph -> Modulate -> Encode, pvrtc_compressor.cc:586-597)
-// through three heap images (A, B: 8 B per block; modulation: 1 B per pixel).  Here:
+// through three heap images (A, B: 8 B per block; modulation: 1 B per pixel).  Here a 2 bpp call takes one of three forms:
 //
+//   the pair              icamd_pvrtc2_morph_*_kernel then icamd_pvrtc2_encode_*_kernel, two barrier-free kernels with 8 B per block
+//                         of scratch between them (below);
+//   one pass              icamd_pvrtc2_onepass_kernel: morph and modulation in one walk down a strip of block rows, a workgroup
+//                         one block row wide, no scratch -- whole textures of 512^2 ... 4096^2;
+//   one pass, halo form   icamd_pvrtc2_onepass_halo_kernel: the same walk on a rectangle wider than a workgroup or smaller than the
+//                         texture (8192^2 and more, regions), a prologue standing in for the neighbours the wrap no longer reaches.
+//
+// PVRTC1 4 bpp (an extension, parity unpinned) has a pair and a one-pass kernel of its own further down.  WHICH form a call gets,
+// with which grid, LDS size, strip height and rectangle, is decided in pvrtc_plan.h (host-only, pinned on the CPU); the launch code
+// at the end of this file reads the tune mode, asks the plan, acquires the workspace for a pair, and launches.  The pair's kernels:
 //   icamd_pvrtc2_morph_kernel   one 8x4 block per lane, raster order (a wave reads 64 x 32 B = 2 KiB contiguous
 //                               per pixel row): GetExtremesFast + ApplyColorChannelReduction -> the block's two
 //                               reduced colours, 8 B per block, into a workspace (0.25 B/px).           (Morph)
@@ -23,7 +33,7 @@
 // fifth "ring" wave per workgroup it was latency/occupancy-bound (SQ_WAIT_ANY 50 %).  Recomputing 12 halo values
 // per lane (+37 % modulation work) removes every dependency between lanes.
 // Launch order is morph(all images of a group) then encode(same group), groups as large as the workspace allows
-// (see launch_pvrtc2); toroidal wrap (pvrtc.cc:216-227,416-423) is applied to block / pixel coordinates.
+// (pvrtc_plan.h); toroidal wrap (pvrtc.cc:216-227,416-423) is applied to block / pixel coordinates.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -33,14 +43,11 @@
 #include "ic_launch.h"
 #include "ic_amd.h"
 #include "pvrtc_block.h"
+#include "pvrtc_plan.h"
 
 namespace icamd {
 
 namespace {
-
-constexpr int kMorphLanes = 256;
-constexpr int kEncodeLanes = 256;
-constexpr uint32_t kFullChipLanes = 256u * 4u * 64u * 2u;  // two waves on each of the 1 024 SIMDs
 
 __device__ __forceinline__ void load_block32(const uint32_t *p, uint32_t n, uint32_t px[32]) {
 #pragma unroll
@@ -157,15 +164,6 @@ struct TlsWorkspace {
 };
 thread_local TlsWorkspace g_tls_workspace;
 
-// images of one launch pair: as many as 4 GiB of pixels (and the 32-bit block index) allow
-uint64_t pvrtc_group(uint32_t size, uint32_t n_images) {
-  const uint64_t image_bytes = (uint64_t)size * size * 4u;
-  uint64_t group = image_bytes ? (4096ull << 20) / image_bytes : 1;
-  if (group < 1) group = 1;
-  if (group > n_images) group = n_images;
-  return group;
-}
-
 }  // namespace
 
 struct PvrtcLaunch {
@@ -190,7 +188,7 @@ struct PvrtcLaunch {
 // Morph: kMorphBlocksPerLane blocks per lane, software-pipelined with two pixel buffers -- the loads of the next
 // block are in flight while the current one is reduced, so a wave always has 8 KiB outstanding and the HBM stream
 // does not drain during its ~700-instruction compute phases (5 waves/SIMD: the 32 KiB stash caps the occupancy).
-constexpr int kMorphBlocksPerLane = 4;
+// (kMorphBlocksPerLane = 4 and the lanes per workgroup: pvrtc_plan.h, which sizes the grids by them)
 
 // LDS of a morph workgroup: the per-lane pixel stash for index lookups, 8 planes x 256 lanes x 16 B = 32 KiB
 constexpr uint32_t kLdsDwords = 8 * kMorphLanes * 4;
@@ -546,10 +544,8 @@ extern "C" __global__ void __launch_bounds__(kEncodeLanes) icamd_pvrtc2_encode_n
 // which is what the ~200 VGPRs of the fused walk allow anyway.  Everything that touches LDS or memory inside the walk is
 // inline asm or a DMA builtin: hipcc drains the ring (vmcnt(0)) in front of any LDS access it can see.
 typedef uint32_t icamd_u32x4 __attribute__((ext_vector_type(4)));
-constexpr uint32_t kOnePassRing = 8;
-constexpr uint32_t kOnePassChunkSlots = 18;                                  // 4 x 4 blocks in Z order + 2 (16-byte aligned stride)
-constexpr uint32_t kOnePassWaveDwords = kOnePassRing * 512u + 16u * kOnePassChunkSlots * 2u;  // ring + tile: 18 688 bytes
-constexpr uint32_t kOnePassXchDwords = 8;                                    // per wave and parity: [lo.a lo.b col0 - | hi.a hi.b - -]
+// (kOnePassRing, kOnePassChunkSlots, kOnePassWaveDwords, kOnePassXchDwords and their 4 bpp twins: pvrtc_plan.h, which sizes the
+// dynamic LDS by them)
 
 // lane i <- v of lane i - 1 (wave_shr:1); lane 0, which has no source lane, keeps `edge` (the DPP "old" operand: no select after it)
 __device__ __forceinline__ uint32_t dpp_from_lower_lane(uint32_t v, uint32_t edge) {
@@ -747,311 +743,8 @@ extern "C" __global__ void __launch_bounds__(512) icamd_pvrtc2_onepass_halo_kern
   pvrtc2_onepass_body<true>(L, lds_dyn);
 }
 
-// the kernel whole-texture launches of 512^2 ... 4096^2 take (launch_pvrtc2); smaller / larger / partial ones: morph + encode
+// the kernel whole-texture launches of 512^2 ... 4096^2 take (pvrtc_plan.h); smaller / larger / partial ones: the pair or the halo form
 const char *pvrtc2_kernel_name() { return "icamd_pvrtc2_onepass_kernel"; }
-
-namespace {
-// inverse of pvrtc_z_index on the host: x from the odd bits, y from the even bits
-uint32_t compact_even_bits_host(uint32_t v) {
-  v &= 0x55555555u;
-  v = (v | v >> 1) & 0x33333333u;
-  v = (v | v >> 2) & 0x0f0f0f0fu;
-  v = (v | v >> 4) & 0x00ff00ffu;
-  v = (v | v >> 8) & 0x0000ffffu;
-  return v;
-}
-}  // namespace
-
-// ---- path selection: one pass (whole textures of 512^2 ... 4096^2, enough of them to fill the chip) or morph + encode --------
-namespace {
-std::atomic<int> g_path_mode{-1};   // -1: not read yet; 0 auto, 1 always two kernels, 2 one pass wherever it is eligible
-std::atomic<int> g_path_strip{-2};  // -2: not read yet; -1 auto, else log2(blocks per strip) of the one-pass kernel
-// The environment is read ONCE, by whichever of the first launch and the first icamd_pvrtc2_tune comes first; a tune() then
-// stores over it, so a launch on another thread can no longer read the environment on top of a tune() call (ADVICE r05).
-std::once_flag g_path_env_once;
-void read_path_env() {
-  std::call_once(g_path_env_once, [] {
-    const char *m = getenv("ICAMD_PVRTC2_PATH"), *k = getenv("ICAMD_PVRTC2_STRIP");
-    int mode = 0;
-    if (m && !strcmp(m, "two")) mode = 1;
-    else if (m && !strcmp(m, "one")) mode = 2;
-    g_path_strip.store(k && *k ? atoi(k) : -1);
-    g_path_mode.store(mode);
-  });
-}
-// Strip height of the one-pass kernel for n_images size^2 textures, or -1 where the morph + encode pair is the better choice.
-// Time model, fitted on an MI355X (profiles/r05_ab_pvrtc_onepass.log, within 5 % of every measured shape from 1 x 512^2 to
-// 16 x 4096^2): a workgroup of K-block strips takes 11 + 5.8 K us whatever its width (its waves walk K + 2 block rows at two
-// waves per SIMD), a CU holds 8 / waves-per-workgroup of them, a launch takes ceil(workgroups / slots) such rounds; the pair
-// takes 10 us + 52.6 us per million blocks.  forced >= 0: that strip height; always: the best strip height, no comparison.
-int onepass_log2_strip(uint32_t log2_size, uint64_t n_images, int forced, bool always, uint32_t compute_units) {
-  const uint32_t log2_bw = log2_size - 3u, log2_bh = log2_size - 2u;
-  if (log2_bw < 6u || log2_bw > 9u) return -1;  // a workgroup is one block row wide: 64 ... 512 lanes
-  // (a forced strip may be as tall as the texture, log2(size / 4): one workgroup per texture -- tests and A/B runs use it)
-  if (forced >= 0) return forced < 2 ? 2 : (forced > (int)log2_bh ? (int)log2_bh : forced);
-  const uint64_t slots = (uint64_t)compute_units * (8u >> (log2_bw - 6u));
-  int best = -1;
-  double best_us = 0.0;
-  for (int sb = 2; sb <= 6 && sb <= (int)log2_bh; ++sb) {
-    const uint64_t wgs = n_images << (log2_bh - (uint32_t)sb);
-    const double us = (double)((wgs + slots - 1) / slots) * (11.0 + 5.8 * (double)(1u << sb));
-    if (best < 0 || us <= best_us) { best_us = us; best = sb; }
-  }
-  const double pair_us = 10.0 + 52.6e-6 * (double)(n_images << (log2_bw + log2_bh));
-  return always || best_us < 0.97 * pair_us ? best : -1;
-}
-hipError_t launch_pvrtc2_onepass(const PvrtcParams &P, int sb, hipStream_t stream) {
-  const uint32_t log2_bw = P.log2_size - 3u, bw = 1u << log2_bw, waves = bw >> 6;
-  const size_t lds_bytes = (size_t)waves * (kOnePassWaveDwords + 2u * kOnePassXchDwords) * 4u;
-  // more than 64 KiB of dynamic LDS has to be allowed per function and device, once
-  static std::atomic<uint64_t> allowed{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !((allowed.load() >> dev) & 1u)) {  // (ordinals past 63: every time)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(icamd_pvrtc2_onepass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(8u * (kOnePassWaveDwords + 2u * kOnePassXchDwords) * 4u));
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) allowed.fetch_or(1ull << dev);
-  }
-  PvrtcLaunch L;
-  L.src = P.src;
-  L.dst = P.dst;
-  L.ab = nullptr;
-  L.src_image_stride = P.src_image_stride;
-  L.dst_image_stride = P.dst_image_stride;
-  L.size = P.size;
-  L.log2_bw = log2_bw;
-  L.log2_bpi = 2 * P.log2_size - 5;
-  L.log2_strip = (uint32_t)sb;
-  L.rx0 = L.ry0 = L.z_first = 0;
-  L.log2_rw = log2_bw;
-  L.log2_rblocks = L.log2_bpi;
-  L.total_blocks = L.total_strips = 0;
-  // the tile's write-out issues 16-byte stores: only when every image's output is 16-byte aligned (the contract asks for 8)
-  L.stage_stores = (reinterpret_cast<uintptr_t>(P.dst) % 16u == 0 && (P.n_images == 1 || P.dst_image_stride % 16u == 0)) ? 1u : 0u;
-  const uint32_t strips_per_image = (P.size / 4u) >> sb;
-  // (launch_pvrtc2 has checked blocks per image x images < 2^31, so the grid fits)
-  hipLaunchKernelGGL(icamd_pvrtc2_onepass_kernel, dim3((uint32_t)(P.n_images * (uint64_t)strips_per_image)), dim3(bw), lds_bytes, stream, L);
-  return hipGetLastError();
-}
-
-// Halo form (r06): the rectangle (rx0, ry0, 2^log2_rw x 2^log2_rh blocks; a whole texture: 0, 0, bw, bh) of each image, workgroups
-// of min(2^log2_rw, 512) lanes, strips of 2^sb block rows.  One launch, no scratch memory.
-struct HaloRect {
-  uint32_t rx0, ry0, log2_rw, log2_rh, z_first;
-};
-constexpr uint32_t kOnePassHaloTableBytes = (64u + 4u) * 8u + (64u + 3u) * 16u + (64u + 3u) * 8u;  // strips of at most 64 blocks
-hipError_t launch_pvrtc2_onepass_halo(const PvrtcParams &P, const HaloRect &R, int sb, hipStream_t stream) {
-  const uint32_t log2_bw = P.log2_size - 3u;
-  const uint32_t log2_wgc = R.log2_rw < 9u ? R.log2_rw : 9u, lanes = 1u << log2_wgc, waves = lanes >> 6;
-  const uint32_t groups = 1u << (R.log2_rw - log2_wgc);
-  const size_t lds_bytes = (size_t)waves * (kOnePassWaveDwords + 2u * kOnePassXchDwords) * 4u + kOnePassHaloTableBytes;
-  static std::atomic<uint64_t> allowed{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !((allowed.load() >> dev) & 1u)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(icamd_pvrtc2_onepass_halo_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(8u * (kOnePassWaveDwords + 2u * kOnePassXchDwords) * 4u + kOnePassHaloTableBytes));
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) allowed.fetch_or(1ull << dev);
-  }
-  PvrtcLaunch L;
-  L.src = P.src;
-  L.dst = P.dst;
-  L.ab = nullptr;
-  L.src_image_stride = P.src_image_stride;
-  L.dst_image_stride = P.dst_image_stride;
-  L.size = P.size;
-  L.log2_bw = log2_bw;
-  L.log2_bpi = 2 * P.log2_size - 5;
-  L.log2_strip = (uint32_t)sb;
-  L.rx0 = R.rx0;
-  L.ry0 = R.ry0;
-  L.z_first = R.z_first;
-  L.log2_rw = R.log2_rw;
-  L.log2_rblocks = R.log2_rw + R.log2_rh;
-  L.total_blocks = L.total_strips = 0;
-  L.log2_wgc = log2_wgc;
-  L.stage_stores = (reinterpret_cast<uintptr_t>(P.dst) % 16u == 0 && (P.n_images == 1 || P.dst_image_stride % 16u == 0)) ? 1u : 0u;
-  (void)hipGetLastError();
-  const uint64_t wgs = (uint64_t)P.n_images * ((1ull << R.log2_rh) >> sb) * groups;
-  hipLaunchKernelGGL(icamd_pvrtc2_onepass_halo_kernel, dim3((uint32_t)wgs), dim3(lanes), lds_bytes, stream, L);
-  return hipGetLastError();
-}
-// Strip height of the halo form for a rectangle of 2^log2_rw x 2^log2_rh blocks per image, or -1 where the pair is the better
-// choice: the time model of onepass_log2_strip (a K-block strip workgroup: 11 + 5.8 K us whatever its width, 8 / waves of them per
-// CU) + 2 us for the prologue; the pair: 10 us + 52.6 us per million blocks.
-int onepass_halo_log2_strip(const HaloRect &R, uint64_t n_images, int forced, bool always, uint32_t compute_units) {
-  if (R.log2_rw < 6u || R.log2_rh < 2u) return -1;  // at least one wave wide and one 4-block strip tall
-  const uint32_t log2_wgc = R.log2_rw < 9u ? R.log2_rw : 9u;
-  const uint64_t groups = 1ull << (R.log2_rw - log2_wgc);
-  const int max_sb = R.log2_rh < 6u ? (int)R.log2_rh : 6;
-  if (forced >= 0) return forced < 2 ? 2 : (forced > max_sb ? max_sb : forced);
-  const uint64_t slots = (uint64_t)compute_units * (8u >> (log2_wgc - 6u));
-  int best = -1;
-  double best_us = 0.0;
-  for (int sb = 2; sb <= max_sb; ++sb) {
-    const uint64_t wgs = (n_images << (R.log2_rh - (uint32_t)sb)) * groups;
-    const double us = 2.0 + (double)((wgs + slots - 1) / slots) * (11.0 + 5.8 * (double)(1u << sb));
-    if (best < 0 || us <= best_us) { best_us = us; best = sb; }
-  }
-  const double pair_us = 10.0 + 52.6e-6 * (double)(n_images << (R.log2_rw + R.log2_rh));
-  return always || best_us < 0.97 * pair_us ? best : -1;
-}
-}  // namespace
-
-// One image, blocks [z_first, z_first + n_blocks) of its Z-order output (n_blocks a power of two, z_first a multiple
-// of it: a rectangle of the block grid).  Reads the region's pixels and a one-block ring around it only.
-static hipError_t launch_pvrtc2_region(const PvrtcParams &P, hipStream_t stream) {
-  const uint32_t log2_bw = P.log2_size - 3, log2_bpi = 2 * P.log2_size - 5;
-  uint32_t m = 0;
-  while ((1u << m) < P.region_blocks) ++m;
-  if ((1u << m) != P.region_blocks || m > log2_bpi || (P.region_first & (P.region_blocks - 1u)) != 0 ||
-      (uint64_t)P.region_first + P.region_blocks > (1ull << log2_bpi))
-    return hipErrorInvalidValue;
-  // r06: regions at least one wave wide and one 4-block strip tall take the one-pass kernel's halo form where the time model
-  // prefers it (one read of the pixels, one launch, no scratch) -- the multi-GPU split of ONE large texture (sharding.pvrtc_region)
-  // no longer pays the pair's second pass over the pixels; icamd_pvrtc2_tune(1, ...) keeps the pair for A/B runs and tests
-  read_path_env();
-  if (g_path_mode.load() != 1) {
-    const uint32_t lrw = m / 2;
-    const HaloRect R = { compact_even_bits_host(P.region_first >> 1), compact_even_bits_host(P.region_first), lrw, m - lrw, P.region_first };
-    const bool force = g_path_mode.load() == 2;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int hsb = onepass_halo_log2_strip(R, 1, force ? g_path_strip.load() : -1, force, device_compute_units(dev));
-    if (hsb >= 0) return launch_pvrtc2_onepass_halo(P, R, hsb, stream);
-  }
-  uint2 *ab = nullptr;
-  Workspace &ws = g_tls_workspace.get();
-  hipError_t e = ws.acquire(((size_t)sizeof(uint2)) << log2_bpi, stream, reinterpret_cast<void **>(&ab));
-  if (e != hipSuccess) return e;
-  (void)hipGetLastError();
-  PvrtcLaunch L;
-  L.src = P.src;
-  L.dst = P.dst;
-  L.ab = ab;
-  L.src_image_stride = L.dst_image_stride = 0;
-  L.size = P.size;
-  L.log2_bw = log2_bw;
-  L.log2_bpi = log2_bpi;
-  L.log2_rblocks = m;
-  L.log2_rw = m / 2;  // x owns the odd bits of the Z index: floor(m/2) of the low m bits
-  const uint32_t log2_rh = m - L.log2_rw;
-  L.rx0 = compact_even_bits_host(P.region_first >> 1);
-  L.ry0 = compact_even_bits_host(P.region_first);
-  L.z_first = P.region_first;
-  L.log2_strip = log2_rh < 3 ? log2_rh : 3;
-  while (L.log2_strip > 0 && (P.region_blocks >> L.log2_strip) < kFullChipLanes) --L.log2_strip;
-  // the staged write-out issues 16-byte stores: only when the region's output is 16-byte aligned (8 is the contract)
-  const bool dst16 = reinterpret_cast<uintptr_t>(P.dst) % 16u == 0;
-  L.stage_stores = (L.log2_strip >= 1 && L.log2_rw >= L.log2_strip && dst16) ? 1u : 0u;
-  L.total_blocks = 1u << log2_bpi;
-  L.total_strips = P.region_blocks >> L.log2_strip;
-  const uint32_t rw = 1u << L.log2_rw, rh = 1u << log2_rh;
-  const dim3 gm((rw + 2 + kMorphLanes - 1) / kMorphLanes, rh + 2), ge((L.total_strips + kEncodeLanes - 1) / kEncodeLanes);
-  hipLaunchKernelGGL(icamd_pvrtc2_morph_rect_kernel, gm, dim3(kMorphLanes), 0, stream, L);
-  hipLaunchKernelGGL(L.log2_rw >= 6 ? icamd_pvrtc2_encode_kernel : icamd_pvrtc2_encode_narrow_kernel, ge, dim3(kEncodeLanes),
-                     0, stream, L);
-  e = hipGetLastError();
-  const hipError_t e2 = ws.release(stream);
-  return e != hipSuccess ? e : e2;
-}
-
-void pvrtc2_tune(int mode, int log2_strip) {
-  read_path_env();
-  g_path_mode.store(mode < 0 || mode > 2 ? 0 : mode);
-  g_path_strip.store(log2_strip < 0 ? -1 : log2_strip);
-}
-
-hipError_t launch_pvrtc2(const PvrtcParams &P, hipStream_t stream) {
-  if (P.n_images == 0) return hipSuccess;
-  if (P.region_blocks != 0) return P.n_images == 1 ? launch_pvrtc2_region(P, stream) : hipErrorInvalidValue;
-  read_path_env();
-  if (g_path_mode.load() != 1 && (uint64_t)(P.size / 8) * (P.size / 4) * P.n_images < (1ull << 31)) {
-    const bool force = g_path_mode.load() == 2;  // (a strip height only counts together with mode 2)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int sb = onepass_log2_strip(P.log2_size, P.n_images, force ? g_path_strip.load() : -1, force, device_compute_units(dev));
-    if (sb >= 0) return launch_pvrtc2_onepass(P, sb, stream);
-    if (P.log2_size - 3u > 9u) {  // textures of 8192^2 and more (r06): a block row is two or more workgroups wide -> halo form
-      const HaloRect R = { 0u, 0u, P.log2_size - 3u, P.log2_size - 2u, 0u };
-      const int hsb = onepass_halo_log2_strip(R, P.n_images, force ? g_path_strip.load() : -1, force, device_compute_units(dev));
-      if (hsb >= 0) return launch_pvrtc2_onepass_halo(P, R, hsb, stream);
-    }
-  }
-  const uint32_t bw = P.size / 8, bh = P.size / 4;
-  const uint64_t bpi = (uint64_t)bw * bh;
-  // Images per launch pair.  Every launch boundary costs a drain/fill of ~4 waves per SIMD: measured 0.67 / 0.60 /
-  // 0.58 / 0.57 ms per 16 x 4096^2 for groups of 64 MiB / 128 MiB / 512 MiB / 1 GiB of pixels (r01).  So: as many
-  // images per launch as the 32-bit block index and a 256 MiB workspace allow.  (r02: hosting the encode workgroups
-  // of one image group and the morph workgroups of the next in ONE grid, 1 : 2 interleaved -- the encode role is
-  // VALU-bound, the morph role memory-bound -- was measured at 0.55 / 0.59 / 0.68 ms for 2 / 4 / 8 stages against
-  // 0.53 ms for the two plain kernels: the shared 167-VGPR allocation and the extra fill/drain phases cost more than
-  // the overlap gains.  Removed.)
-  const uint64_t group = pvrtc_group(P.size, P.n_images);
-  if (bpi * group >= (1ull << 31)) return hipErrorInvalidValue;
-
-  // Workspace for the reduced colours (8 B per block of one image group).  A grow-only hipMalloc buffer per host
-  // thread: stream-ordered pool memory (hipMallocAsync) proved unusable for producer->consumer kernels on ROCm 7.2
-  // (a reused pool block was observed zero-filled underneath the first kernel; scripts/coh_test.hip).
-  uint2 *ab = nullptr;
-  Workspace &ws = g_tls_workspace.get();
-  hipError_t e = ws.acquire((size_t)(bpi * group * sizeof(uint2)), stream, reinterpret_cast<void **>(&ab), P.internal_workspace);
-  if (e != hipSuccess) return e;
-  (void)hipGetLastError();
-  PvrtcLaunch L;
-  L.ab = ab;
-  L.src_image_stride = P.src_image_stride;
-  L.dst_image_stride = P.dst_image_stride;
-  L.size = P.size;
-  L.log2_bw = P.log2_size - 3;
-  L.log2_bpi = 2 * P.log2_size - 5;
-  // strip height: 8 blocks (32 pixel rows) amortise the one halo row per strip to 1/32 of the modulation work
-  // while a 4096^2 image still yields 1 024 waves; never more than the image's block rows (size / 4)
-  L.log2_strip = P.log2_size - 2 < 3 ? P.log2_size - 2 : 3;
-  // ... and never so tall that a small launch leaves the chip empty: a strip is one long dependent instruction
-  // stream (~1 200 per block), so below ~2 waves per SIMD of strips, shorter strips finish sooner
-  // (one 1024^2 texture: 40 us with 8-block strips, a quarter of that with 1-block strips)
-  while (L.log2_strip > 0 && ((bpi * group) >> L.log2_strip) < kFullChipLanes) --L.log2_strip;
-  L.rx0 = L.ry0 = L.z_first = 0;
-  L.log2_rw = L.log2_bw;
-  L.log2_rblocks = L.log2_bpi;
-  // the staged write-out issues 16-byte stores: taken only when every image's output is 16-byte aligned (the
-  // contract asks for 8); otherwise each block is stored on its own, 8 bytes at its Z-order slot
-  const bool dst16 = reinterpret_cast<uintptr_t>(P.dst) % 16u == 0 && (P.n_images == 1 || P.dst_image_stride % 16u == 0);
-  for (uint64_t first = 0; first < P.n_images; first += group) {
-    const uint64_t count = (P.n_images - first < group) ? P.n_images - first : group;
-    // images [i0, i0 + cnt) of this chunk as one launch descriptor
-    auto part = [&](uint64_t i0, uint64_t cnt, uint32_t log2_strip) {
-      PvrtcLaunch Q = L;
-      Q.src = P.src + (first + i0) * P.src_image_stride;
-      Q.dst = P.dst + (first + i0) * P.dst_image_stride;
-      Q.ab = ab + i0 * bpi;
-      Q.log2_strip = log2_strip;
-      Q.stage_stores = (log2_strip >= 1 && Q.log2_rw >= log2_strip && dst16) ? 1u : 0u;
-      Q.total_blocks = (uint32_t)(bpi * cnt);
-      Q.total_strips = Q.total_blocks >> log2_strip;
-      return Q;
-    };
-    const PvrtcLaunch Q = part(0, count, L.log2_strip);
-    // one block per lane up to AND INCLUDING two waves per SIMD of four-block lanes -- one 4096^2 texture is exactly that:
-    // morph 17.0 -> 14.7 us per call (r03, rocprofv3; the memory-bound kernel wants the extra waves in flight)
-    const bool small = Q.total_blocks <= (uint32_t)kMorphBlocksPerLane * kFullChipLanes;
-    const uint32_t per_wg = kMorphLanes * (small ? 1 : kMorphBlocksPerLane);
-    const dim3 gm((Q.total_blocks + per_wg - 1) / per_wg), ge((Q.total_strips + kEncodeLanes - 1) / kEncodeLanes);
-    if (small) hipLaunchKernelGGL(icamd_pvrtc2_morph_small_kernel, gm, dim3(kMorphLanes), 0, stream, Q);
-    else if (Q.log2_bw >= 6) hipLaunchKernelGGL(icamd_pvrtc2_morph_dense_kernel, gm, dim3(kMorphLanes), 0, stream, Q);
-    else hipLaunchKernelGGL(icamd_pvrtc2_morph_kernel, gm, dim3(kMorphLanes), 0, stream, Q);
-    hipLaunchKernelGGL(Q.log2_rw >= 6 ? icamd_pvrtc2_encode_kernel : icamd_pvrtc2_encode_narrow_kernel, ge,
-                       dim3(kEncodeLanes), 0, stream, Q);
-  }
-  e = hipGetLastError();
-  const hipError_t e2 = ws.release(stream);
-  return e != hipSuccess ? e : e2;
-}
 
 // ---- PVRTC1 4 bpp (r05): EXTENSION, PARITY UNPINNED (pvrtc_block.h; the reference has no 4 bpp mode) -----------------------
 // Two kernels like the 2 bpp pair, one 4 x 4 block per lane, lanes in Z ORDER (lane k of an image = block with Z index k:
@@ -1065,16 +758,8 @@ struct Pvrtc4Launch {
   uint64_t src_image_stride, dst_image_stride;
   uint32_t log2_n, log2_bpi, total_blocks;
 };
-__device__ __forceinline__ uint32_t compact_even_bits_dev(uint32_t v) {
-  v &= 0x55555555u;
-  v = (v | v >> 1) & 0x33333333u;
-  v = (v | v >> 2) & 0x0f0f0f0fu;
-  v = (v | v >> 4) & 0x00ff00ffu;
-  v = (v | v >> 8) & 0x0000ffffu;
-  return v;
-}
 __device__ __forceinline__ void pvrtc4_load_block(const Pvrtc4Launch &L, const uint32_t *img, uint32_t z, uint32_t px[16]) {
-  const uint32_t bx = compact_even_bits_dev(z >> 1), by = compact_even_bits_dev(z);
+  const uint32_t bx = compact_even_bits(z >> 1), by = compact_even_bits(z);
   const uint32_t *p = img + (((by * 4u) << L.log2_n) + bx * 4u);
 #pragma unroll
   for (int y = 0; y < 4; ++y) {
@@ -1125,8 +810,6 @@ extern "C" __global__ void __launch_bounds__(kEncodeLanes) icamd_pvrtc4_encode_k
 // (pvrtc4_onepass_strip).  A row slot of the per-wave ring is 64 lanes x 16 bytes = 1 KiB (one DMA instruction per row), eight
 // of them plus a 1 KiB tile of finished blocks (2 block rows, 32-byte runs) = 9 KiB per wave: sixteen waves per CU, four per
 // SIMD, which a 1 024-lane workgroup needs anyway (and which caps the walk at 128 VGPRs).
-constexpr uint32_t kOnePass4WaveDwords = kOnePassRing * 256u + 256u;  // ring + tile: 9 216 bytes
-constexpr uint32_t kOnePass4XchDwords = 4;                            // per wave and parity: lo.a lo.b hi.a hi.b
 struct Pvrtc4OnePass {
   const uint8_t *src;
   uint8_t *dst;
@@ -1217,104 +900,137 @@ extern "C" __global__ void __launch_bounds__(1024) icamd_pvrtc4_onepass_kernel(P
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- launch code: read mode and strip, ask the plan (pvrtc_plan.h), acquire the workspace if it says pair, launch ----------------
 namespace {
-// Strip height of the 4 bpp one-pass kernel, or -1 where the pair is the better choice.  Measured (r05, profiles/
-// r05_ab_pvrtc4_onepass.log): a strip workgroup takes 11 + 5.8 K us on a full CU whatever its width -- the 2 bpp kernel's
-// figure: the same pixels per CU and block row --, a CU holds 16 / waves-per-workgroup of them; the pair takes 10 us + 1.87 us per
-// million pixels.  Below ~8 Mpixel per launch neither fills the chip and the pair's two short kernels are as fast or faster
-// (1 x 2048^2: 15 vs 21 us), so it keeps those.
-int onepass4_log2_strip(uint32_t log2_size, uint64_t n_images, int forced, bool always, uint32_t compute_units) {
-  const uint32_t log2_bw = log2_size - 2u;  // blocks per row = lanes per workgroup
-  if (log2_bw < 6u || log2_bw > 10u) return -1;
-  if (forced >= 0) return forced < 1 ? 1 : (forced > (int)log2_bw ? (int)log2_bw : forced);
-  const uint64_t pixels = n_images << (2u * log2_size);
-  if (!always && pixels < (8ull << 20)) return -1;
-  const uint64_t slots = (uint64_t)compute_units * (16u >> (log2_bw - 6u));
-  int best = -1;
-  double best_us = 0.0;
-  for (int sb = 2; sb <= 6 && sb <= (int)log2_bw; ++sb) {
-    const uint64_t wgs = n_images << (log2_bw - (uint32_t)sb);
-    const double us = (double)((wgs + slots - 1) / slots) * (11.0 + 5.8 * (double)(1u << sb));
-    if (best < 0 || us <= best_us) { best_us = us; best = sb; }
-  }
-  const double pair_us = 10.0 + 1.87e-6 * (double)pixels;
-  return always || best_us < 0.97 * pair_us ? best : -1;
+std::atomic<int> g_path_mode{-1};   // -1: not read yet; 0 auto, 1 always two kernels, 2 one pass wherever it is eligible
+std::atomic<int> g_path_strip{-2};  // -2: not read yet; -1 auto, else log2(blocks per strip) of the one-pass kernel
+// The environment is read ONCE, by whichever of the first launch and the first icamd_pvrtc2_tune comes first; a tune() then
+// stores over it, so a launch on another thread can no longer read the environment on top of a tune() call (ADVICE r05).
+std::once_flag g_path_env_once;
+void read_path_env() {
+  std::call_once(g_path_env_once, [] {
+    const char *m = getenv("ICAMD_PVRTC2_PATH"), *k = getenv("ICAMD_PVRTC2_STRIP");
+    int mode = 0;
+    if (m && !strcmp(m, "two")) mode = 1;
+    else if (m && !strcmp(m, "one")) mode = 2;
+    g_path_strip.store(k && *k ? atoi(k) : -1);
+    g_path_mode.store(mode);
+  });
 }
-hipError_t launch_pvrtc4_onepass(const PvrtcParams &P, int sb, hipStream_t stream) {
-  const uint32_t lanes = P.size / 4u, waves = lanes >> 6;
-  const size_t lds_bytes = (size_t)waves * (kOnePass4WaveDwords + 2u * kOnePass4XchDwords) * 4u;
+
+// The plan of this call, for the tune mode and strip of this moment and the compute units of this device
+PvrtcPlan plan_launch(uint32_t bpp, const PvrtcParams &P) {
+  read_path_env();
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool dst16 = reinterpret_cast<uintptr_t>(P.dst) % 16u == 0 && (P.n_images == 1 || P.dst_image_stride % 16u == 0);
+  const PvrtcPlanIn in = { bpp, P.log2_size, P.n_images, P.region_first, P.region_blocks, g_path_mode.load(), g_path_strip.load(),
+                           device_compute_units(dev), dst16 };
+  return pvrtc_plan(in);
+}
+
+// More than 64 KiB of dynamic LDS has to be allowed per function and device, once: `bytes` is what the kernel's widest workgroup
+// takes.  One mask of device ordinals per kernel (ordinals past 63: every time).
+template <auto Kernel>
+hipError_t allow_dynamic_lds(size_t bytes) {
   static std::atomic<uint64_t> allowed{0};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !((allowed.load() >> dev) & 1u)) {  // (ordinals past 63: every time)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(icamd_pvrtc4_onepass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(16u * (kOnePass4WaveDwords + 2u * kOnePass4XchDwords) * 4u));
+  if (dev < 0 || dev >= 64 || !((allowed.load() >> dev) & 1u)) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64) allowed.fetch_or(1ull << dev);
   }
-  Pvrtc4OnePass L;
-  L.src = P.src;
-  L.dst = P.dst;
-  L.src_image_stride = P.src_image_stride;
-  L.dst_image_stride = P.dst_image_stride;
-  L.log2_n = P.log2_size;
-  L.log2_strip = (uint32_t)sb;
-  L.stage_stores = (reinterpret_cast<uintptr_t>(P.dst) % 16u == 0 && (P.n_images == 1 || P.dst_image_stride % 16u == 0)) ? 1u : 0u;
-  const uint32_t strips_per_image = lanes >> sb;
-  hipLaunchKernelGGL(icamd_pvrtc4_onepass_kernel, dim3((uint32_t)(P.n_images * (uint64_t)strips_per_image)), dim3(lanes), lds_bytes, stream, L);
-  return hipGetLastError();
+  return hipSuccess;
+}
+
+// The descriptor of a 2 bpp launch, from `first_image` on: the plan's figures; the pair adds its workspace and the launch's share of
+// the images (one-pass forms: nullptr and the plan's empty chunk)
+PvrtcLaunch pvrtc2_descriptor(const PvrtcParams &P, const PvrtcPlan &plan, uint64_t first_image, uint2 *ab, const PvrtcPairChunk &chunk) {
+  PvrtcLaunch L;
+  L.src = P.src + first_image * P.src_image_stride;
+  L.dst = P.dst + first_image * P.dst_image_stride;
+  L.ab = ab;
+  L.src_image_stride = P.src_image_stride; L.dst_image_stride = P.dst_image_stride;
+  L.size = P.size;
+  L.log2_bw = P.log2_size - 3; L.log2_bpi = 2 * P.log2_size - 5;
+  L.log2_strip = plan.log2_strip;
+  L.total_blocks = chunk.total_blocks; L.total_strips = chunk.total_strips;
+  L.rx0 = plan.rx0; L.ry0 = plan.ry0; L.z_first = plan.z_first;
+  L.log2_rw = plan.log2_rw;
+  L.log2_rblocks = plan.log2_rw + plan.log2_rh;
+  L.stage_stores = plan.stage_stores;
+  L.log2_wgc = plan.log2_wgc;
+  return L;
 }
 }  // namespace
 
-hipError_t launch_pvrtc4(const PvrtcParams &P, hipStream_t stream) {
-  if (P.n_images == 0) return hipSuccess;
-  if (P.region_blocks != 0) return hipErrorInvalidValue;
+void pvrtc2_tune(int mode, int log2_strip) {
   read_path_env();
-  if (g_path_mode.load() != 1 && (uint64_t)(P.size / 4) * (P.size / 4) * P.n_images < (1ull << 31)) {
-    const bool force = g_path_mode.load() == 2;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int sb = onepass4_log2_strip(P.log2_size, P.n_images, force ? g_path_strip.load() : -1, force, device_compute_units(dev));
-    if (sb >= 0) return launch_pvrtc4_onepass(P, sb, stream);
+  g_path_mode.store(mode < 0 || mode > 2 ? 0 : mode);
+  g_path_strip.store(log2_strip < 0 ? -1 : log2_strip);
+}
+
+namespace {
+hipError_t launch_pvrtc(uint32_t bpp, const PvrtcParams &P, hipStream_t stream) {
+  if (P.n_images == 0) return hipSuccess;
+  const PvrtcPlan plan = plan_launch(bpp, P);
+  if (plan.path == kPvrtcRefused) return hipErrorInvalidValue;
+  if (plan.path != kPvrtcPair) {  // one launch, no scratch memory
+    const bool halo = plan.path == kPvrtcOnePassHalo;
+    const hipError_t e = bpp == 4 ? allow_dynamic_lds<icamd_pvrtc4_onepass_kernel>(plan.lds_opt_in_bytes)
+                         : halo   ? allow_dynamic_lds<icamd_pvrtc2_onepass_halo_kernel>(plan.lds_opt_in_bytes)
+                                  : allow_dynamic_lds<icamd_pvrtc2_onepass_kernel>(plan.lds_opt_in_bytes);
+    if (e != hipSuccess) return e;
+    (void)hipGetLastError();
+    const dim3 grid(plan.workgroups), lanes(plan.lanes);
+    if (bpp == 4) {
+      const Pvrtc4OnePass L = { P.src, P.dst, P.src_image_stride, P.dst_image_stride, P.log2_size, plan.log2_strip, plan.stage_stores };
+      hipLaunchKernelGGL(icamd_pvrtc4_onepass_kernel, grid, lanes, plan.lds_bytes, stream, L);
+    } else {
+      hipLaunchKernelGGL(halo ? icamd_pvrtc2_onepass_halo_kernel : icamd_pvrtc2_onepass_kernel, grid, lanes, plan.lds_bytes, stream,
+                         pvrtc2_descriptor(P, plan, 0, nullptr, plan.full));
+    }
+    return hipGetLastError();
   }
-  const uint64_t bpi = (uint64_t)(P.size / 4) * (P.size / 4);
-  const uint64_t group = pvrtc_group(P.size, P.n_images);
-  if (bpi * group >= (1ull << 31)) return hipErrorInvalidValue;
+  // Workspace for the reduced colours (8 B per block of one image group).  A grow-only hipMalloc buffer per host
+  // thread: stream-ordered pool memory (hipMallocAsync) proved unusable for producer->consumer kernels on ROCm 7.2
+  // (a reused pool block was observed zero-filled underneath the first kernel; scripts/coh_test.hip).
   uint2 *ab = nullptr;
   Workspace &ws = g_tls_workspace.get();
-  hipError_t e = ws.acquire((size_t)(bpi * group * sizeof(uint2)), stream, reinterpret_cast<void **>(&ab), P.internal_workspace);
+  hipError_t e = ws.acquire(plan.workspace_bytes, stream, reinterpret_cast<void **>(&ab), P.internal_workspace);
   if (e != hipSuccess) return e;
   (void)hipGetLastError();
-  for (uint64_t first = 0; first < P.n_images; first += group) {
-    const uint64_t count = (P.n_images - first < group) ? P.n_images - first : group;
-    Pvrtc4Launch L;
-    L.src = P.src + first * P.src_image_stride;
-    L.dst = P.dst + first * P.dst_image_stride;
-    L.ab = ab;
-    L.src_image_stride = P.src_image_stride;
-    L.dst_image_stride = P.dst_image_stride;
-    L.log2_n = P.log2_size;
-    L.log2_bpi = 2 * P.log2_size - 4;
-    L.total_blocks = (uint32_t)(bpi * count);
-    const dim3 grid((L.total_blocks + kMorphLanes - 1) / kMorphLanes);
-    hipLaunchKernelGGL(icamd_pvrtc4_morph_kernel, grid, dim3(kMorphLanes), 0, stream, L);
-    hipLaunchKernelGGL(icamd_pvrtc4_encode_kernel, grid, dim3(kEncodeLanes), 0, stream, L);
+  static void (*const kMorph[])(PvrtcLaunch) = { icamd_pvrtc2_morph_small_kernel, icamd_pvrtc2_morph_dense_kernel, icamd_pvrtc2_morph_kernel,
+                                                 icamd_pvrtc2_morph_rect_kernel };  // (indexed by PvrtcMorph)
+  for (uint64_t first = 0; first < P.n_images; first += plan.group) {
+    const PvrtcPairChunk &c = P.n_images - first < plan.group ? plan.tail : plan.full;
+    const dim3 gm(c.morph_grid_x, c.morph_grid_y), ge(c.encode_grid);
+    if (bpp == 4) {
+      const Pvrtc4Launch L = { P.src + first * P.src_image_stride, P.dst + first * P.dst_image_stride, ab, P.src_image_stride,
+                               P.dst_image_stride, P.log2_size, 2 * P.log2_size - 4, c.total_blocks };
+      hipLaunchKernelGGL(icamd_pvrtc4_morph_kernel, gm, dim3(kMorphLanes), 0, stream, L);
+      hipLaunchKernelGGL(icamd_pvrtc4_encode_kernel, ge, dim3(kEncodeLanes), 0, stream, L);
+    } else {
+      const PvrtcLaunch L = pvrtc2_descriptor(P, plan, first, ab, c);
+      hipLaunchKernelGGL(kMorph[c.morph], gm, dim3(kMorphLanes), 0, stream, L);
+      hipLaunchKernelGGL(plan.encode == kPvrtcEncodeWide ? icamd_pvrtc2_encode_kernel : icamd_pvrtc2_encode_narrow_kernel, ge,
+                         dim3(kEncodeLanes), 0, stream, L);
+    }
   }
   e = hipGetLastError();
   const hipError_t e2 = ws.release(stream);
   return e != hipSuccess ? e : e2;
 }
-size_t pvrtc4_workspace_bytes(uint32_t size, uint32_t n_images) {
-  if (n_images == 0) return 0;
-  return (size_t)((uint64_t)(size / 4) * (size / 4) * pvrtc_group(size, n_images) * sizeof(uint2));
-}
+}  // namespace
+
+hipError_t launch_pvrtc2(const PvrtcParams &P, hipStream_t stream) { return launch_pvrtc(2, P, stream); }
+hipError_t launch_pvrtc4(const PvrtcParams &P, hipStream_t stream) { return launch_pvrtc(4, P, stream); }
 const char *pvrtc4_kernel_name() { return "icamd_pvrtc4_onepass_kernel"; }
 
-size_t pvrtc2_workspace_bytes(uint32_t size, uint32_t n_images) {
-  if (n_images == 0) return 0;
-  return (size_t)((uint64_t)(size / 8) * (size / 4) * pvrtc_group(size, n_images) * sizeof(uint2));
-}
+size_t pvrtc4_workspace_bytes(uint32_t size, uint32_t n_images) { return pvrtc_workspace_bytes(4, size, n_images); }
+size_t pvrtc2_workspace_bytes(uint32_t size, uint32_t n_images) { return pvrtc_workspace_bytes(2, size, n_images); }
 void pvrtc2_select_workspace(int slot) { g_tls_workspace.slot = slot & 1; }
 void pvrtc2_set_workspace(void *d_workspace, size_t bytes) {
   const int keep = g_tls_workspace.slot;
