@@ -1,5 +1,6 @@
 // blockops_kernels.hip -- Pad / Downsample / DXT1->ETC1 transcode kernels: one output
-// block per lane, coalesced 8/16-byte block loads and stores.  See blockops_block.h for the per-block math.
+// block per lane, coalesced 8/16-byte block loads and stores.  See blockops_block.h for the per-block math and
+// blockops_plan.h for which kernel a call gets, with which grid: the launchers at the end of this file run what the plan says.
 #include <cstdlib>
 #include "blockops_block.h"
 #include "ic_launch.h"
@@ -7,11 +8,28 @@
 
 namespace icamd {
 
+static_assert(kBlockOpDxt1 == ICAMD_DXT1 && kBlockOpDxt5 == ICAMD_DXT5 && kBlockOpEtc1 == ICAMD_ETC1, "blockops_plan.h codecs");
+static_assert(kBlockOpLanes == kThreadsPerWorkgroup, "blockops_plan.h workgroup");
+
 namespace {
 constexpr int kWords(int codec) { return codec == ICAMD_DXT5 ? 4 : 2; }
 }
 
-// (r, c) of output block k: the source block it copies / replicates, and whether it is a pad block.
+// What a Pad kernel's work items are: every output block, pad blocks made on the way (DXT); every output block, only the image's
+// own written (the ETC1 copy); the pad blocks alone, one lane each; the pad blocks alone, four lanes each (kSmallerError)
+enum PadPart : int { kPadWhole = 0, kPadCopy = 1, kPadBorder = 2, kPadBorderQuad = 3 };
+
+// Border block k of an image -> (r, c): the in_rows x extra columns right of the image first, then the extra rows over the full width
+struct RowCol { uint32_t r, c; };
+__device__ __forceinline__ RowCol pad_border_rc(const BlockOpParams &P, uint32_t k) {
+  const uint32_t dc = P.out_cols - P.in_cols, right = P.in_rows * dc;
+  uint32_t r, c;
+  if (k < right) { r = k / dc; c = P.in_cols + (k - r * dc); }
+  else { const uint32_t j = k - right; r = P.in_rows + j / P.out_cols; c = j - (r - P.in_rows) * P.out_cols; }
+  return { r, c };
+}
+
+// (r, c) of an output block: the source block it copies / replicates, and whether it is a pad block.
 template <int CODEC, int STRATEGY>
 __device__ __forceinline__ void pad_block(const BlockOpParams &P, uint32_t img, uint32_t r, uint32_t c, bool copy_interior,
                                           bool make_border) {
@@ -48,17 +66,17 @@ __device__ __forceinline__ void pad_block(const BlockOpParams &P, uint32_t img, 
 }
 
 // DXT: one pass over the output grid (a pad block is a few bit edits).  ETC1 (r04): a pad block is a decode + re-encode -- up to
-// the whole kSmallerError search -- so the copy of the image's own blocks runs as one light kernel over the grid (PART 1: 7 VGPRs,
-// 8 waves per SIMD) and the pad blocks as a second, small launch over the BORDER only (PART 2: the in_rows x extra columns to
-// the right, then the extra rows over the full width); in one kernel the searches' 121 VGPRs capped the copy at 4 waves per SIMD
-// and every wave that touched the border ran the search (28.6 -> ~7 us per 4096^2 image padded by 8 pixels).
+// the whole kSmallerError search -- so the copy of the image's own blocks runs as one light kernel over the grid (kPadCopy: 7 VGPRs,
+// 8 waves per SIMD) and the pad blocks as a second, small launch over the BORDER only (kPadBorder); in one kernel the searches'
+// 121 VGPRs capped the copy at 4 waves per SIMD and every wave that touched the border ran the search (28.6 -> ~7 us per 4096^2
+// image padded by 8 pixels).
 // Batched launches (icamd_pad_batch_device, r05): n_images equally shaped grids, out_per_image work items each (output blocks;
-// PART 2: border blocks).
+// kPadBorder: border blocks; kPadBorderQuad: border_lanes_per_image quad lanes).
 template <int CODEC, int STRATEGY, int PART>
 __device__ __forceinline__ void pad_one(const BlockOpParams &P, uint32_t k) {
   uint32_t img = 0;
   if (P.n_images > 1) {
-    if (PART == 3) {  // work items are quad lanes of pad blocks
+    if (PART == kPadBorderQuad) {
       img = fastdiv(k, P.div_border_lanes_per_image);
       k -= img * P.border_lanes_per_image;
     } else {
@@ -66,13 +84,12 @@ __device__ __forceinline__ void pad_one(const BlockOpParams &P, uint32_t k) {
       k -= img * P.out_per_image;
     }
   }
-  if (PART == 3) {  // PART 2 with four lanes per pad block (kSmallerError): work item k = 4 * border block + quad lane
+  if (PART == kPadBorderQuad) {  // kPadBorder with four lanes per pad block (kSmallerError): work item k = 4 * border block + quad lane
     const uint32_t t = k & 3u;
     k >>= 2;
-    const uint32_t dc = P.out_cols - P.in_cols, right = P.in_rows * dc;
-    uint32_t r, c;
-    if (k < right) { r = k / dc; c = P.in_cols + (k - r * dc); }
-    else { const uint32_t j = k - right; r = P.in_rows + j / P.out_cols; c = j - (r - P.in_rows) * P.out_cols; }
+    const RowCol at = pad_border_rc(P, k);
+    const uint32_t r = at.r, c = at.c;
+    // (its own addressing: sharing pad_block's changed the instruction order of every Pad kernel)
     const bool in_rows = r < P.in_rows, in_cols = c < P.in_cols;
     const uint32_t sr = in_rows ? r : P.in_rows - 1, sc = in_cols ? c : P.in_cols - 1;
     const uint32_t *s = reinterpret_cast<const uint32_t *>(P.src + (size_t)img * P.src_image_stride) + ((size_t)sr * P.in_cols + sc) * 2;
@@ -82,16 +99,13 @@ __device__ __forceinline__ void pad_one(const BlockOpParams &P, uint32_t k) {
     if (writes) { dst[0] = o.lo; dst[1] = o.hi; }
     return;
   }
-  if (PART == 2) {
-    const uint32_t dc = P.out_cols - P.in_cols, right = P.in_rows * dc;
-    uint32_t r, c;
-    if (k < right) { r = k / dc; c = P.in_cols + (k - r * dc); }
-    else { const uint32_t j = k - right; r = P.in_rows + j / P.out_cols; c = j - (r - P.in_rows) * P.out_cols; }
-    pad_block<CODEC, STRATEGY>(P, img, r, c, false, true);
+  if (PART == kPadBorder) {
+    const RowCol at = pad_border_rc(P, k);
+    pad_block<CODEC, STRATEGY>(P, img, at.r, at.c, false, true);
     return;
   }
   const uint32_t r = fastdiv(k, P.div_out_cols), c = k - r * P.out_cols;
-  pad_block<CODEC, STRATEGY>(P, img, r, c, true, PART == 0);
+  pad_block<CODEC, STRATEGY>(P, img, r, c, true, PART == kPadWhole);
 }
 
 // STRATEGY: the ETC1 re-encode strategy as a compile-time constant (one kernel per strategy, like the encoders: the
@@ -192,26 +206,22 @@ __device__ __forceinline__ void downsample_one(const BlockOpParams &P, uint32_t 
   downsample_at<CODEC, STRATEGY, QUAD>(P, img, r, c, kk, quad_lane, stash);
 }
 
-// Lanes per workgroup: the kernels that run an ETC1 codeword SEARCH per output block (Downsample and the Pad border with
-// kSplitHorizontally / kSplitVertically / kSmallerError) are launched as one-wave workgroups like the encoders (r05,
-// etc1_kernels.hip etc1_wave_workgroups: the search's cost depends on the content, and a four-wave workgroup holds its
-// slots until its slowest wave is done); everything else keeps 256.
-constexpr int blockop_lanes(int codec, int strategy, int part) {
-  return (codec == ICAMD_ETC1 && strategy != 3 && part != 1) ? 64 : kThreadsPerWorkgroup;
-}
+// Lanes per workgroup: blockop_lanes (blockops_plan.h), one wave where the kernel runs an ETC1 search per block.
 #define ICAMD_PAD_KERNEL(NAME, CODEC, STRATEGY, PART)                                                          \
   extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pad_##NAME##_kernel(BlockOpParams P) { \
-    const uint32_t k = blockIdx.x * (uint32_t)blockop_lanes(CODEC, STRATEGY, PART) + threadIdx.x;              \
+    const uint32_t k = blockIdx.x * blockop_lanes(CODEC, STRATEGY, PART == kPadCopy) + threadIdx.x;            \
     if (k < P.total_out) pad_one<CODEC, STRATEGY, PART>(P, k);                                                 \
   }
+// the per-lane pixel stash of the Downsample kernels: only the DXT colour encoder uses it
+#define ICAMD_DOWNSAMPLE_STASH(CODEC)                                                                          \
+  __shared__ uint32_t lds_px[CODEC == ICAMD_ETC1 ? 1 : 4][CODEC == ICAMD_ETC1 ? 1 : kThreadsPerWorkgroup][4];  \
+  BlockStash stash;                                                                                            \
+  stash.base = CODEC == ICAMD_ETC1 ? &lds_px[0][0][0] : &lds_px[0][threadIdx.x][0];
 #define ICAMD_DOWNSAMPLE_KERNEL(NAME, CODEC, STRATEGY)                                                         \
   extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup)                                           \
   icamd_downsample_##NAME##_kernel(BlockOpParams P) {                                                          \
-    /* the per-lane pixel stash is only used by the DXT colour encoder */                                      \
-    __shared__ uint32_t lds_px[CODEC == ICAMD_ETC1 ? 1 : 4][CODEC == ICAMD_ETC1 ? 1 : kThreadsPerWorkgroup][4]; \
-    BlockStash stash;                                                                                          \
-    stash.base = CODEC == ICAMD_ETC1 ? &lds_px[0][0][0] : &lds_px[0][threadIdx.x][0];                          \
-    const uint32_t k = blockIdx.x * (uint32_t)blockop_lanes(CODEC, STRATEGY, 0) + threadIdx.x;                 \
+    ICAMD_DOWNSAMPLE_STASH(CODEC)                                                                              \
+    const uint32_t k = blockIdx.x * blockop_lanes(CODEC, STRATEGY, false) + threadIdx.x;                       \
     if (k < P.total_out) downsample_one<CODEC, STRATEGY>(P, k, stash);                                         \
   }
 
@@ -221,29 +231,27 @@ constexpr int blockop_lanes(int codec, int strategy, int part) {
 #define ICAMD_DOWNSAMPLE_ROWS_KERNEL(NAME, CODEC, STRATEGY)                                                    \
   extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup)                                           \
   icamd_downsample_##NAME##_rows_kernel(BlockOpParams P) {                                                     \
-    __shared__ uint32_t lds_px[CODEC == ICAMD_ETC1 ? 1 : 4][CODEC == ICAMD_ETC1 ? 1 : kThreadsPerWorkgroup][4]; \
-    BlockStash stash;                                                                                          \
-    stash.base = CODEC == ICAMD_ETC1 ? &lds_px[0][0][0] : &lds_px[0][threadIdx.x][0];                          \
+    ICAMD_DOWNSAMPLE_STASH(CODEC)                                                                              \
     const uint32_t c = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x, r = blockIdx.y, img = blockIdx.z;      \
     if (c < P.out_cols) downsample_at<CODEC, STRATEGY>(P, img, r, c, r * P.out_cols + c, 0u, stash);           \
   }
-ICAMD_PAD_KERNEL(dxt1, ICAMD_DXT1, 0, 0)
-ICAMD_PAD_KERNEL(dxt5, ICAMD_DXT5, 0, 0)
-ICAMD_PAD_KERNEL(etc1_copy, ICAMD_ETC1, 0, 1)
-ICAMD_PAD_KERNEL(etc1_border_split_h, ICAMD_ETC1, 0, 2)
-ICAMD_PAD_KERNEL(etc1_border_split_v, ICAMD_ETC1, 1, 2)
-ICAMD_PAD_KERNEL(etc1_border, ICAMD_ETC1, 2, 2)
-ICAMD_PAD_KERNEL(etc1_border_heuristic, ICAMD_ETC1, 3, 2)
+ICAMD_PAD_KERNEL(dxt1, ICAMD_DXT1, 0, kPadWhole)
+ICAMD_PAD_KERNEL(dxt5, ICAMD_DXT5, 0, kPadWhole)
+ICAMD_PAD_KERNEL(etc1_copy, ICAMD_ETC1, 0, kPadCopy)
+ICAMD_PAD_KERNEL(etc1_border_split_h, ICAMD_ETC1, 0, kPadBorder)
+ICAMD_PAD_KERNEL(etc1_border_split_v, ICAMD_ETC1, 1, kPadBorder)
+ICAMD_PAD_KERNEL(etc1_border, ICAMD_ETC1, 2, kPadBorder)
+ICAMD_PAD_KERNEL(etc1_border_heuristic, ICAMD_ETC1, 3, kPadBorder)
 // kSmallerError (r05): four lanes per pad block, and -- the split search needs 61 VGPRs where the whole one needed 121, so the
 // copy no longer loses occupancy to it -- in the SAME launch as the copy of the image's own blocks: the first border_wgs
 // workgroups are the pad blocks (they start first and are the long ones), the others copy.  One launch per Pad call.
 extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pad_etc1_quad_kernel(BlockOpParams P) {
   if (blockIdx.x < P.border_wgs) {
     const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
-    if (k < P.border_lanes) pad_one<ICAMD_ETC1, 2, 3>(P, k);
+    if (k < P.border_lanes) pad_one<ICAMD_ETC1, 2, kPadBorderQuad>(P, k);
   } else {
     const uint32_t k = (blockIdx.x - P.border_wgs) * kThreadsPerWorkgroup + threadIdx.x;
-    if (k < P.total_out) pad_one<ICAMD_ETC1, 2, 1>(P, k);
+    if (k < P.total_out) pad_one<ICAMD_ETC1, 2, kPadCopy>(P, k);
   }
 }
 ICAMD_DOWNSAMPLE_KERNEL(dxt1, ICAMD_DXT1, 0)
@@ -255,9 +263,7 @@ ICAMD_DOWNSAMPLE_KERNEL(etc1_heuristic, ICAMD_ETC1, 3)
 ICAMD_DOWNSAMPLE_ROWS_KERNEL(dxt1, ICAMD_DXT1, 0)
 ICAMD_DOWNSAMPLE_ROWS_KERNEL(dxt5, ICAMD_DXT5, 0)
 ICAMD_DOWNSAMPLE_ROWS_KERNEL(etc1_heuristic, ICAMD_ETC1, 3)
-// kSmallerError on grids of at most kDownsampleQuadMaxBlocks output blocks (r05): four lanes per output block.  A 512^2 level is
-// 4 096 output blocks = 64 waves of ~3 000 dependent instructions on 64 of 1 024 SIMDs; the quad form makes it 256 waves of ~1 500.
-constexpr uint32_t kDownsampleQuadMaxBlocks = 36864;
+// kSmallerError on grids of at most kDownsampleQuadMaxBlocks output blocks (r05, blockops_plan.h): four lanes per output block.
 extern "C" __global__ void __launch_bounds__(64) icamd_downsample_etc1_quad_kernel(BlockOpParams P) {
   BlockStash stash;
   stash.base = nullptr;  // (only the DXT colour encoder parks pixels)
@@ -280,73 +286,73 @@ static bool pad_border_quad() {
   return on;
 }
 
-hipError_t launch_pad(int codec, const BlockOpParams &P, hipStream_t stream) {
-  if (P.total_out == 0) return hipSuccess;
-  const dim3 grid((P.total_out + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), block(kThreadsPerWorkgroup);
-  if (codec == ICAMD_DXT1) hipLaunchKernelGGL(icamd_pad_dxt1_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_DXT5) hipLaunchKernelGGL(icamd_pad_dxt5_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_ETC1) {
-    const uint64_t border = (uint64_t)P.in_rows * (P.out_cols - P.in_cols) + (uint64_t)(P.out_rows - P.in_rows) * P.out_cols;
-    if (border && P.etc_strategy != 0u && P.etc_strategy != 1u && P.etc_strategy != 3u && pad_border_quad() &&
-        border * 4u * P.n_images < (1ull << 31)) {
-      BlockOpParams Q = P;
-      Q.border_lanes_per_image = (uint32_t)border * 4u;
-      Q.div_border_lanes_per_image = make_fastdiv(Q.border_lanes_per_image);
-      Q.border_lanes = Q.border_lanes_per_image * P.n_images;
-      Q.border_wgs = (Q.border_lanes + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup;
-      hipLaunchKernelGGL(icamd_pad_etc1_quad_kernel, dim3(grid.x + Q.border_wgs), block, 0, stream, Q);
-      return hipGetLastError();
+// The kernels of the plan's BlockOpKernel values
+using BlockOpKernelFn = void (*)(BlockOpParams);
+static constexpr BlockOpKernelFn kBlockOpKernelFns[kBlockOpKernels] = {
+  icamd_pad_dxt1_kernel, icamd_pad_dxt5_kernel, icamd_pad_etc1_copy_kernel, icamd_pad_etc1_border_split_h_kernel,
+  icamd_pad_etc1_border_split_v_kernel, icamd_pad_etc1_border_kernel, icamd_pad_etc1_border_heuristic_kernel, icamd_pad_etc1_quad_kernel,
+  icamd_downsample_dxt1_kernel, icamd_downsample_dxt5_kernel, icamd_downsample_etc1_split_h_kernel, icamd_downsample_etc1_split_v_kernel,
+  icamd_downsample_etc1_kernel, icamd_downsample_etc1_heuristic_kernel, icamd_downsample_dxt1_rows_kernel,
+  icamd_downsample_dxt5_rows_kernel, icamd_downsample_etc1_heuristic_rows_kernel, icamd_downsample_etc1_quad_kernel };
+
+// Runs a plan: each group of images, each of its launches, BlockOpParams filled here from the call and the plan.
+static hipError_t launch_blockop(const BlockOpCall &call, const BlockOpPlan &plan, hipStream_t stream) {
+  if (plan.form == kBlockOpRefused) return hipErrorInvalidValue;
+  if (plan.form == kBlockOpNothing) return hipSuccess;
+  const BlockOpIn &in = call.in;
+  for (uint64_t first = 0; first < in.n_images; first += plan.group) {
+    const BlockOpGroup &g = in.n_images - first >= plan.group ? plan.full : plan.tail;
+    for (const BlockOpLaunch &l : g.launch) {
+      if (l.kernel == kNoKernel) continue;
+      BlockOpParams P;
+      P.src = call.src + first * call.src_image_stride;
+      P.dst = call.dst + first * call.dst_image_stride;
+      P.in_rows = in.in_rows; P.in_cols = in.in_cols;
+      P.out_rows = in.out_rows; P.out_cols = in.out_cols;
+      P.total_out = l.items;
+      P.etc_strategy = in.etc_strategy;
+      P.src_height = in.src_height; P.src_width = in.src_width;
+      P.div_out_cols = make_fastdiv(in.out_cols);
+      P.n_images = g.count;
+      P.out_per_image = l.items_per_image;
+      P.div_out_per_image = make_fastdiv(l.items_per_image);
+      P.src_image_stride = call.src_image_stride;
+      P.dst_image_stride = call.dst_image_stride;
+      if (g.form == kPadQuad) {
+        P.border_wgs = g.border_wgs;
+        P.border_lanes = g.border_lanes;
+        P.border_lanes_per_image = plan.border_lanes_per_image;
+        P.div_border_lanes_per_image = make_fastdiv(plan.border_lanes_per_image);
+      }
+      hipLaunchKernelGGL(kBlockOpKernelFns[l.kernel], dim3(l.grid_x, l.grid_y, l.grid_z), dim3(l.lanes), 0, stream, P);
     }
-    hipLaunchKernelGGL(icamd_pad_etc1_copy_kernel, grid, block, 0, stream, P);
-    BlockOpParams B = P;  // the pad blocks only: right of the image, then below it
-    B.out_per_image = (uint32_t)border;
-    B.div_out_per_image = make_fastdiv(border ? (uint32_t)border : 1u);
-    B.total_out = (uint32_t)(border * P.n_images);
-    if (border) {
-      const uint32_t lanes = (uint32_t)blockop_lanes(ICAMD_ETC1, P.etc_strategy == 3u ? 3 : 2, 2);
-      const dim3 bgrid((B.total_out + lanes - 1) / lanes), bblock(lanes);
-      if (P.etc_strategy == 0u) hipLaunchKernelGGL(icamd_pad_etc1_border_split_h_kernel, bgrid, bblock, 0, stream, B);
-      else if (P.etc_strategy == 1u) hipLaunchKernelGGL(icamd_pad_etc1_border_split_v_kernel, bgrid, bblock, 0, stream, B);
-      else if (P.etc_strategy == 3u) hipLaunchKernelGGL(icamd_pad_etc1_border_heuristic_kernel, bgrid, bblock, 0, stream, B);
-      else hipLaunchKernelGGL(icamd_pad_etc1_border_kernel, bgrid, bblock, 0, stream, B);
-    }
-  } else return hipErrorInvalidValue;
-  return hipGetLastError();
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
 }
 
-hipError_t launch_downsample(int codec, const BlockOpParams &P, hipStream_t stream) {
-  if (P.total_out == 0) return hipSuccess;
-  const dim3 grid((P.total_out + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), block(kThreadsPerWorkgroup);
-  // row tiles where a row fills a workgroup (small grids keep the linear launch)
-  const bool rows = P.in_rows > 1 && P.in_cols > 1 && P.out_cols >= (uint32_t)kThreadsPerWorkgroup &&
-                    P.out_rows <= 65535u && P.n_images <= 65535u;
-  const dim3 rgrid((P.out_cols + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup, P.out_rows, P.n_images);
-  if (codec == ICAMD_DXT1) {
-    if (rows) hipLaunchKernelGGL(icamd_downsample_dxt1_rows_kernel, rgrid, block, 0, stream, P);
-    else hipLaunchKernelGGL(icamd_downsample_dxt1_kernel, grid, block, 0, stream, P);
-  } else if (codec == ICAMD_DXT5) {
-    if (rows) hipLaunchKernelGGL(icamd_downsample_dxt5_rows_kernel, rgrid, block, 0, stream, P);
-    else hipLaunchKernelGGL(icamd_downsample_dxt5_kernel, grid, block, 0, stream, P);
-  } else if (codec == ICAMD_ETC1 && P.etc_strategy == 3u && rows) {
-    hipLaunchKernelGGL(icamd_downsample_etc1_heuristic_rows_kernel, rgrid, block, 0, stream, P);
-  } else if (codec == ICAMD_ETC1) {
-    const uint32_t lanes = (uint32_t)blockop_lanes(ICAMD_ETC1, P.etc_strategy == 3u ? 3 : 2, 0);
-    const dim3 egrid((P.total_out + lanes - 1) / lanes), eblock(lanes);
-    if (P.etc_strategy == 0u) hipLaunchKernelGGL(icamd_downsample_etc1_split_h_kernel, egrid, eblock, 0, stream, P);
-    else if (P.etc_strategy == 1u) hipLaunchKernelGGL(icamd_downsample_etc1_split_v_kernel, egrid, eblock, 0, stream, P);
-    else if (P.etc_strategy == 3u) hipLaunchKernelGGL(icamd_downsample_etc1_heuristic_kernel, egrid, eblock, 0, stream, P);
-    else if (P.total_out <= kDownsampleQuadMaxBlocks && pad_border_quad())  // (the same A/B switch as the Pad border: ICAMD_PAD_BORDER_QUAD=0)
-      hipLaunchKernelGGL(icamd_downsample_etc1_quad_kernel, dim3((P.total_out * 4u + 63u) / 64u), dim3(64), 0, stream, P);
-    else hipLaunchKernelGGL(icamd_downsample_etc1_kernel, egrid, eblock, 0, stream, P);
-  } else return hipErrorInvalidValue;
-  return hipGetLastError();
+hipError_t launch_pad(BlockOpCall call, hipStream_t stream) {
+  if (call.in.codec < ICAMD_DXT1 || call.in.codec > ICAMD_ETC1) return hipErrorInvalidValue;
+  call.in.quad = pad_border_quad();
+  return launch_blockop(call, pad_plan(call.in), stream);
 }
 
-hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint32_t n_blocks, hipStream_t stream) {
-  if (n_blocks == 0) return hipSuccess;
-  const dim3 grid((n_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), block(kThreadsPerWorkgroup);
-  hipLaunchKernelGGL(icamd_dxt1_to_etc1_kernel, grid, block, 0, stream, static_cast<uint2 *>(blocks), n_blocks);
-  return hipGetLastError();
+hipError_t launch_downsample(BlockOpCall call, hipStream_t stream) {
+  if (call.in.codec < ICAMD_DXT1 || call.in.codec > ICAMD_ETC1) return hipErrorInvalidValue;
+  call.in.quad = pad_border_quad();  // (the same A/B switch as the Pad border: ICAMD_PAD_BORDER_QUAD=0)
+  return launch_blockop(call, downsample_plan(call.in), stream);
+}
+
+hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint64_t n_blocks, hipStream_t stream) {
+  hipError_t err = hipSuccess;
+  for_chunks(n_blocks, kTranscodeChunk, [&](uint64_t first, uint64_t count) {
+    if (err != hipSuccess) return;
+    hipLaunchKernelGGL(icamd_dxt1_to_etc1_kernel, dim3((uint32_t)((count + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup)),
+                       dim3(kThreadsPerWorkgroup), 0, stream, static_cast<uint2 *>(blocks) + first, (uint32_t)count);
+    err = hipGetLastError();
+  });
+  return err;
 }
 
 // ---- CreateSolidImage / CopySubimage on device-resident block grids (helper.h:522-592) ----
@@ -360,7 +366,6 @@ struct FillParams {
   uint32_t words;  // 2 or 4
 };
 // n <= kFillBatch images of blocks_per_image blocks each, image i filled with its own block w[i] (icamd_create_solid_batch_device)
-constexpr uint32_t kFillBatch = 64;
 struct FillBatchParams {
   uint8_t *dst;
   uint64_t dst_image_stride;
@@ -414,10 +419,8 @@ hipError_t launch_fill_blocks(void *dst, uint64_t n_blocks, int block_bytes, con
   P.n_blocks = n_blocks;
   P.words = (uint32_t)block_bytes / 4u;
   for (int i = 0; i < 4; ++i) P.w[i] = words[i];
-  uint64_t wgs = (n_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup;
-  if (wgs > 256u * 64u) wgs = 256u * 64u;  // 8 waves on every SIMD several times over; the loop covers the rest
   (void)hipGetLastError();
-  hipLaunchKernelGGL(icamd_fill_blocks_kernel, dim3((uint32_t)wgs), dim3(kThreadsPerWorkgroup), 0, stream, P);
+  hipLaunchKernelGGL(icamd_fill_blocks_kernel, dim3(fill_workgroups(n_blocks)), dim3(kThreadsPerWorkgroup), 0, stream, P);
   return hipGetLastError();
 }
 
@@ -425,20 +428,18 @@ hipError_t launch_fill_blocks_batch(void *dst, uint64_t dst_image_stride, uint32
                                     const uint32_t (*words)[4], uint32_t n_images, hipStream_t stream) {
   if (blocks_per_image == 0 || n_images == 0) return hipSuccess;
   (void)hipGetLastError();
-  uint32_t wgs = (blocks_per_image + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup;
-  for (uint32_t first = 0; first < n_images; first += kFillBatch) {
+  for_chunks(n_images, kFillBatch, [&](uint64_t first, uint64_t count) {
     FillBatchParams P;
-    P.n = n_images - first < kFillBatch ? n_images - first : kFillBatch;
-    P.dst = static_cast<uint8_t *>(dst) + (uint64_t)first * dst_image_stride;
+    P.n = (uint32_t)count;
+    P.dst = static_cast<uint8_t *>(dst) + first * dst_image_stride;
     P.dst_image_stride = dst_image_stride;
     P.blocks_per_image = blocks_per_image;
     P.words = (uint32_t)block_bytes / 4u;
     for (uint32_t i = 0; i < P.n; ++i)
       for (int j = 0; j < 4; ++j) P.w[i][j] = words[first + i][j];
-    // ~8 waves on every SIMD over the whole launch; the loop covers the rest of an image
-    const uint32_t per_image = (256u * 32u + P.n - 1) / P.n;
-    hipLaunchKernelGGL(icamd_fill_blocks_batch_kernel, dim3(wgs < per_image ? wgs : per_image, P.n), dim3(kThreadsPerWorkgroup), 0, stream, P);
-  }
+    hipLaunchKernelGGL(icamd_fill_blocks_batch_kernel, dim3(fill_batch_workgroups(blocks_per_image, P.n), P.n),
+                       dim3(kThreadsPerWorkgroup), 0, stream, P);
+  });
   return hipGetLastError();
 }
 
@@ -454,17 +455,15 @@ hipError_t launch_copy_subimage(int block_bytes, const void *src, uint32_t src_c
   P.src_image_stride = src_image_stride;
   P.dst_image_stride = dst_image_stride;
   (void)hipGetLastError();
-  const uint32_t gx = (cols + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup;
-  for (uint32_t img0 = 0; img0 < n_images; img0 += 65535u) {
-    const uint32_t nz = n_images - img0 < 65535u ? n_images - img0 : 65535u;
-    P.src = static_cast<const uint8_t *>(src) + (uint64_t)img0 * src_image_stride;
-    P.dst = static_cast<uint8_t *>(dst) + (uint64_t)img0 * dst_image_stride;
-    for (uint32_t first = 0; first < rows; first += 65535u) {
-      P.row_first = first;
-      hipLaunchKernelGGL(icamd_copy_subimage_kernel, dim3(gx, rows - first < 65535u ? rows - first : 65535u, nz),
+  for_chunks(n_images, kGridLimitYZ, [&](uint64_t img0, uint64_t nz) {
+    P.src = static_cast<const uint8_t *>(src) + img0 * src_image_stride;
+    P.dst = static_cast<uint8_t *>(dst) + img0 * dst_image_stride;
+    for_chunks(rows, kGridLimitYZ, [&](uint64_t row0, uint64_t ny) {
+      P.row_first = (uint32_t)row0;
+      hipLaunchKernelGGL(icamd_copy_subimage_kernel, dim3(copy_subimage_grid_x(cols), (uint32_t)ny, (uint32_t)nz),
                          dim3(kThreadsPerWorkgroup), 0, stream, P);
-    }
-  }
+    });
+  });
   return hipGetLastError();
 }
 

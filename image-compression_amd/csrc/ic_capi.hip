@@ -335,33 +335,29 @@ int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t
   return ICAMD_OK;
 }
 
-// The compressed-domain batches (pad, downsample) once their arguments are checked: P holds the block grids, and
-// as many images go in one launch as the 32-bit block index allows.
-int blockop_batch(hipError_t (*launch)(int, const icamd::BlockOpParams &, hipStream_t), const char *what, int codec,
-                  icamd::BlockOpParams &P, int etc_strategy, uint32_t src_height, uint32_t src_width, uint32_t n_images,
-                  const void *d_blocks, size_t src_image_stride_bytes, void *d_out, size_t dst_image_stride_bytes,
-                  void *hip_stream) {
-  if (n_images == 0) return ICAMD_OK;  // (after the checks: a call the reference would refuse is refused for any count)
-  int rc = require_device();
+// The geometry checks of Pad and Downsample, for device and host buffers alike: false where the reference refuses.  Pad
+// (helper.h:393-404): the padded grid holds the image's, and the output is the padded image's size.
+bool pad_geometry_ok(int codec, uint32_t ch, uint32_t cw, uint32_t ph, uint32_t pw, size_t out_size) {
+  return num_blocks4(ph) >= num_blocks4(ch) && num_blocks4(pw) >= num_blocks4(cw) && out_size == icamd_encoded_size(codec, ph, pw);
+}
+// Downsample (helper.h:281-284, :340-341): grids of more than one block have an even number of them per side, a single block
+// is 1, 2 or 4 pixels per side (none of zero: the entry points' first check); the output is the halved image's size.
+bool downsample_geometry_ok(int codec, uint32_t uh, uint32_t uw, size_t out_size) {
+  const uint32_t r = num_blocks4(uh), c = num_blocks4(uw);
+  if ((r > 1 && r % 2) || (c > 1 && c % 2) || (r == 1 && c == 1 && (uh == 3 || uw == 3))) return false;
+  return out_size == icamd_encoded_size(codec, (uh + 1) / 2, (uw + 1) / 2);
+}
+
+// The compressed-domain batches (pad, downsample) once their arguments are checked: `in` holds the geometry; the launcher
+// plans the launches (blockops_plan.h) and groups the images.
+int blockop_batch(hipError_t (*launch)(icamd::BlockOpCall, hipStream_t), const char *what, const icamd::BlockOpIn &in,
+                  const void *d_blocks, size_t src_image_stride_bytes, void *d_out, size_t dst_image_stride_bytes, void *hip_stream) {
+  if (in.n_images == 0) return ICAMD_OK;  // (after the checks: a call the reference would refuse is refused for any count)
+  const int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  const uint64_t per = (uint64_t)P.out_rows * P.out_cols;
-  if (per >= (1ull << 31)) return fail(ICAMD_ERR_ARG, "more than 2^31 blocks in one image");
-  P.etc_strategy = (uint32_t)etc_strategy;
-  P.src_height = src_height; P.src_width = src_width;
-  P.div_out_cols = icamd::make_fastdiv(P.out_cols);
-  P.out_per_image = (uint32_t)per;
-  P.div_out_per_image = icamd::make_fastdiv(P.out_per_image);
-  P.src_image_stride = src_image_stride_bytes;
-  P.dst_image_stride = dst_image_stride_bytes;
-  const uint64_t group = std::max<uint64_t>(1, ((1ull << 31) - 1) / per);
-  for (uint64_t first = 0; first < n_images; first += group) {
-    const uint64_t count = std::min<uint64_t>(group, n_images - first);
-    P.src = static_cast<const uint8_t *>(d_blocks) + first * src_image_stride_bytes;
-    P.dst = static_cast<uint8_t *>(d_out) + first * dst_image_stride_bytes;
-    P.n_images = (uint32_t)count;
-    P.total_out = (uint32_t)(per * count);
-    ICAMD_HIP(launch(codec, P, static_cast<hipStream_t>(hip_stream)), what);
-  }
+  if (!icamd::blockop_image_fits(in.out_rows, in.out_cols)) return fail(ICAMD_ERR_ARG, "more than 2^31 blocks in one image");
+  ICAMD_HIP(launch({ in, static_cast<const uint8_t *>(d_blocks), static_cast<uint8_t *>(d_out), src_image_stride_bytes,
+                     dst_image_stride_bytes }, static_cast<hipStream_t>(hip_stream)), what);
   return ICAMD_OK;
 }
 
@@ -1004,17 +1000,14 @@ int icamd_pad_batch_device(int compressor, int etc_strategy, int format, uint32_
   if (!d_blocks || !d_out || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_out) | src_image_stride_bytes | dst_image_stride_bytes) % 4u)
     return fail(ICAMD_ERR_ARG, "block pointers and image strides must be 4-byte aligned");
-  icamd::BlockOpParams P;
-  P.in_rows = num_blocks4(ch); P.in_cols = num_blocks4(cw);
-  P.out_rows = num_blocks4(ph); P.out_cols = num_blocks4(pw);
-  if (P.in_rows == 0 || P.in_cols == 0 || P.out_rows < P.in_rows || P.out_cols < P.in_cols) return ICAMD_FALSE;
-  if (out_size_per_image != icamd_encoded_size(codec, ph, pw)) return ICAMD_FALSE;
+  if (ch == 0 || cw == 0 || !pad_geometry_ok(codec, ch, cw, ph, pw, out_size_per_image)) return ICAMD_FALSE;
   // (a non-zero stride is checked for one image too: a caller that passes one states how far its buffer reaches)
   if (((n_images > 1 || src_image_stride_bytes != 0) && src_image_stride_bytes < icamd_encoded_size(codec, ch, cw)) ||
       ((n_images > 1 || dst_image_stride_bytes != 0) && dst_image_stride_bytes < out_size_per_image))
     return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
-  return blockop_batch(icamd::launch_pad, "launch pad", codec, P, etc_strategy, ch, cw, n_images, d_blocks, src_image_stride_bytes,
-                       d_out, dst_image_stride_bytes, hip_stream);
+  const icamd::BlockOpIn in = { codec, (uint32_t)etc_strategy, num_blocks4(ch), num_blocks4(cw), num_blocks4(ph), num_blocks4(pw),
+                                ch, cw, n_images, false };
+  return blockop_batch(icamd::launch_pad, "launch pad", in, d_blocks, src_image_stride_bytes, d_out, dst_image_stride_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_pad_device(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, const void *d_blocks,
@@ -1029,21 +1022,16 @@ int icamd_downsample_batch_device(int compressor, int etc_strategy, int format, 
   if (!d_blocks || !d_out || uh == 0 || uw == 0 || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
   if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_out) | src_image_stride_bytes | dst_image_stride_bytes) % 4u)
     return fail(ICAMD_ERR_ARG, "block pointers and image strides must be 4-byte aligned");
-  icamd::BlockOpParams P;
-  P.in_rows = num_blocks4(uh); P.in_cols = num_blocks4(uw);
-  // helper.h:281-284, :340-341
-  if ((P.in_rows > 1 && P.in_rows % 2) || (P.in_cols > 1 && P.in_cols % 2)) return ICAMD_FALSE;
-  if (P.in_rows == 1 && P.in_cols == 1 && (uh == 3 || uw == 3)) return ICAMD_FALSE;
-  const uint32_t dh = (uh + 1) / 2, dw = (uw + 1) / 2;
-  P.out_rows = num_blocks4(dh); P.out_cols = num_blocks4(dw);
-  if (out_size_per_image != icamd_encoded_size(codec, dh, dw)) return ICAMD_FALSE;
+  if (!downsample_geometry_ok(codec, uh, uw, out_size_per_image)) return ICAMD_FALSE;
   // (a non-zero stride is checked for one image too: a caller that passes one states how far its buffer reaches)
   if ((n_images > 1 || src_image_stride_bytes != 0) && src_image_stride_bytes < icamd_encoded_size(codec, uh, uw))
     return fail(ICAMD_ERR_ARG, "source image stride smaller than an image");
   if ((n_images > 1 || dst_image_stride_bytes != 0) && dst_image_stride_bytes < out_size_per_image)
     return fail(ICAMD_ERR_ARG, "destination image stride smaller than an image");
-  return blockop_batch(icamd::launch_downsample, "launch downsample", codec, P, etc_strategy, uh, uw, n_images, d_blocks,
-                       src_image_stride_bytes, d_out, dst_image_stride_bytes, hip_stream);
+  const icamd::BlockOpIn in = { codec, (uint32_t)etc_strategy, num_blocks4(uh), num_blocks4(uw), num_blocks4((uh + 1) / 2),
+                                num_blocks4((uw + 1) / 2), uh, uw, n_images, false };
+  return blockop_batch(icamd::launch_downsample, "launch downsample", in, d_blocks, src_image_stride_bytes, d_out,
+                       dst_image_stride_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_downsample_device(int compressor, int etc_strategy, int format, uint32_t uh, uint32_t uw,
@@ -1057,12 +1045,7 @@ int icamd_transcode_dxt1_to_etc1_device(void *d_blocks, size_t n_bytes, void *hi
   if (n_bytes < 8) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  const size_t kChunk = (size_t)1 << 30;  // blocks per launch (32-bit block index in the kernel)
-  for (size_t first = 0; first < n_bytes / 8; first += kChunk) {
-    const size_t count = std::min(kChunk, n_bytes / 8 - first);
-    ICAMD_HIP(icamd::launch_transcode_dxt1_to_etc1(static_cast<uint8_t *>(d_blocks) + first * 8, (uint32_t)count,
-                                                   static_cast<hipStream_t>(hip_stream)), "launch transcode");
-  }
+  ICAMD_HIP(icamd::launch_transcode_dxt1_to_etc1(d_blocks, n_bytes / 8, static_cast<hipStream_t>(hip_stream)), "launch transcode");
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 
@@ -1070,8 +1053,7 @@ int icamd_pad(int compressor, int etc_strategy, int format, uint32_t ch, uint32_
               uint32_t ph, uint32_t pw, uint8_t *out, size_t out_size) try {
   int codec;
   if (!blocks || !out || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
-  if (num_blocks4(ph) < num_blocks4(ch) || num_blocks4(pw) < num_blocks4(cw)) return ICAMD_FALSE;
-  if (out_size != icamd_encoded_size(codec, ph, pw)) return ICAMD_FALSE;
+  if (!pad_geometry_ok(codec, ch, cw, ph, pw, out_size)) return ICAMD_FALSE;  // (an empty image is refused by the device entry)
   return staged_blockop(tls_staging(), blocks, icamd_encoded_size(codec, ch, cw), out, out_size, out_size, false,
                         [&](void *din, void *dout, hipStream_t s) {
                           return icamd_pad_device(compressor, etc_strategy, format, ch, cw, din, ph, pw, dout, out_size, s);
@@ -1082,9 +1064,7 @@ int icamd_downsample(int compressor, int etc_strategy, int format, uint32_t uh, 
                      uint8_t *out, size_t out_size) try {
   int codec;
   if (!blocks || !out || uh == 0 || uw == 0 || !resolve_codec(compressor, format, &codec)) return ICAMD_FALSE;
-  const uint32_t r = num_blocks4(uh), c = num_blocks4(uw);
-  if ((r > 1 && r % 2) || (c > 1 && c % 2) || (r == 1 && c == 1 && (uh == 3 || uw == 3))) return ICAMD_FALSE;
-  if (out_size != icamd_encoded_size(codec, (uh + 1) / 2, (uw + 1) / 2)) return ICAMD_FALSE;
+  if (!downsample_geometry_ok(codec, uh, uw, out_size)) return ICAMD_FALSE;
   return staged_blockop(tls_staging(), blocks, icamd_encoded_size(codec, uh, uw), out, out_size, out_size, false,
                         [&](void *din, void *dout, hipStream_t s) {
                           return icamd_downsample_device(compressor, etc_strategy, format, uh, uw, din, dout, out_size, s);

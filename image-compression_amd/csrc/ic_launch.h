@@ -1,5 +1,7 @@
 // ic_launch.h -- host-side launch entry points of the kernel translation units
-// (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip); called by ic_capi.hip.
+// (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip, blockops_kernels.hip); called by ic_capi.hip.
+// Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC) and blockops_plan.h (Pad, Downsample and
+// the chunks of CopySubimage, CreateSolid and the transcode); the launchers here run what a plan says.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -7,6 +9,7 @@
 
 #include <atomic>
 
+#include "blockops_plan.h"
 #include "ic_device.h"
 
 namespace icamd {
@@ -173,7 +176,8 @@ hipError_t launch_mip_filter_pass(int mode, int comps, int filter, const MipPara
 const char *mip_box_kernel_name(int mode, int comps);              // "" where launch_mip_pass has no kernel
 const char *mip_kernel_name(int mode, int comps, int filter);      // "" where launch_mip_filter_pass has no kernel
 
-// Compressed-domain operations on one image's block grid.
+// Compressed-domain operations on block grids.  BlockOpParams is what a kernel receives: launch_blockop
+// (blockops_kernels.hip) fills it, per launch, from the caller's BlockOpCall and the plan of blockops_plan.h.
 struct BlockOpParams {
   const uint8_t *src;
   uint8_t *dst;
@@ -192,9 +196,17 @@ struct BlockOpParams {
   uint32_t border_wgs = 0, border_lanes = 0, border_lanes_per_image = 0;
   FastDiv div_border_lanes_per_image = { 0, 0, 1 };
 };
-hipError_t launch_pad(int codec, const BlockOpParams &P, hipStream_t stream);
-hipError_t launch_downsample(int codec, const BlockOpParams &P, hipStream_t stream);
-hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint32_t n_blocks, hipStream_t stream);
+// A Pad / Downsample call: the geometry the plan is made from (in.quad is the launcher's), the first image's blocks and the
+// strides to the next ones in bytes.  Any number of images: the launcher groups them as the plan says.
+struct BlockOpCall {
+  BlockOpIn in;
+  const uint8_t *src;
+  uint8_t *dst;
+  uint64_t src_image_stride, dst_image_stride;
+};
+hipError_t launch_pad(BlockOpCall call, hipStream_t stream);
+hipError_t launch_downsample(BlockOpCall call, hipStream_t stream);
+hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint64_t n_blocks, hipStream_t stream);  // 8-byte blocks, in place
 // CreateSolidImage: `words` (block_bytes / 4 of them) replicated n_blocks times.  CopySubimage: rows x cols blocks
 // starting at block (r0, c0) of a grid src_cols blocks wide.
 hipError_t launch_fill_blocks(void *dst, uint64_t n_blocks, int block_bytes, const uint32_t words[4], hipStream_t stream);
