@@ -55,6 +55,7 @@ EXPORTS = [
 RCCL_UNIQUE_ID_BYTES = 128
 # mip filters (bits; include/ic_amd.h, "mip filters"): 0 is the box filter of the plain mip entry points
 MIP_FILTER_BOX, MIP_FILTER_SRGB, MIP_FILTER_ALPHA_WEIGHTED = 0, 1, 2
+MIP_FILTER_NORMAL = 4  # BC5 chains and the RG8 pyramid only; not combinable
 MIP_PYRAMID = -1  # `codec` of mip_kernel_name for the pixel pyramid
 CONTAINER_DDS, CONTAINER_KTX, CONTAINER_PKM, CONTAINER_PVR = 0, 1, 2, 3
 
@@ -725,8 +726,8 @@ def mip_level_shape(height, width, level):
 def encode_mips_device(codec, src, height, width, src_components, *, levels=None, swap_rb=False,
                        etc_strategy=ETC_SMALLER_ERROR, n_images=1, row_stride_bytes=None, src_image_stride_bytes=None,
                        dst_image_stride_bytes=None, out=None, workspace=None, stream=None, mip_filter=0):
-    """Fused mip-chain encode (icamd_encode_mips_device; with mip_filter -- MIP_FILTER_SRGB | MIP_FILTER_ALPHA_WEIGHTED -- other
-    than 0, icamd_encode_mips_filtered_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes).
+    """Fused mip-chain encode (icamd_encode_mips_device; with mip_filter -- MIP_FILTER_SRGB | MIP_FILTER_ALPHA_WEIGHTED, or
+    MIP_FILTER_NORMAL for BC5 -- other than 0, icamd_encode_mips_filtered_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes).
     Returns (flat, views): flat is [n_images, dst_image_stride] (device), views[l] = flat[:, offset[l]:offset[l + 1]], the
     blocks of level l.  The workspace is allocated here unless the caller passes one (a uint8 CUDA tensor of at least
     mip_workspace_size bytes).  No synchronisation."""

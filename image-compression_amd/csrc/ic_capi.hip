@@ -465,10 +465,17 @@ int mip_check_components(int codec, int comps, int swap_rb) {
   if (swap_rb && comps < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
   return ICAMD_OK;
 }
-// The filter rules of the filtered mip entry points (ICAMD_MIP_FILTER_*; codec may be icamd::kMipPyramidMode): colour only.
+// The filter rules of the filtered mip entry points (ICAMD_MIP_FILTER_*; codec may be icamd::kMipPyramidMode): the colour
+// filters for colour only, the normal-map filter for BC5 and the two-byte pyramid only.
 int mip_check_filter(int codec, int comps, int filter) {
+  if (filter == ICAMD_MIP_FILTER_NORMAL) {
+    if (codec == icamd::kMipPyramidMode)
+      return comps == 2 ? ICAMD_OK : fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_NORMAL: the pixel pyramid needs a 2-component (RG) source");
+    return codec == ICAMD_BC5 ? ICAMD_OK : fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_NORMAL applies to ICAMD_BC5 chains only");
+  }
   if (filter < 0 || filter > (ICAMD_MIP_FILTER_SRGB | ICAMD_MIP_FILTER_ALPHA_WEIGHTED))
-    return fail(ICAMD_ERR_ARG, "mip filter must be a combination of ICAMD_MIP_FILTER_SRGB and ICAMD_MIP_FILTER_ALPHA_WEIGHTED");
+    return fail(ICAMD_ERR_ARG, "mip filter must be a combination of ICAMD_MIP_FILTER_SRGB and ICAMD_MIP_FILTER_ALPHA_WEIGHTED, "
+                               "or ICAMD_MIP_FILTER_NORMAL alone");
   if (filter == ICAMD_MIP_FILTER_BOX) return ICAMD_OK;
   if (codec == ICAMD_BC4 || codec == ICAMD_BC5)
     return fail(ICAMD_ERR_ARG, "BC4 / BC5 hold data channels: only ICAMD_MIP_FILTER_BOX applies");
@@ -1491,6 +1498,7 @@ static int encode_mips(int codec, int etc_strategy, int src_components, int swap
                        uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
                        size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
                        size_t workspace_bytes, void *hip_stream) {
+  if (filter == ICAMD_MIP_FILTER_NORMAL && codec != ICAMD_BC5) return mip_check_filter(codec, src_components, filter);
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
@@ -1628,7 +1636,7 @@ int icamd_mip_pyramid_filtered_device(int src_components, int filter, uint32_t h
 } ICAMD_ABI_CATCH
 
 const char *icamd_mip_kernel_name(int codec, int src_components, int filter) {
-  if (filter < 0 || filter > 3) return "";
+  if (filter < 0 || filter > ICAMD_MIP_FILTER_NORMAL) return "";
   const bool pyramid = codec == ICAMD_MIP_PYRAMID || codec == ICAMD_ETC1;  // ETC1 chains: the pyramid kernel, then the ETC1 kernels
   if (!pyramid && !mip_codec(codec)) return "";
   if (codec == ICAMD_ETC1 && src_components != 3 && src_components != 4) return "";

@@ -171,9 +171,13 @@ constexpr int kMipPyramidMode = -1;  // `mode` of the pixel-pyramid kernels (no 
 // mode: ICAMD_DXT1 / DXT5 / BC4 / BC5 or kMipPyramidMode (ETC1 chains are the pyramid + the ETC1 kernels, ic_capi.hip)
 hipError_t launch_mip_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream);
 // The same pass with one of the ICAMD_MIP_FILTER_* filters (mip_filter_kernels.hip): DXT1 (3 / 4 components; 4 with the
-// alpha-weighted bit), DXT5 and kMipPyramidMode (likewise); filter 0 is launch_mip_pass.  hipErrorInvalidValue for the rest.
+// alpha-weighted bit), DXT5 and kMipPyramidMode (likewise); filter 0 is launch_mip_pass and ICAMD_MIP_FILTER_NORMAL is
+// launch_mip_normal_pass.  hipErrorInvalidValue for the rest.
 hipError_t launch_mip_filter_pass(int mode, int comps, int filter, const MipParams &P, uint32_t n_images, hipStream_t stream);
+// The same pass with ICAMD_MIP_FILTER_NORMAL (mip_normal_kernels.hip): ICAMD_BC5 (2..4 components) and kMipPyramidMode (2).
+hipError_t launch_mip_normal_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream);
 const char *mip_box_kernel_name(int mode, int comps);              // "" where launch_mip_pass has no kernel
+const char *mip_normal_kernel_name(int mode, int comps);           // "" where launch_mip_normal_pass has no kernel
 const char *mip_kernel_name(int mode, int comps, int filter);      // "" where launch_mip_filter_pass has no kernel
 
 // Compressed-domain operations on block grids.  BlockOpParams is what a kernel receives: launch_blockop

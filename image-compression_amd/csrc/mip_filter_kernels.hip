@@ -53,12 +53,14 @@ const FilterKernel *filter_kernel(int mode, int comps, int filter) {
 
 hipError_t launch_mip_filter_pass(int mode, int comps, int filter, const MipParams &P, uint32_t n_images, hipStream_t stream) {
   if (filter == 0) return launch_mip_pass(mode, comps, P, n_images, stream);
+  if (filter == kMipFilterNormal) return launch_mip_normal_pass(mode, comps, P, n_images, stream);
   const FilterKernel *k = filter_kernel(mode, comps, filter);
   return launch_mip_kernel(k ? k->kernel : nullptr, P, n_images, stream);
 }
 
 const char *mip_kernel_name(int mode, int comps, int filter) {
   if (filter == 0) return mip_box_kernel_name(mode, comps);
+  if (filter == kMipFilterNormal) return mip_normal_kernel_name(mode, comps);
   const FilterKernel *k = filter_kernel(mode, comps, filter);
   return k ? k->name : "";
 }

@@ -1,5 +1,6 @@
 // mip_pass.h -- the fused mip-chain pass (and the plain pixel pyramid) for gfx950 (include/ic_amd.h, mip-chain section), shared
-// by mip_kernels.hip (the box filter) and mip_filter_kernels.hip (the sRGB / alpha-weighted filters, mip_filter.h).
+// by mip_kernels.hip (the box filter), mip_filter_kernels.hip (the sRGB / alpha-weighted filters, mip_filter.h) and
+// mip_normal_kernels.hip (the normal-map filter, mip_normal.h).
 //
 // One pass reads an input level once and writes up to six (eight when the input is a single tile) levels of the chain:
 //  * a 256-lane workgroup owns a 128 x 128-pixel tile of the input level; a lane encodes four of its 32 x 32 blocks straight
@@ -16,7 +17,8 @@
 // 2j + 1 IS pixel min(4 bx + 2j + 1, w - 1).
 // The pixel pyramid entry is the same kernel with no encoder: it writes levels 1..6 as tight COMPS-byte rows.
 // A fused ETC1 kernel is deferred: ETC1 chains run the pyramid kernel + etc1_kernels.hip per level (ic_capi.hip).
-// FILTER != 0 adds the filter's tables to LDS (mip_filter_table_bytes), filled once per workgroup before the first round.
+// FILTER 1..3 adds the filter's tables to LDS (mip_filter_table_bytes), filled once per workgroup before the first round;
+// FILTER 4 (normals) has no tables.
 #ifndef ICAMD_MIP_PASS_H_
 #define ICAMD_MIP_PASS_H_
 
@@ -26,6 +28,7 @@
 #include "ic_amd.h"
 #include "ic_launch.h"
 #include "mip_filter.h"
+#include "mip_normal.h"
 
 namespace icamd {
 
@@ -132,7 +135,7 @@ __device__ __forceinline__ void mip_pass(const MipParams &P) {
   stash.base = &lds_stash[0][kDxt ? threadIdx.x : 0][0];
   const uint32_t tid = threadIdx.x, tx = blockIdx.x, ty = blockIdx.y + P.tile_row0;
   MipFilterTables ft = { nullptr, nullptr, nullptr };
-  if constexpr (FILTER != 0) {
+  if constexpr (mip_filter_table_bytes(FILTER) != 0) {
     // the filter's tables, one copy per workgroup (256 lanes: one entry of T and M, four of R each)
     if constexpr ((FILTER & kMipFilterSrgb) != 0) {
       __shared__ uint16_t lds_to_linear[256], lds_midpoint[256];
@@ -179,7 +182,8 @@ __device__ __forceinline__ void mip_pass(const MipParams &P) {
         for (uint32_t p = tid; p < (1u << (2u * lg)); p += kThreadsPerWorkgroup) {
           const uint32_t x = p & ((1u << lg) - 1u), y = p >> lg;
           const uint32_t *q = prev + 2u * y * sp + 2u * x;
-          lds[mip_lds_off(j) + p] = mip_filter_px<FILTER, COMPS>(q[0], q[sx], q[sy], q[sy + sx], ft);
+          if constexpr (FILTER == kMipFilterNormal) lds[mip_lds_off(j) + p] = mip_normal_px<COMPS>(q[0], q[sx], q[sy], q[sy + sx], swap);
+          else lds[mip_lds_off(j) + p] = mip_filter_px<FILTER, COMPS>(q[0], q[sx], q[sy], q[sy + sx], ft);
         }
         __syncthreads();
       }
@@ -218,8 +222,9 @@ __device__ __forceinline__ void mip_pass(const MipParams &P) {
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
               const int q = 8 * dy + 2 * dx;
-              lds[(2u * by + (uint32_t)dy) * 64u + 2u * bx + (uint32_t)dx] =
-                  mip_filter_px<FILTER, COMPS>(px[q], px[q + 1], px[q + 4], px[q + 5], ft);
+              uint32_t &next = lds[(2u * by + (uint32_t)dy) * 64u + 2u * bx + (uint32_t)dx];
+              if constexpr (FILTER == kMipFilterNormal) next = mip_normal_px<COMPS>(px[q], px[q + 1], px[q + 4], px[q + 5], swap);
+              else next = mip_filter_px<FILTER, COMPS>(px[q], px[q + 1], px[q + 4], px[q + 5], ft);
             }
         }
         out = dst + P.level_off[0] + ((uint64_t)(row >> 2) * bw0 + (col >> 2)) * kBlockBytes;

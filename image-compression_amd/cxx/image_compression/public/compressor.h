@@ -95,7 +95,9 @@ class Compressor {
 //                          1 .. floor(log2(max(height, width))) + 1     -> icamd_compress_mips
 //   CompressMipChainFiltered  the same with a mip filter (include/ic_amd.h, ICAMD_MIP_FILTER_*: 1 = average the light the
 //                          sRGB codes stand for, 2 = weight colour by alpha, 3 = both; 0 is CompressMipChain).  false also
-//                          for a filter outside 0 .. 3 and for the alpha-weighted filter with kRGB / kBGR
+//                          for a filter outside 0 .. 3 and for the alpha-weighted filter with kRGB / kBGR.  That includes
+//                          ICAMD_MIP_FILTER_NORMAL (4), the normal-map filter of BC5 chains: no Compressor + format pair
+//                          selects BC5 (use icamd_encode_mips_filtered_device)
 //                                                                        -> icamd_compress_mips_filtered
 //   MeasureErrorDevice     the error of the blocks Compress wrote for an image against that image's pixels, both device
 //                          resident: d_stats receives one icamd_error_stats record (include/ic_amd.h: per-channel sums of

@@ -420,9 +420,35 @@ int icamd_compress_mips(int compressor, int etc_strategy, int format, uint32_t h
  * on the filter.  A flat image stays flat under every filter, and a 0 / 255 checkerboard becomes 188 under SRGB (127 under
  * BOX).  Codecs: DXT1, DXT5, ETC1 (any strategy) and the pixel pyramid; a filter other than 0 needs src_components 3 or 4,
  * ALPHA_WEIGHTED 4.  ICAMD_ERR_ARG -- before a device is needed -- for BC4 / BC5 (data channels) with a filter other than 0,
- * a filter outside 0..3 and those component counts; every other rule, status and the workspace size (which does not depend
- * on the filter) as for the entry point without `_filtered`, which is the same call with filter 0. */
+ * a filter outside 0..3 (but see ICAMD_MIP_FILTER_NORMAL below) and those component counts; every other rule, status and the
+ * workspace size (which does not depend on the filter) as for the entry point without `_filtered`, which is the same call
+ * with filter 0.
+ *
+ * ---- normal-map mip filter (EXTENSION: ICAMD_MIP_FILTER_NORMAL = 4, on its own only: 5, 6 and 7 are ICAMD_ERR_ARG) ----
+ * For tangent-space normal maps in BC5: R and G hold x and y of a unit vector.  The box filter shortens the averaged vector
+ * and tilts it towards +z, so every lower mip is flatter than the surface it stands for; this filter sums the four vectors
+ * (z rebuilt from x and y) and brings the sum back to unit length.  Geometry, cascade, the four source pixels, the per-level
+ * encode and the packing are the mip-chain section's.  Integer arithmetic only; the result is exact.
+ * r_i, g_i: the R and G bytes of p_i by the ICAMD_BC5 rules (R is byte 0, or byte 2 with swap_rb; G is byte 1).
+ *   x_i = 2 r_i - 255,  y_i = 2 g_i - 255                      (unit length is 255)
+ *   rem_i = max(0, 65025 - x_i^2 - y_i^2)
+ *   z_i = (isqrt(4 rem_i) + 1) >> 1                            (the nearest integer to the root; isqrt is the floor root)
+ *   X = sum x_i,  Y = sum y_i,  Z = sum z_i,  N2 = X^2 + Y^2 + Z^2          (N2 <= 3 * 1020^2 < 2^22)
+ *   N2 == 0:  R' = (sum r_i) >> 2,  G' = (sum g_i) >> 2        (the box value, like A == 0 of the alpha-weighted filter)
+ *   else      Ls = isqrt(N2 << 8)                              (the length with 4 fraction bits; N2 << 8 < 2^30)
+ *             for V in (X, Y):  m = min(255, (4080 |V| + (Ls >> 1)) / Ls), integer division (the numerator is below 2^23);
+ *                               v = m with the sign of V;  the output code is (v + 256) >> 1.
+ * Every other byte of the pixel (B, A, or R's unused twin under swap_rb) is the truncating mean of filter 0, which keeps the
+ * hand-off image of chains longer than one pass, and 3- and 4-byte sources, defined.
+ * A flat image whose (x, y) is no longer than a unit vector stays flat; flat (255, 255), an over-long vector, becomes
+ * (218, 218); the quad (218,128) (218,128) (128,218) (128,218) -- two normals tilted 45 degrees towards +x, two towards +y --
+ * becomes (180, 180), the unit vector in that direction, where the box filter gives (173, 173).
+ * icamd_encode_mips_filtered_device: ICAMD_BC5 only, src_components 2..4, swap_rb only with 3 or 4; the workspace size is
+ * unchanged.  icamd_mip_pyramid_filtered_device: src_components == 2 only.  Every other codec or component count is
+ * ICAMD_ERR_ARG before a device is needed.  icamd_compress_mips_filtered and the C++ CompressMipChainFiltered refuse it
+ * (ICAMD_ERR_ARG): no Compressor + format pair selects BC5. */
 enum { ICAMD_MIP_FILTER_BOX = 0, ICAMD_MIP_FILTER_SRGB = 1, ICAMD_MIP_FILTER_ALPHA_WEIGHTED = 2 };  /* bits; 3 = both */
+enum { ICAMD_MIP_FILTER_NORMAL = 4 };  /* not a bit: valid alone */
 int icamd_encode_mips_filtered_device(int codec, int etc_strategy, int src_components, int swap_rb, int filter,
                                       uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
                                       uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,

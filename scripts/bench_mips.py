@@ -19,6 +19,11 @@ dxt5, etc1 and `pyramid` (icamd_mip_pyramid_filtered_device alone), with per leg
   (c)  unfused   level 0 through icamd_encode_device, the filtered pyramid, then icamd_encode_device per level (not for `pyramid`)
 and the ratios a / a0 and c / a.  Parity: image 0 of (a) against (c).
 
+--filter 4 (the normal-map filter, BC5 only) times the BC5 chain of a 16 x 4096^2 normal map from RG8 and from RGBA8 sources:
+the filtered call against the box call of the same build, after a warm-up of both, in interleaved repeats (normal, box, normal,
+box, ...).  Parity: image 0 of the RG8 chain against level 0 through icamd_encode_device + the filtered RG8 pyramid +
+icamd_encode_device per level, and the RGBA8 chain against the RG8 chain (BC5 reads R and G only).
+
   python scripts/bench_mips.py [--k 10] [--reps 5] [--legs dxt1,dxt5,etc1,bc4,bc5,etc1_1024,dxt1_16384] [--no-psnr] [--filter F]
 One JSON line per leg; exit status 1 if any parity check fails."""
 import argparse
@@ -135,6 +140,64 @@ def bench_filtered(a, dev):
     return ok
 
 
+def bench_normal(a, dev):
+    """--filter 4: BC5 from RG8 and RGBA8, normal against box interleaved; one JSON line per source layout."""
+    lib = pkg.lib()
+    codec, n, s, f = pkg.BC5, 16, 4096, pkg.MIP_FILTER_NORMAL
+    levels = pkg.mip_max_levels(s, s)
+    total, offs = pkg.mip_chain_size(codec, s, s)
+    rng = np.random.default_rng(1)
+    ang, tilt = rng.uniform(0, 2 * np.pi, (s, s)), rng.uniform(0, 1, (s, s))  # unit normals, z > 0, one code of noise
+    img = rng.integers(0, 256, (s, s, 4), dtype=np.uint8)
+    img[..., 0] = np.clip(np.rint(127.5 + 127.5 * tilt * np.cos(ang)) + rng.integers(-1, 2, (s, s)), 0, 255)
+    img[..., 1] = np.clip(np.rint(127.5 + 127.5 * tilt * np.sin(ang)) + rng.integers(-1, 2, (s, s)), 0, 255)
+    st = pkg._stream_handle()
+    chains = {}
+    ok = True
+    for comps in (2, 4):
+        src = torch.from_numpy(np.ascontiguousarray(img[..., :comps]).reshape(-1)).to(dev).repeat(n)
+        out = torch.empty((n, total), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(1, pkg.mip_workspace_size(codec, comps, s, s, levels, n)),), dtype=torch.uint8, device=dev)
+        fns = {"normal": lambda: pkg.encode_mips_device(codec, src, s, s, comps, n_images=n, out=out, workspace=ws, mip_filter=f),
+               "box": lambda: pkg.encode_mips_device(codec, src, s, s, comps, n_images=n, out=out, workspace=ws)}
+        for fn in fns.values():  # precondition: both code objects loaded, clocks and caches in their steady state
+            time_calls(fn, a.k, 1, a.warmup)
+        times = {"normal": [], "box": []}
+        for _ in range(a.reps):
+            for name in ("normal", "box"):
+                times[name] += time_calls(fns[name], a.k, 1, 0)
+        rec = {"leg": "bc5_rg8" if comps == 2 else "bc5_rgba8", "filter": f, "n_images": n, "size": s, "levels": levels,
+               "kernel": pkg.mip_kernel_name(codec, comps, f), "box_kernel": pkg.mip_kernel_name(codec, comps, 0), "lib": pkg.LIB_PATH}
+        for name, t in times.items():
+            rec[name + "_ms"] = round(statistics.median(t), 4)
+            rec[name + "_ms_min_max"] = [round(min(t), 4), round(max(t), 4)]
+        rec["normal_over_box"] = round(statistics.median(times["normal"]) / statistics.median(times["box"]), 3)
+        fns["normal"]()
+        torch.cuda.synchronize()
+        chains[comps] = out[0].clone()
+        if comps == 2:
+            pyr_per, poffs = pkg.mip_pyramid_size(2, s, s, levels)
+            pyr = torch.empty((1, pyr_per), dtype=torch.uint8, device=dev)
+            out_c = torch.empty((total,), dtype=torch.uint8, device=dev)
+            lib.icamd_encode_device(codec, 2, 2, 0, s, s, s, s, s * 2, 1, 0, 0, src.data_ptr(), out_c.data_ptr(), st)
+            lib.icamd_mip_pyramid_filtered_device(2, f, s, s, s * 2, levels, 1, 0, 0, src.data_ptr(), pyr.data_ptr(), st)
+            for l in range(1, levels):
+                lh, lw = pkg.mip_level_shape(s, s, l)
+                lib.icamd_encode_device(codec, 2, 2, 0, lh, lw, lh, lw, lw * 2, 1, 0, 0, pyr.data_ptr() + poffs[l - 1],
+                                        out_c.data_ptr() + offs[l], st)
+            torch.cuda.synchronize()
+            rec["parity_fused_vs_unfused"] = bool(torch.equal(chains[2], out_c))
+            ok &= rec["parity_fused_vs_unfused"]
+            del pyr, out_c
+        else:
+            rec["parity_rgba8_vs_rg8"] = bool(torch.equal(chains[4], chains[2]))
+            ok &= rec["parity_rgba8_vs_rg8"]
+        print(json.dumps(rec), flush=True)
+        del src, out, ws
+        torch.cuda.empty_cache()
+    return ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, default=10)
@@ -142,10 +205,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--no-psnr", action="store_true")
-    ap.add_argument("--filter", type=int, default=0, choices=[0, 1, 2, 3])
+    ap.add_argument("--filter", type=int, default=0, choices=[0, 1, 2, 3, 4])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if a.filter == pkg.MIP_FILTER_NORMAL:
+        return 0 if bench_normal(a, dev) else 1
     if a.filter:
         return 0 if bench_filtered(a, dev) else 1
     lib = pkg.lib()

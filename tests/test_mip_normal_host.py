@@ -1,0 +1,390 @@
+"""CPU tier of the normal-map mip filter (include/ic_amd.h, "normal-map mip filter"; ICAMD_MIP_FILTER_NORMAL):
+* the numpy restatement (tests/normal_filter_oracle.py) against a literal per-pixel loop, and the named properties of the
+  definition as literal values;
+* the filter math of csrc/mip_normal.h compiled for the host (tests/host_emul/mip_normal_emul.cc) against that oracle,
+  exhaustively where the domain is small, with the floating-point first guess and with the guess forced one off either way;
+* every argument rule of the filtered entry points, answered before a device is needed, and a loud error without a GPU;
+* the four kernels compile for gfx950 with zero scratch and the LDS of their box twins;
+* the images of the GPU tier hold the cases of the definition."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import bc45_oracle as B
+import ic_testlib as T
+import mips_oracle as M
+import normal_filter_oracle as N
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(T.ROOT, "image-compression_amd", "csrc")
+OK, FALSE, ERR_NO_DEVICE, ERR_ARG = 0, 1, -1, -4
+NORMAL = 4
+BIASES = (0, -1, 1)
+N2_MAX = 3 * 1020 * 1020
+
+
+@pytest.fixture(scope="module")
+def pkg():
+    import ic_amd_loader
+    return ic_amd_loader.load_package()
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("mip_normal") / "libmip_normal_emul.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DICAMD_HOST_EMULATION", "-I" + CSRC, "-o", so,
+                           os.path.join(HERE, "host_emul", "mip_normal_emul.cc")])
+    L = ctypes.CDLL(so)
+    L.mip_normal_emul_z.restype = None
+    L.mip_normal_emul_z.argtypes = [T.ci, T.vp, T.vp, T.u32, T.vp]
+    L.mip_normal_emul_length.restype = None
+    L.mip_normal_emul_length.argtypes = [T.ci, T.u32, T.u32, T.vp]
+    L.mip_normal_emul_code.restype = None
+    L.mip_normal_emul_code.argtypes = [T.ci, T.vp, T.vp, T.u32, T.vp]
+    L.mip_normal_emul_quads.restype = ctypes.c_int
+    L.mip_normal_emul_quads.argtypes = [T.ci, T.ci, T.ci, T.vp, T.u32, T.vp]
+    return L
+
+
+# ---- the oracle
+
+@pytest.mark.parametrize("h,w", [(1, 1), (1, 9), (9, 1), (2, 3), (5, 5), (7, 13), (17, 2), (33, 31)])
+def test_numpy_filter_matches_the_literal_rule(h, w):
+    """The odd and thin shapes of tests/test_mips_host.py, every level of the cascade."""
+    for c in (2, 3, 4):
+        for swap in (0, 1):
+            p = N.normal_image(h, w, c, swap, index=h * 100 + w) if (h + w) % 2 else \
+                np.random.default_rng(h * 100 + w).integers(0, 256, (h, w, c), dtype=np.uint8)
+            levels = N.pyramid(p, swap)
+            assert len(levels) == M.max_levels(h, w)
+            for l in range(1, len(levels)):
+                assert levels[l].shape[:2] == M.level_shape(h, w, l)
+                assert np.array_equal(levels[l], N.next_level_literal(levels[l - 1], swap)), (h, w, c, swap, l)
+
+
+def _one(q, swap=0):
+    return N.next_level(N.rg_quad(q), swap)[0, 0].tolist()
+
+
+def _box(q):
+    return M.next_level(N.rg_quad(q))[0, 0].tolist()
+
+
+def test_named_properties_of_the_definition():
+    # flat stays flat: every (r, g) no longer than a unit vector, as a flat quad
+    r, g = np.meshgrid(np.arange(256), np.arange(256), indexing="ij")
+    x, y = 2 * r - 255, 2 * g - 255
+    inside = x * x + y * y <= 65025
+    assert int(inside.sum()) == 51040
+    flat = np.stack([r[inside], g[inside]], axis=-1).astype(np.uint8)
+    assert np.array_equal(N.filter_quads(flat, flat, flat, flat), flat)
+    # ... which needs the rounded z: with the floored root 12 of them move (by one code)
+    xs, ys = x[inside], y[inside]
+    zf = N.isqrt(65025 - xs * xs - ys * ys)
+    Ls = N.isqrt((16 * xs * xs + 16 * ys * ys + 16 * zf * zf) << 8)
+    moved = np.zeros(xs.shape, bool)
+    for V, code in ((4 * xs, flat[:, 0]), (4 * ys, flat[:, 1])):
+        v = np.sign(V) * np.minimum(255, N.unclamped_m(V, Ls))
+        assert (np.abs(((v + 256) >> 1) - code) <= 1).all()
+        moved |= ((v + 256) >> 1) != code
+    assert int(moved.sum()) == 12
+    # over-long vectors are renormalised
+    assert _one([(255, 255)] * 4) == [218, 218]
+    # the quad of the header: two normals tilted 45 degrees towards +x, two towards +y
+    q = [(218, 128), (218, 128), (128, 218), (128, 218)]
+    assert _one(q) == [180, 180] and _box(q) == [173, 173]
+    # one tilted texel among three flat ones
+    q = [(255, 128), (128, 128), (128, 128), (128, 128)]
+    assert _one(q) == [168, 128] and _box(q) == [159, 128]
+    # an arbitrary quad
+    q = [(200, 60), (10, 250), (128, 128), (90, 30)]
+    assert _one(q) == [92, 110] and _box(q) == [107, 117]
+    # N2 == 0 occurs: the box value
+    for q in ([(255, 255), (0, 0), (255, 0), (0, 255)], [(255, 128), (0, 127), (255, 128), (0, 127)]):
+        assert N.quad_cases(N.rg_quad(q))[0] == 1
+        assert _one(q) == _box(q) == [127, 127]
+    # a symmetric pair is centred
+    q = [(218, 128), (37, 128), (218, 128), (37, 128)]
+    assert _one(q) == [128, 128] and _box(q) == [127, 128]
+    # R is byte 2 under swap_rb; the other bytes are the truncating mean
+    p = np.array([[[7, 128, 218, 9], [2, 128, 218, 250]], [[1, 218, 128, 3], [0, 218, 128, 4]]], np.uint8)
+    assert N.next_level(p, 1)[0, 0].tolist() == [2, 180, 180, 66]
+    assert N.next_level(p[..., :3], 1)[0, 0].tolist() == [2, 180, 180]
+
+
+def test_the_clamp_never_fires():
+    """min(255, m) stays in the definition; over 300 000 random quads, the planted kinds and every flat quad the unclamped m
+    is at most 255 -- the largest value seen is asserted to be exactly 255, so a change that makes the clamp fire shows here."""
+    rng = np.random.default_rng(77)
+    quads = rng.integers(0, 256, (4, 300000, 2), dtype=np.uint8)
+    _, worst = N.filter_quads(*quads, return_unclamped=True)
+    r, g = np.meshgrid(np.arange(256), np.arange(256), indexing="ij")
+    flat = np.stack([r.ravel(), g.ravel()], axis=-1).astype(np.uint8)
+    _, worst_flat = N.filter_quads(flat, flat, flat, flat, return_unclamped=True)
+    extremes = rng.choice([0, 1, 127, 128, 254, 255], (4, 100000, 2)).astype(np.uint8)
+    _, worst_extreme = N.filter_quads(*extremes, return_unclamped=True)
+    print("largest unclamped m: random %d, flat %d, extremes %d" % (worst, worst_flat, worst_extreme))
+    assert max(worst, worst_flat, worst_extreme) == 255
+
+
+def test_every_gpu_test_image_holds_the_cases_of_the_definition():
+    """An N2 == 0 quad, a quad with a clamped rem, a flat unit quad and a general quad occur among the level-1 quads of every
+    image the GPU tier uses (N.GPU_TEST_IMAGES, the list N.gpu_image serves it from).  5 x 3 has two quads: each image holds
+    two of the cases and its indices hold all four.  The only quad of a 1 x 1 image is four copies of its texel, and x = 2r - 255
+    is odd, so neither N2 == 0 nor a general quad can occur there: its indices hold the other two."""
+    small = {}
+    for h, w, comps, swap, index in sorted(set(N.GPU_TEST_IMAGES)):
+        cases = N.quad_cases(N.normal_image(h, w, comps, swap, index), swap)
+        quads = max(1, h >> 1) * max(1, w >> 1)
+        if quads >= 4:
+            assert all(cases), (h, w, comps, swap, index, cases)
+        else:
+            assert sum(1 for c in cases if c) >= quads, (h, w, index, cases)
+            small[(h, w)] = small.get((h, w), np.zeros(4, np.int64)) + np.array(cases)
+    assert sorted(small) == [(1, 1), (5, 3)]
+    assert (small[(5, 3)] > 0).all(), small
+    assert (small[(1, 1)] > 0).tolist() == [False, True, True, False], small
+
+
+# ---- csrc/mip_normal.h on the host
+
+@pytest.mark.parametrize("bias", BIASES)
+def test_emulated_z_for_every_texel(emul, bias):
+    r, g = [a.ravel().astype(np.uint8) for a in np.meshgrid(np.arange(256), np.arange(256), indexing="ij")]
+    out = np.zeros(65536, np.uint32)
+    emul.mip_normal_emul_z(bias, r.ctypes.data, g.ctypes.data, 65536, out.ctypes.data)
+    assert np.array_equal(out, N.z_of(r, g))
+
+
+@pytest.mark.parametrize("bias", BIASES)
+def test_emulated_length_for_every_n2(emul, bias):
+    out = np.zeros(N2_MAX + 1, np.uint32)
+    emul.mip_normal_emul_length(bias, 0, out.size, out.ctypes.data)
+    assert np.array_equal(out, N.isqrt(np.arange(N2_MAX + 1, dtype=np.int64) << 8))
+
+
+@pytest.mark.parametrize("bias", BIASES)
+def test_emulated_quotient_for_every_length(emul, bias):
+    """Every Ls that occurs (N2 = 1 .. 3 * 1020^2) with |V| = 0, 1, the length itself (Ls / 16 rounded), 1020 and random
+    values, both signs."""
+    rng = np.random.default_rng(9)
+    lengths = np.unique(N.isqrt(np.arange(1, N2_MAX + 1, dtype=np.int64) << 8))
+    assert lengths[0] == 16 and lengths[-1] == N.isqrt(N2_MAX << 8)
+    Ls = np.repeat(lengths, 8)
+    V = np.zeros(Ls.size, np.int64)
+    V[1::8] = 1
+    V[2::8] = (Ls[2::8] + 8) >> 4
+    V[3::8] = 1020
+    V[4::8] = -((Ls[4::8] + 8) >> 4)
+    V[5::8] = -1020
+    V[6::8] = rng.integers(-1020, 1021, V[6::8].size)
+    V[7::8] = rng.integers(0, 2, V[7::8].size) * 2 - 1
+    V[7::8] *= np.minimum(1020, rng.integers(0, (Ls[7::8] >> 4) + 2))  # up to just past the length
+    out = np.zeros(Ls.size, np.uint32)
+    V32, Ls32 = V.astype(np.int32), Ls.astype(np.uint32)
+    emul.mip_normal_emul_code(bias, V32.ctypes.data, Ls32.ctypes.data, Ls.size, out.ctypes.data)
+    want = (np.sign(V) * np.minimum(255, N.unclamped_m(V, Ls)) + 256) >> 1
+    assert np.array_equal(out, want)
+
+
+def _pack(p):
+    p = np.asarray(p, np.uint32)
+    v = p[..., 0] | p[..., 1] << 8
+    if p.shape[-1] >= 3:
+        v = v | p[..., 2] << 16
+    return (v | p[..., 3] << 24) if p.shape[-1] == 4 else v
+
+
+def _planted_quads(comps, swap, rng, n=48000):
+    """n quads (n, 4, comps): random bytes, then 4000 of each planted kind."""
+    rc = N.r_channel(comps, swap)
+    quads = rng.integers(0, 256, (n, 4, comps), dtype=np.uint8)
+
+    def plant(first, rg):
+        quads[first:first + rg.shape[0], :, rc] = rg[..., 0]
+        quads[first:first + rg.shape[0], :, 1] = rg[..., 1]
+
+    k = 4000
+    # N2 == 0: the two quads of the header in every order of their texels, and with r and g exchanged
+    zero = np.array([[(255, 255), (0, 0), (255, 0), (0, 255)], [(255, 128), (0, 127), (255, 128), (0, 127)]], np.uint8)
+    zero = zero[rng.integers(0, 2, k)][np.arange(k)[:, None], np.argsort(rng.random((k, 4)), axis=1)]
+    plant(0, np.where(rng.integers(0, 2, (k, 1, 1)) == 1, zero[..., ::-1], zero))
+    # all rem_i == 0: both components in the outer 20 codes
+    far = rng.integers(0, 21, (2 * k, 4, 2))
+    far = np.where(rng.integers(0, 2, far.shape) == 1, 255 - far, far).astype(np.uint8)
+    plant(k, far[:k])
+    # a single texel with rem > 0
+    one = far[k:].copy()
+    one[np.arange(k), rng.integers(0, 4, k)] = rng.integers(100, 156, (k, 2))
+    plant(2 * k, one)
+    # flat unit quads: one texel no longer than a unit vector, four times
+    ang, tilt = rng.uniform(0, 2 * np.pi, k), rng.uniform(0, 1, k)
+    t = np.stack([np.floor(128 + 126 * tilt * np.cos(ang)), np.floor(128 + 126 * tilt * np.sin(ang))], -1).astype(np.uint8)
+    plant(3 * k, np.repeat(t[:, None], 4, axis=1))
+    # near-cancelling quads, N2 in 1..16: opposite pairs of over-long texels (z = 0) with one or two codes of imbalance
+    a = far[:k, 0].astype(np.int64)
+    near = np.stack([a, 255 - a, a[:, ::-1], 255 - a[:, ::-1]], axis=1)
+    step = np.zeros((k, 4, 2), np.int64)
+    step[np.arange(k), rng.integers(0, 4, k), rng.integers(0, 2, k)] = (rng.integers(0, 2, k) * 2 - 1) * rng.integers(1, 3, k)
+    near = near + step
+    near = np.where((near < 0) | (near > 255), near - 2 * step, near).astype(np.uint8)
+    plant(4 * k, near)
+    return quads
+
+
+@pytest.mark.parametrize("comps,swap", [(2, 0), (3, 0), (3, 1), (4, 0), (4, 1)])
+def test_emulated_four_pixel_rule(emul, comps, swap):
+    rng = np.random.default_rng(10 * comps + swap)
+    quads = _planted_quads(comps, swap, rng)
+    n = quads.shape[0]
+    k = 4000
+    rgq = np.stack([quads[..., N.r_channel(comps, swap)], quads[..., 1]], axis=-1)
+    # the planted kinds are what they claim to be
+    xs, ys = 2 * rgq[..., 0].astype(np.int64) - 255, 2 * rgq[..., 1].astype(np.int64) - 255
+    zs = N.z_of(rgq[..., 0], rgq[..., 1])
+    n2 = xs.sum(1) ** 2 + ys.sum(1) ** 2 + zs.sum(1) ** 2
+    rem_pos = (xs * xs + ys * ys < 65025).sum(1)
+    assert (n2[:k] == 0).all() and (rem_pos[k:2 * k] == 0).all() and (rem_pos[2 * k:3 * k] == 1).all()
+    assert (xs * xs + ys * ys <= 65025)[3 * k:4 * k].all() and (rgq[3 * k:4 * k] == rgq[3 * k:4 * k, :1]).all()
+    assert sorted(set(n2[4 * k:5 * k].tolist())) == [4, 16]
+    packed = np.ascontiguousarray(_pack(quads), np.uint32)
+    if comps == 3:  # byte 3 of a 3-byte pixel is undefined on input: the result must not depend on it
+        packed |= rng.integers(0, 256, packed.shape).astype(np.uint32) << 24
+    want = _pack(N.filter_quads(quads[:, 0], quads[:, 1], quads[:, 2], quads[:, 3], swap))
+    mask = np.uint32({2: 0x0000ffff, 3: 0x00ffffff, 4: 0xffffffff}[comps])
+    for bias in BIASES:
+        out = np.zeros(n, np.uint32)
+        assert emul.mip_normal_emul_quads(bias, comps, swap, packed.ctypes.data, n, out.ctypes.data) == 1
+        assert np.array_equal(out & mask, want), bias
+    assert emul.mip_normal_emul_quads(0, 1, 0, packed.ctypes.data, 1, out.ctypes.data) == 0
+
+
+# ---- argument rules (answered before any device work)
+
+def _enc(lib, codec=B.BC5, comps=2, swap=0, mip_filter=NORMAL, h=64, w=64, levels=7, n=1, src=16, dst=16, ws=None, ws_bytes=0):
+    return lib.icamd_encode_mips_filtered_device(codec, 2, comps, swap, mip_filter, h, w, w * comps, levels, n, 0, 0, src, dst,
+                                                 ws, ws_bytes, None)
+
+
+def _pyr(lib, comps=2, mip_filter=NORMAL, h=8, w=8, levels=2, n=1, src=16, dst=16):
+    return lib.icamd_mip_pyramid_filtered_device(comps, mip_filter, h, w, w * comps, levels, n, 0, 0, src, dst, None)
+
+
+ACCEPTED = [(2, 0), (3, 0), (3, 1), (4, 0), (4, 1)]
+
+
+def test_accepted_forms_pass_every_argument_check(pkg):
+    """With n_images == 0 a call that passes every check returns ICAMD_OK without touching a device or its pointers."""
+    lib = pkg.lib()
+    for comps, swap in ACCEPTED:
+        assert _enc(lib, comps=comps, swap=swap, n=0) == OK, (comps, swap)
+    assert _pyr(lib, n=0) == OK
+    # the workspace size does not depend on the filter: a chain that needs one is refused without it, accepted with it
+    need = lib.icamd_mip_workspace_size(B.BC5, 2, 256, 256, 9, 1)
+    assert need == 4 * 4 * 2
+    assert _enc(lib, h=256, w=256, levels=9, n=0) == OK
+    assert _enc(lib, h=256, w=256, levels=9, ws=64, ws_bytes=need - 1) == ERR_ARG
+    assert _enc(lib, h=256, w=256, levels=9) == ERR_ARG
+    assert b"workspace" in lib.icamd_last_error()
+    assert pkg.MIP_FILTER_NORMAL == NORMAL
+
+
+def test_normal_filter_is_refused_where_it_does_not_apply(pkg):
+    lib = pkg.lib()
+
+    def refused(rc):
+        assert rc == ERR_ARG
+        assert b"NORMAL" in lib.icamd_last_error()
+
+    for codec in (T.DXT1, T.DXT5, T.ETC1, B.BC4, T.PVRTC2, T.PVRTC4):
+        for comps in (3, 4):
+            refused(_enc(lib, codec=codec, comps=comps))
+    refused(_enc(lib, codec=B.BC4, comps=2))
+    refused(_enc(lib, codec=B.BC4, comps=1))
+    for comps in (1, 3, 4):
+        refused(_pyr(lib, comps=comps))
+    for f in (5, 6, 7):  # NORMAL is valid on its own only
+        assert _enc(lib, mip_filter=f) == ERR_ARG and _pyr(lib, mip_filter=f) == ERR_ARG
+        assert b"NORMAL" in lib.icamd_last_error()
+    for f in (-1, 8, 256):
+        assert _enc(lib, mip_filter=f) == ERR_ARG and _pyr(lib, mip_filter=f) == ERR_ARG
+    # the BC5 source rules hold under the filter
+    assert _enc(lib, comps=1) == ERR_ARG
+    assert _enc(lib, comps=2, swap=1) == ERR_ARG
+    assert _enc(lib, levels=8) == ERR_ARG and _enc(lib, levels=0) == ERR_ARG
+    assert _enc(lib, src=None) == FALSE and _enc(lib, dst=None) == FALSE and _enc(lib, h=0) == FALSE
+    assert _pyr(lib, src=None) == FALSE and _pyr(lib, w=0) == FALSE
+    # filters 1..3 stay refused on BC4 / BC5 and on the two-byte pyramid
+    for f in (1, 2, 3):
+        assert _enc(lib, mip_filter=f, comps=4) == ERR_ARG and _enc(lib, codec=B.BC4, mip_filter=f, comps=4) == ERR_ARG
+        assert _pyr(lib, mip_filter=f) == ERR_ARG
+    # the host form: no Compressor + format pair selects BC5
+    buf = np.zeros(64 * 64 * 4, np.uint8)
+    out = np.zeros(1 << 16, np.uint8)
+    cm = lib.icamd_compress_mips_filtered
+    for compressor, fmt, codec in [(T.DXTC, T.RGBA, T.DXT5), (T.DXTC, T.RGB, T.DXT1), (T.ETC, T.RGB, T.ETC1)]:
+        size = M.chain_offsets(codec, 64, 64, 7)[-1]
+        refused(cm(compressor, 2, fmt, NORMAL, 64, 64, 0, 7, buf.ctypes.data, out.ctypes.data, size))
+    assert cm(T.PVRTC, 2, T.RGBA, NORMAL, 64, 64, 0, 7, buf.ctypes.data, out.ctypes.data, 1024) == ERR_ARG
+    with pytest.raises(pkg.BackendError):
+        pkg.compress_mips_host(T.DXTC, T.RGBA, buf, 64, 64, mip_filter=pkg.MIP_FILTER_NORMAL)
+
+
+def test_kernel_name_table(pkg):
+    assert pkg.mip_kernel_name(B.BC5, 2, NORMAL) == "icamd_nmip_bc5_rg8_kernel"
+    assert pkg.mip_kernel_name(B.BC5, 3, NORMAL) == "icamd_nmip_bc5_rgb888_kernel"
+    assert pkg.mip_kernel_name(B.BC5, 4, NORMAL) == "icamd_nmip_bc5_rgba8_kernel"
+    assert pkg.mip_kernel_name(pkg.MIP_PYRAMID, 2, NORMAL) == "icamd_nmip_pyramid_rg8_kernel"
+    for codec in (T.DXT1, T.DXT5, T.ETC1, B.BC4, T.PVRTC2, T.PVRTC4, B.BC5, pkg.MIP_PYRAMID, 99):
+        for comps in range(0, 6):
+            if (codec == B.BC5 and comps in (2, 3, 4)) or (codec == pkg.MIP_PYRAMID and comps == 2):
+                continue
+            assert pkg.mip_kernel_name(codec, comps, NORMAL) == "", (codec, comps)
+    for f in (5, 6, 7, 8):
+        assert pkg.mip_kernel_name(B.BC5, 2, f) == "" and pkg.mip_kernel_name(pkg.MIP_PYRAMID, 2, f) == ""
+    assert pkg.mip_kernel_name(B.BC5, 2, 0) == "icamd_mip_bc5_rg8_kernel"  # filter 0 is the box kernel still
+
+
+def test_no_gpu_means_a_loud_error_not_a_cpu_result(pkg):
+    lib = pkg.lib()
+    if lib.icamd_device_count() > 0:
+        pytest.skip("a HIP device is present: the GPU tier covers this path")
+    for comps, swap in ACCEPTED:
+        assert _enc(lib, comps=comps, swap=swap) == ERR_NO_DEVICE, (comps, swap)
+        assert lib.icamd_last_error().decode()
+    assert _pyr(lib) == ERR_NO_DEVICE
+
+
+# ---- build check: exactly the four kernels, zero scratch, the LDS of the box twins
+
+def _kernel_metas(tmp_path, source):
+    out = os.path.join(str(tmp_path), source + ".s")
+    subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(T.ROOT, "include"),
+                           "-I" + CSRC, "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, source)],
+                          stderr=subprocess.DEVNULL)
+    metas = {}
+    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", open(out).read(), re.S):
+        blk = m.group(0)
+        metas[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)),
+                                                             int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk).group(1)))
+    return metas
+
+
+def test_normal_mip_kernels_use_no_scratch_and_the_lds_of_their_box_twins(tmp_path):
+    if not shutil.which("hipcc"):
+        pytest.skip("hipcc not available")
+    normal = _kernel_metas(tmp_path, "mip_normal_kernels.hip")
+    box = _kernel_metas(tmp_path, "mip_kernels.hip")
+    twins = {"icamd_nmip_bc5_rg8_kernel": "icamd_mip_bc5_rg8_kernel", "icamd_nmip_bc5_rgb888_kernel": "icamd_mip_bc5_rgb888_kernel",
+             "icamd_nmip_bc5_rgba8_kernel": "icamd_mip_bc5_rgba8_kernel", "icamd_nmip_pyramid_rg8_kernel": "icamd_mip_pyramid_rg8_kernel"}
+    assert sorted(normal) == sorted(twins)  # exactly the four kernels, and no box or fmip kernel beside them
+    for name, twin in twins.items():
+        scratch, lds = normal[name]
+        assert scratch == 0, "%s uses %d bytes of scratch" % (name, scratch)
+        assert lds == box[twin][1] and lds > 0, (name, lds, box[twin])
+    assert "mip_normal_kernels.hip" in open(os.path.join(T.ROOT, "image-compression_amd", "Makefile")).read()
