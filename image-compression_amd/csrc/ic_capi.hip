@@ -412,53 +412,9 @@ int run_workers(const char *entry, int n_devices, uint32_t n_images, int *status
 }
 
 
-// ---- mip chains (EXTENSION, include/ic_amd.h): pass planning shared by the fused encode and the pixel pyramid ----
-uint32_t mip_dim(uint32_t v, uint32_t l) { return l >= 32u ? 1u : std::max(1u, v >> l); }
-uint32_t mip_max_levels(uint32_t h, uint32_t w) {
-  if (h == 0 || w == 0) return 0;
-  uint32_t m = std::max(h, w), l = 0;
-  while (m >>= 1) ++l;
-  return l + 1u;
-}
-bool mip_codec(int codec) {
-  return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_BC4 || codec == ICAMD_BC5;
-}
-// One kernel launch: levels [l0, l0 + n) of the chain from level l0's pixels.  A pass over more than one 128 x 128 tile
-// reaches local level 5 in blocks (6 with pixels only); `handoff`: further levels follow, from level l0 + 6's pixels.
-struct MipPass {
-  uint32_t l0, n, in_h, in_w;
-  bool handoff;
-};
-std::vector<MipPass> mip_plan(uint32_t h, uint32_t w, uint32_t levels, bool pyramid) {
-  std::vector<MipPass> plan;
-  for (uint32_t l0 = 0;; l0 += 6u) {
-    MipPass p;
-    p.l0 = l0;
-    p.in_h = mip_dim(h, l0);
-    p.in_w = mip_dim(w, l0);
-    const bool single = p.in_h <= 128u && p.in_w <= 128u;
-    p.n = single ? levels - l0 : std::min(levels - l0, pyramid ? 7u : 6u);
-    p.handoff = l0 + p.n < levels;
-    plan.push_back(p);
-    if (!p.handoff) break;
-  }
-  return plan;
-}
-// bytes of one image's handoff image at level l (COMPS bytes per pixel)
-size_t mip_level_pixels(uint32_t h, uint32_t w, uint32_t l, int comps) { return (size_t)mip_dim(h, l) * mip_dim(w, l) * (size_t)comps; }
-// one image's pixel pyramid (levels 1 .. levels-1, tight rows, back to back)
-size_t mip_pyramid_bytes(uint32_t h, uint32_t w, uint32_t levels, int comps) {
-  size_t total = 0;
-  for (uint32_t l = 1; l < levels; ++l) total += mip_level_pixels(h, w, l, comps);
-  return total;
-}
-size_t mip_workspace_bytes(int codec, uint32_t h, uint32_t w, uint32_t levels, int comps, uint32_t n_images) {
-  if (codec == ICAMD_ETC1) return mip_pyramid_bytes(h, w, levels, comps) * n_images;  // the pyramid, then the ETC1 kernels
-  size_t total = 0;
-  for (const MipPass &p : mip_plan(h, w, levels, false))
-    if (p.handoff) total += mip_level_pixels(h, w, p.l0 + 6u, comps) * n_images;
-  return total;
-}
+// ---- mip chains (EXTENSION, include/ic_amd.h): what a call launches is mip_plan.h's; here are the argument checks ----
+using icamd::mip_codec;
+using icamd::mip_max_levels;
 int mip_check_components(int codec, int comps, int swap_rb) {
   if (!codec_accepts_components(codec, comps))
     return fail(ICAMD_ERR_ARG, "mip chain: source components not accepted by this codec (as icamd_encode_device)");
@@ -492,8 +448,8 @@ int mip_check_geometry(int codec, int comps, uint32_t height, uint32_t width, ui
     return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
   if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)comps) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
   const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)comps;
-  const size_t dst_bytes = codec == icamd::kMipPyramidMode ? mip_pyramid_bytes(height, width, levels, comps)
-                                                           : icamd_mip_chain_size(codec, height, width, levels, nullptr);
+  const size_t dst_bytes = codec == icamd::kMipPyramidMode ? icamd::mip_pyramid_bytes(height, width, levels, comps)
+                                                           : icamd::mip_chain_bytes(codec, height, width, levels, nullptr);
   if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < dst_bytes))
     return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
   return ICAMD_OK;
@@ -1476,21 +1432,13 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
 uint32_t icamd_mip_max_levels(uint32_t height, uint32_t width) { return mip_max_levels(height, width); }
 
 size_t icamd_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets) {
-  if (!mip_codec(codec) || levels == 0 || levels > mip_max_levels(height, width)) return 0;
-  size_t total = 0;
-  for (uint32_t l = 0; l < levels; ++l) {
-    if (level_offsets) level_offsets[l] = total;
-    total += icamd_encoded_size(codec, mip_dim(height, l), mip_dim(width, l));
-  }
-  if (level_offsets) level_offsets[levels] = total;
-  return total;
+  return icamd::mip_chain_bytes(codec, height, width, levels, level_offsets);
 }
 
 size_t icamd_mip_workspace_size(int codec, int src_components, uint32_t height, uint32_t width, uint32_t levels,
                                 uint32_t n_images) {
-  if (!mip_codec(codec) || src_components < 1 || src_components > 4 || levels == 0 || levels > mip_max_levels(height, width))
-    return 0;
-  return mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
+  if (!mip_codec(codec)) return 0;
+  return icamd::mip_chain_plan({ codec, src_components, ICAMD_MIP_FILTER_BOX, height, width, levels, n_images, 0, 0, 0 }).workspace_bytes;
 }
 
 // icamd_encode_mips_device / icamd_encode_mips_filtered_device (the former is filter 0)
@@ -1510,62 +1458,29 @@ static int encode_mips(int codec, int etc_strategy, int src_components, int swap
   rc = mip_check_geometry(codec, src_components, height, width, row_stride_bytes, levels, n_images, src_image_stride_bytes,
                           dst_image_stride_bytes);
   if (rc != ICAMD_OK) return rc;
-  const size_t ws_need = mip_workspace_bytes(codec, height, width, levels, src_components, n_images);
-  if (ws_need && (!d_workspace || workspace_bytes < ws_need))
+  const icamd::MipChainPlan plan = icamd::mip_chain_plan({ codec, src_components, filter, height, width, levels, n_images,
+                                                           row_stride_bytes, src_image_stride_bytes, dst_image_stride_bytes });
+  if (plan.workspace_bytes && (!d_workspace || workspace_bytes < plan.workspace_bytes))
     return fail(ICAMD_ERR_ARG, "workspace smaller than icamd_mip_workspace_size");
   if (n_images == 0) return ICAMD_OK;
   rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  size_t offsets[33];
-  (void)icamd_mip_chain_size(codec, height, width, levels, offsets);
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (codec == ICAMD_ETC1) {
-    // level 0 from the source and every other level from the pixel pyramid in the workspace, each through the ETC1 kernels
-    // of icamd_encode_device (a fused ETC1 kernel is deferred)
-    uint8_t *dst = static_cast<uint8_t *>(d_dst), *ws = static_cast<uint8_t *>(d_workspace);
-    const size_t pyr = mip_pyramid_bytes(height, width, levels, src_components);
-    rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, height, width, row_stride_bytes, n_images,
-                             src_image_stride_bytes, dst_image_stride_bytes, d_src, dst, hip_stream);
-    if (rc == ICAMD_OK && levels > 1)
-      rc = icamd_mip_pyramid_filtered_device(src_components, filter, height, width, row_stride_bytes, levels, n_images,
-                                             src_image_stride_bytes, pyr, d_src, ws, hip_stream);
-    size_t poff = 0;
-    for (uint32_t l = 1; l < levels && rc == ICAMD_OK; ++l) {
-      const uint32_t lh = mip_dim(height, l), lw = mip_dim(width, l);
-      rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, lh, lw, lh, lw, lw * (uint32_t)src_components,
-                               n_images, pyr, dst_image_stride_bytes, ws + poff, dst + offsets[l], hip_stream);
-      poff += mip_level_pixels(height, width, l, src_components);
-    }
-    return rc;
-  }
-  const uint8_t *in = static_cast<const uint8_t *>(d_src);
-  uint64_t in_image_stride = src_image_stride_bytes;
-  uint32_t in_row_stride = row_stride_bytes;
-  uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-  for (const MipPass &p : mip_plan(height, width, levels, false)) {
-    icamd::MipParams P = {};
-    P.src = in;
-    P.src_image_stride = in_image_stride;
-    P.row_stride = in_row_stride;
-    P.height = p.in_h;
-    P.width = p.in_w;
-    P.dst = static_cast<uint8_t *>(d_dst);
-    P.dst_image_stride = dst_image_stride_bytes;
-    for (uint32_t j = 0; j < p.n; ++j) P.level_off[j] = offsets[p.l0 + j];
-    P.enc_mask = (1u << p.n) - 1u;
-    P.swap_rb = swap_rb ? 1u : 0u;
-    if (p.handoff) {  // level l0 + 6's pixels, tight rows, images back to back: the next pass's input
-      const size_t per = mip_level_pixels(height, width, p.l0 + 6u, src_components);
-      P.pix = ws;
-      P.pix_image_stride = per;
-      P.pix_mask = 1u << 6;
-      in = ws;
-      in_image_stride = per;
-      in_row_stride = mip_dim(width, p.l0 + 6u) * (uint32_t)src_components;
-      ws += per * n_images;
-    }
-    ICAMD_HIP(icamd::launch_mip_filter_pass(codec, src_components, filter, P, n_images, stream), "launch mip chain");
-  }
+  if (plan.form != icamd::kMipLaunch) return fail(ICAMD_ERR_ARG, "mip chain: no kernel for this codec, source layout and filter");
+  const icamd::MipBuffers buffers = { static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_workspace), static_cast<uint8_t *>(d_dst) };
+  // ETC1 (the plan has encode calls): level 0 from the source, the pixel pyramid into the workspace, then every other level from
+  // it, each through the ETC1 kernels of icamd_encode_device (a fused ETC1 kernel is deferred)
+  const bool etc1 = plan.n_encodes != 0;
+  const auto encode_level = [&](const icamd::MipEncodeCall &e) {
+    const uint8_t *in = (e.in.base == icamd::kMipSource ? buffers.src : buffers.workspace) + e.in.offset;
+    return icamd_encode_device(codec, etc_strategy, src_components, swap_rb, e.height, e.width, e.height, e.width, e.in_row_stride,
+                               n_images, e.in_image_stride, dst_image_stride_bytes, in, buffers.out + e.out_offset, hip_stream);
+  };
+  if (etc1 && (rc = encode_level(plan.encode[0])) != ICAMD_OK) return rc;
+  for (uint32_t k = 0; k < plan.n_passes; ++k)
+    ICAMD_HIP(icamd::launch_mip_pass(etc1 ? icamd::kMipPyramidMode : codec, src_components, filter, plan.pass[k], buffers,
+                                     !etc1 && swap_rb, static_cast<hipStream_t>(hip_stream)), "launch mip chain");
+  for (uint32_t l = 1; l < plan.n_encodes; ++l)
+    if ((rc = encode_level(plan.encode[l])) != ICAMD_OK) return rc;
   return ICAMD_OK;
 }
 
@@ -1599,25 +1514,13 @@ static int mip_pyramid(int src_components, int filter, uint32_t height, uint32_t
   if (n_images == 0) return ICAMD_OK;
   rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  if (levels == 1) return ICAMD_OK;
-  size_t poff[34];  // poff[l]: bytes of levels 1 .. l-1 (level l's offset in one image's output)
-  poff[1] = 0;
-  for (uint32_t l = 1; l < levels; ++l) poff[l + 1] = poff[l] + mip_level_pixels(height, width, l, src_components);
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  uint8_t *dst = static_cast<uint8_t *>(d_dst);
-  for (const MipPass &p : mip_plan(height, width, levels, true)) {
-    icamd::MipParams P = {};
-    P.src = p.l0 == 0 ? static_cast<const uint8_t *>(d_src) : dst + poff[p.l0];
-    P.src_image_stride = p.l0 == 0 ? src_image_stride_bytes : dst_image_stride_bytes;
-    P.row_stride = p.l0 == 0 ? row_stride_bytes : p.in_w * (uint32_t)src_components;
-    P.height = p.in_h;
-    P.width = p.in_w;
-    P.pix = dst;
-    P.pix_image_stride = dst_image_stride_bytes;
-    for (uint32_t j = 1; j < p.n; ++j) P.pix_off[j] = poff[p.l0 + j];
-    P.pix_mask = ((1u << p.n) - 1u) & ~1u;
-    ICAMD_HIP(icamd::launch_mip_filter_pass(icamd::kMipPyramidMode, src_components, filter, P, n_images, stream), "launch mip pyramid");
-  }
+  const icamd::MipChainPlan plan = icamd::mip_chain_plan({ icamd::kMipPyramidMode, src_components, filter, height, width, levels, n_images,
+                                                           row_stride_bytes, src_image_stride_bytes, dst_image_stride_bytes });
+  if (plan.form == icamd::kMipRefused) return fail(ICAMD_ERR_ARG, "mip pyramid: no kernel for this source layout and filter");
+  const icamd::MipBuffers buffers = { static_cast<const uint8_t *>(d_src), nullptr, static_cast<uint8_t *>(d_dst) };
+  for (uint32_t k = 0; k < plan.n_passes; ++k)
+    ICAMD_HIP(icamd::launch_mip_pass(icamd::kMipPyramidMode, src_components, filter, plan.pass[k], buffers, false,
+                                     static_cast<hipStream_t>(hip_stream)), "launch mip pyramid");
   return ICAMD_OK;
 }
 
@@ -1661,7 +1564,7 @@ static int compress_mips(int compressor, int etc_strategy, int format, int filte
   if (stride > 0xffffffffull) return fail(ICAMD_ERR_ARG, "row stride does not fit 32 bits");
   const size_t in_bytes = (size_t)(height - 1) * stride + (size_t)width * comps;
   const size_t ws_off = (out_size + 255u) & ~(size_t)255u;
-  const size_t ws = mip_workspace_bytes(codec, height, width, levels, comps, 1);
+  const size_t ws = icamd_mip_workspace_size(codec, comps, height, width, levels, 1);
   return staged_blockop(tls_staging(), buffer, in_bytes, out, out_size, ws_off + ws, false, [&](void *din, void *dout, hipStream_t s) {
     uint8_t *d_out = static_cast<uint8_t *>(dout);
     return encode_mips(codec, etc_strategy, comps, swap, filter, height, width, (uint32_t)stride, levels, 1, 0, 0, din, d_out,

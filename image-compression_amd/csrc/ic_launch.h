@@ -1,7 +1,8 @@
 // ic_launch.h -- host-side launch entry points of the kernel translation units
 // (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip, blockops_kernels.hip); called by ic_capi.hip.
-// Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC) and blockops_plan.h (Pad, Downsample and
-// the chunks of CopySubimage, CreateSolid and the transcode); the launchers here run what a plan says.
+// Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC), blockops_plan.h (Pad, Downsample and
+// the chunks of CopySubimage, CreateSolid and the transcode) and mip_plan.h (the passes, grids and kernels of the mip chains);
+// the launchers here run what a plan says.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -11,6 +12,7 @@
 
 #include "blockops_plan.h"
 #include "ic_device.h"
+#include "mip_plan.h"
 
 namespace icamd {
 
@@ -165,20 +167,18 @@ struct MipParams {
   uint32_t height, width, row_stride;
   uint32_t enc_mask, pix_mask;
   uint32_t swap_rb;
-  uint32_t tile_row0;  // first tile row of this launch (set by launch_mip_pass)
+  uint32_t tile_row0;  // first tile row of this launch (launch_mip_pass: a piece of the plan's tile rows)
 };
-constexpr int kMipPyramidMode = -1;  // `mode` of the pixel-pyramid kernels (no encoder)
-// mode: ICAMD_DXT1 / DXT5 / BC4 / BC5 or kMipPyramidMode (ETC1 chains are the pyramid + the ETC1 kernels, ic_capi.hip)
-hipError_t launch_mip_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream);
-// The same pass with one of the ICAMD_MIP_FILTER_* filters (mip_filter_kernels.hip): DXT1 (3 / 4 components; 4 with the
-// alpha-weighted bit), DXT5 and kMipPyramidMode (likewise); filter 0 is launch_mip_pass and ICAMD_MIP_FILTER_NORMAL is
-// launch_mip_normal_pass.  hipErrorInvalidValue for the rest.
-hipError_t launch_mip_filter_pass(int mode, int comps, int filter, const MipParams &P, uint32_t n_images, hipStream_t stream);
-// The same pass with ICAMD_MIP_FILTER_NORMAL (mip_normal_kernels.hip): ICAMD_BC5 (2..4 components) and kMipPyramidMode (2).
-hipError_t launch_mip_normal_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream);
-const char *mip_box_kernel_name(int mode, int comps);              // "" where launch_mip_pass has no kernel
-const char *mip_normal_kernel_name(int mode, int comps);           // "" where launch_mip_normal_pass has no kernel
-const char *mip_kernel_name(int mode, int comps, int filter);      // "" where launch_mip_filter_pass has no kernel
+// A planned pass (mip_plan.h: which passes a call runs, where each reads and writes and how it is cut into launches is decided
+// there) with the kernel of (mode, comps, filter): mode is ICAMD_DXT1 / DXT5 / BC4 / BC5 or kMipPyramidMode (ETC1 chains are the
+// pyramid + the ETC1 kernels, mip_plan.h).  hipErrorInvalidValue where the kernel list has no such row.
+struct MipBuffers {  // what MipBase names: the caller's source, workspace and output
+  const uint8_t *src;
+  uint8_t *workspace, *out;
+};
+hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
+                           hipStream_t stream);
+const char *mip_kernel_name(int mode, int comps, int filter);  // "" where launch_mip_pass has no kernel
 
 // Compressed-domain operations on block grids.  BlockOpParams is what a kernel receives: launch_blockop
 // (blockops_kernels.hip) fills it, per launch, from the caller's BlockOpCall and the plan of blockops_plan.h.

@@ -1,65 +1,57 @@
 // mip_kernels.hip -- fused mip-chain encode (and the plain pixel pyramid) for gfx950 (include/ic_amd.h, mip-chain section) with
-// the box filter: the pass of mip_pass.h, which describes it.  The kernels of the other filters: mip_filter_kernels.hip.
+// the box filter: the pass of mip_pass.h, which describes it.  The kernels of the other filters: mip_filter_kernels.hip and
+// mip_normal_kernels.hip.  Also the one table of all the mip kernels (mip_plan.h's list) and the launcher of a planned pass.
 #include "mip_pass.h"
 
 namespace icamd {
 
 extern "C" {
-#define ICAMD_MIP_KERNEL(name, mode, comps) \
-  __global__ void __launch_bounds__(kThreadsPerWorkgroup) name(MipParams P) { mip_pass<mode, comps, 0>(P); }
-ICAMD_MIP_KERNEL(icamd_mip_dxt1_rgb888_kernel, ICAMD_DXT1, 3)
-ICAMD_MIP_KERNEL(icamd_mip_dxt1_rgba8_kernel, ICAMD_DXT1, 4)
-ICAMD_MIP_KERNEL(icamd_mip_dxt5_rgba8_kernel, ICAMD_DXT5, 4)
-ICAMD_MIP_KERNEL(icamd_mip_bc4_r8_kernel, ICAMD_BC4, 1)
-ICAMD_MIP_KERNEL(icamd_mip_bc4_rg8_kernel, ICAMD_BC4, 2)
-ICAMD_MIP_KERNEL(icamd_mip_bc4_rgb888_kernel, ICAMD_BC4, 3)
-ICAMD_MIP_KERNEL(icamd_mip_bc4_rgba8_kernel, ICAMD_BC4, 4)
-ICAMD_MIP_KERNEL(icamd_mip_bc5_rg8_kernel, ICAMD_BC5, 2)
-ICAMD_MIP_KERNEL(icamd_mip_bc5_rgb888_kernel, ICAMD_BC5, 3)
-ICAMD_MIP_KERNEL(icamd_mip_bc5_rgba8_kernel, ICAMD_BC5, 4)
-ICAMD_MIP_KERNEL(icamd_mip_pyramid_r8_kernel, kMipPyramidMode, 1)
-ICAMD_MIP_KERNEL(icamd_mip_pyramid_rg8_kernel, kMipPyramidMode, 2)
-ICAMD_MIP_KERNEL(icamd_mip_pyramid_rgb888_kernel, kMipPyramidMode, 3)
-ICAMD_MIP_KERNEL(icamd_mip_pyramid_rgba8_kernel, kMipPyramidMode, 4)
-#undef ICAMD_MIP_KERNEL
+ICAMD_MIP_BOX_KERNELS(ICAMD_MIP_DEFINE_KERNEL)
+#define ICAMD_MIP_DECLARE_KERNEL(name, mode, comps, filter) __global__ void __launch_bounds__(kThreadsPerWorkgroup) name(MipParams P);
+ICAMD_MIP_FILTER_KERNELS(ICAMD_MIP_DECLARE_KERNEL)
+ICAMD_MIP_NORMAL_KERNELS(ICAMD_MIP_DECLARE_KERNEL)
+#undef ICAMD_MIP_DECLARE_KERNEL
 }  // extern "C"
 
-static MipKernel mip_kernel(int mode, int comps) {
-  switch (mode) {
-    case ICAMD_DXT1: return comps == 3 ? icamd_mip_dxt1_rgb888_kernel : comps == 4 ? icamd_mip_dxt1_rgba8_kernel : nullptr;
-    case ICAMD_DXT5: return comps == 4 ? icamd_mip_dxt5_rgba8_kernel : nullptr;
-    case ICAMD_BC4:
-      return comps == 1 ? icamd_mip_bc4_r8_kernel : comps == 2 ? icamd_mip_bc4_rg8_kernel : comps == 3 ? icamd_mip_bc4_rgb888_kernel
-           : comps == 4 ? icamd_mip_bc4_rgba8_kernel : nullptr;
-    case ICAMD_BC5:
-      return comps == 2 ? icamd_mip_bc5_rg8_kernel : comps == 3 ? icamd_mip_bc5_rgb888_kernel : comps == 4 ? icamd_mip_bc5_rgba8_kernel
-           : nullptr;
-    case kMipPyramidMode:
-      return comps == 1 ? icamd_mip_pyramid_r8_kernel : comps == 2 ? icamd_mip_pyramid_rg8_kernel
-           : comps == 3 ? icamd_mip_pyramid_rgb888_kernel : comps == 4 ? icamd_mip_pyramid_rgba8_kernel : nullptr;
+typedef void (*MipKernel)(MipParams);
+#define ICAMD_MIP_POINTER(name, mode, comps, filter) name,
+static const MipKernel kMipKernels[] = { ICAMD_MIP_KERNELS(ICAMD_MIP_POINTER) };  // by mip_kernel_index
+#undef ICAMD_MIP_POINTER
+
+hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
+                           hipStream_t stream) {
+  const int k = mip_kernel_index(mode, comps, filter);
+  if (k < 0) return hipErrorInvalidValue;
+  uint8_t *const base[] = { const_cast<uint8_t *>(buffers.src), buffers.workspace, buffers.out };  // by MipBase
+  MipParams P = {};
+  P.src_image_stride = pass.in_image_stride;
+  P.row_stride = pass.in_row_stride;
+  P.height = pass.height;
+  P.width = pass.width;
+  P.enc_mask = pass.enc_mask;
+  P.pix_mask = pass.pix_mask;
+  P.swap_rb = swap_rb ? 1u : 0u;
+  P.dst_image_stride = pass.dst_image_stride;
+  P.pix_image_stride = pass.pix_image_stride;
+  for (int j = 0; j < 8; ++j) {
+    P.level_off[j] = pass.level_off[j];
+    P.pix_off[j] = pass.pix_off[j];
   }
-  return nullptr;
+  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+  for (uint32_t z = 0; z < mip_pieces(pass.n_images); ++z) {
+    const MipPiece images = mip_piece(pass.n_images, z);
+    P.src = base[pass.in.base] + pass.in.offset + (uint64_t)images.first * pass.in_image_stride;
+    P.dst = pass.enc_mask ? buffers.out + (uint64_t)images.first * pass.dst_image_stride : nullptr;
+    P.pix = pass.pix_mask ? base[pass.pix.base] + pass.pix.offset + (uint64_t)images.first * pass.pix_image_stride : nullptr;
+    for (uint32_t y = 0; y < mip_pieces(pass.tile_rows); ++y) {
+      const MipPiece rows = mip_piece(pass.tile_rows, y);
+      P.tile_row0 = rows.first;
+      hipLaunchKernelGGL(kMipKernels[k], dim3(pass.grid_x, rows.count, images.count), dim3(kThreadsPerWorkgroup), 0, stream, P);
+    }
+  }
+  return hipGetLastError();
 }
 
-hipError_t launch_mip_pass(int mode, int comps, const MipParams &P, uint32_t n_images, hipStream_t stream) {
-  return launch_mip_kernel(mip_kernel(mode, comps), P, n_images, stream);
-}
-
-const char *mip_box_kernel_name(int mode, int comps) {
-  switch (mode) {
-    case ICAMD_DXT1: return comps == 3 ? "icamd_mip_dxt1_rgb888_kernel" : comps == 4 ? "icamd_mip_dxt1_rgba8_kernel" : "";
-    case ICAMD_DXT5: return comps == 4 ? "icamd_mip_dxt5_rgba8_kernel" : "";
-    case ICAMD_BC4:
-      return comps == 1 ? "icamd_mip_bc4_r8_kernel" : comps == 2 ? "icamd_mip_bc4_rg8_kernel" : comps == 3 ? "icamd_mip_bc4_rgb888_kernel"
-           : comps == 4 ? "icamd_mip_bc4_rgba8_kernel" : "";
-    case ICAMD_BC5:
-      return comps == 2 ? "icamd_mip_bc5_rg8_kernel" : comps == 3 ? "icamd_mip_bc5_rgb888_kernel" : comps == 4 ? "icamd_mip_bc5_rgba8_kernel"
-           : "";
-    case kMipPyramidMode:
-      return comps == 1 ? "icamd_mip_pyramid_r8_kernel" : comps == 2 ? "icamd_mip_pyramid_rg8_kernel"
-           : comps == 3 ? "icamd_mip_pyramid_rgb888_kernel" : comps == 4 ? "icamd_mip_pyramid_rgba8_kernel" : "";
-  }
-  return "";
-}
+const char *mip_kernel_name(int mode, int comps, int filter) { return mip_kernel_form(mode, comps, filter).name; }
 
 }  // namespace icamd

@@ -1,6 +1,7 @@
 // mip_pass.h -- the fused mip-chain pass (and the plain pixel pyramid) for gfx950 (include/ic_amd.h, mip-chain section), shared
 // by mip_kernels.hip (the box filter), mip_filter_kernels.hip (the sRGB / alpha-weighted filters, mip_filter.h) and
-// mip_normal_kernels.hip (the normal-map filter, mip_normal.h).
+// mip_normal_kernels.hip (the normal-map filter, mip_normal.h).  Device code only: which passes a call runs, on which grids, and
+// which kernels exist is mip_plan.h's.
 //
 // One pass reads an input level once and writes up to six (eight when the input is a single tile) levels of the chain:
 //  * a 256-lane workgroup owns a 128 x 128-pixel tile of the input level; a lane encodes four of its 32 x 32 blocks straight
@@ -32,7 +33,6 @@
 
 namespace icamd {
 
-constexpr uint32_t kMipTile = 128;    // input pixels per tile side
 // dword offset of local level j (1..7) in LDS: level j is (128 >> j)^2 pixel dwords
 constexpr uint32_t mip_lds_off(uint32_t j) { return j <= 1 ? 0u : mip_lds_off(j - 1) + (kMipTile >> (j - 1)) * (kMipTile >> (j - 1)); }
 constexpr uint32_t kMipLdsDwords = mip_lds_off(8);  // 5461 dwords = 21 844 bytes
@@ -264,28 +264,9 @@ __device__ __forceinline__ void mip_pass(const MipParams &P) {
   }
 }
 
-typedef void (*MipKernel)(MipParams);
-
-// One pass over n_images images: images go into grid.z and tile rows into grid.y in chunks of at most 65 535 (MipParams::tile_row0).
-inline hipError_t launch_mip_kernel(MipKernel k, const MipParams &P, uint32_t n_images, hipStream_t stream) {
-  if (!k) return hipErrorInvalidValue;
-  if (n_images == 0) return hipSuccess;
-  const uint32_t gx = (uint32_t)(((uint64_t)P.width + kMipTile - 1u) / kMipTile);
-  const uint32_t gy = (uint32_t)(((uint64_t)P.height + kMipTile - 1u) / kMipTile);
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  for (uint32_t first = 0; first < n_images; first += 65535u) {
-    const uint32_t count = n_images - first < 65535u ? n_images - first : 65535u;
-    for (uint32_t row0 = 0; row0 < gy; row0 += 65535u) {
-      MipParams Q = P;
-      Q.src = P.src + (uint64_t)first * P.src_image_stride;
-      Q.dst = P.dst ? P.dst + (uint64_t)first * P.dst_image_stride : nullptr;
-      Q.pix = P.pix ? P.pix + (uint64_t)first * P.pix_image_stride : nullptr;
-      Q.tile_row0 = row0;
-      hipLaunchKernelGGL(k, dim3(gx, gy - row0 < 65535u ? gy - row0 : 65535u, count), dim3(kThreadsPerWorkgroup), 0, stream, Q);
-    }
-  }
-  return hipGetLastError();
-}
+// A row of mip_plan.h's kernel list as its kernel: each mip translation unit defines its own sub-list.
+#define ICAMD_MIP_DEFINE_KERNEL(name, mode, comps, filter) \
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) name(MipParams P) { mip_pass<mode, comps, filter>(P); }
 
 }  // namespace icamd
 #endif  // ICAMD_MIP_PASS_H_

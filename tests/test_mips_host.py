@@ -2,8 +2,9 @@
 * icamd_mip_max_levels / icamd_mip_chain_size / offsets / icamd_mip_workspace_size against a Python formula;
 * every refusal returns its status, and valid arguments without a device fail loudly (no CPU path);
 * the numpy pyramid of tests/mips_oracle.py against a literal restatement of the rule;
-* a Python model of the kernel's pass plan and tile / level / edge index mapping (a restatement of mip_kernels.hip, not its
-  code: the GPU tier runs the kernels themselves on the same shapes) against that pyramid;
+* a Python model of the pass plan (mip_plan.h) and the kernel's tile / level / edge index mapping (mip_pass.h) -- a restatement, not
+  their code: tests/test_mip_plan_host.py holds the compiled plan against this model, and the GPU tier runs the kernels themselves on
+  the same shapes -- against that pyramid;
 * (ref) the compiled reference's Compress of every pyramid level equals the oracle's encode;
 * the new kernels compile for gfx950 with zero scratch and the planned LDS size."""
 import ctypes
@@ -188,8 +189,8 @@ def test_numpy_pyramid_matches_the_literal_rule(h, w):
     assert M.next_level(p)[0, 0, 0] == (10 + 13 + 10 + 13) // 4
 
 
-# ---- a Python model of the kernel's index mapping (mip_kernels.hip restated: pass plan, 128 x 128 tiles, LDS levels, edge
-# clamps).  It checks the mapping's design -- that the tile rules reproduce the pyramid and the clamped blocks on odd, thin and
+# ---- a Python model of the kernel's index mapping (mip_plan.h's pass plan and mip_pass.h's 128 x 128 tiles, LDS levels and edge
+# clamps, restated).  It checks the mapping's design -- that the tile rules reproduce the pyramid and the clamped blocks on odd, thin and
 # multi-tile shapes -- not the compiled code, which tests/test_gpu_mips.py checks on the device.
 
 def _model_plan(h, w, levels, pyramid):
