@@ -34,6 +34,10 @@ PVRTC4 = 4  # EXTENSION, parity unpinned: PVRTC1 4 bpp (include/ic_amd.h); icamd
 # EXTENSION, parity pinned through the reference's DXT5 alpha path (include/ic_amd.h): BC4 (RGTC1, one channel, 8 bytes per
 # block) and BC5 (RGTC2, two channels, 16 bytes per block); encode_device / decode_device / encode_batch_sharded_device only
 BC4, BC5 = 5, 6
+# EXTENSION (include/ic_amd.h ICAMD_ETC2_RGBA8): ETC2 RGBA8 = EAC alpha word + ETC1-compatible colour word, 16 bytes per block,
+# from RGBA8 sources; colour half pinned to the ETC1 encoder byte for byte, alpha half defined in DESIGN.md 3.11.  7..15 are
+# unassigned and rejected.  encode_device / decode_device / measure_error_device / containers only
+ETC2_RGBA8 = 16
 OK, FALSE = 0, 1
 
 EXPORTS = [
@@ -324,7 +328,7 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
-    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, BC4: 1, BC5: 2}.get(codec, 3)  # BC4 -> R8, BC5 -> RG8
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, BC4: 1, BC5: 2}.get(codec, 3)  # BC4 -> R8, BC5 -> RG8
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

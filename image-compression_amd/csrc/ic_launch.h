@@ -85,6 +85,9 @@ hipError_t launch_tiled(Kernel wide_kernel, Kernel narrow_kernel, GridParams P, 
 // codec: ICAMD_DXT1 / ICAMD_DXT5; comps: source bytes per pixel (3 or 4; DXT5 requires 4).
 hipError_t launch_dxt(int codec, int comps, const GridParams &P, hipStream_t stream);
 hipError_t launch_etc1(int comps, const GridParams &P, hipStream_t stream);
+// ETC2 RGBA8 (extension, etc2_kernels.hip): RGBA8 sources only; P.etc_strategy picks the colour half's kernel as for ETC1
+hipError_t launch_etc2(const GridParams &P, hipStream_t stream);
+const char *etc2_kernel_name(int comps);  // "" unless comps == 4
 
 // PVRTC1 2bpp: square power-of-two RGBA8 images, n_images of them.
 struct PvrtcParams {
@@ -124,6 +127,7 @@ struct DecodeParams {
   FastDiv div_bpi, div_cols;
 };
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
+hipError_t launch_etc2_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGBA8 -> RGBA8 rows (etc2_kernels.hip)
 
 // Quality metric (metric_kernels.hip): n_images block grids against their source pixels, one launch of fewer than 2^31
 // blocks.  block_rows x block_cols are the blocks that cover the IMAGE (blocks of a padded grid beyond it are never visited);

@@ -60,7 +60,36 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_decode_device writes R8 (BC4) or RG8 (BC5) rows and needs swap_rb = 0.  Reachable through icamd_encode_device,
         * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_encoded_size, icamd_kernel_name and the container
         * functions only: no Compressor + format pair selects them. */
-       ICAMD_BC4 = 5, ICAMD_BC5 = 6 };
+       ICAMD_BC4 = 5, ICAMD_BC5 = 6,
+       /* Values 7..15 are unassigned and rejected by every entry point. */
+       /* EXTENSION: ETC2 RGBA8 (COMPRESSED_RGBA8_ETC2_EAC), 16 bytes per 4 x 4 block in the raster block order of ETC1: the
+        * 8-byte EAC alpha word, then the 8-byte colour word.
+        *   Colour half, PARITY PINNED: bytes 8..15 of a block are exactly the 8 bytes icamd_encode_device(ICAMD_ETC1,
+        *       etc_strategy, 4, swap_rb, ...) writes for it -- all four strategies, padded grids and image edges included (like
+        *       ETC1 the encoder stores bytes 0..2 of a pixel as they lie in memory, whatever swap_rb).  Every such block is a valid
+        *       ETC2 colour word: the ETC1 encoder only selects differential mode when both 5-bit bases lie in 0..31, so the
+        *       overflow patterns of ETC2's T, H and planar modes never occur.
+        *   Alpha half, PARITY UNPINNED (the reference has no EAC): byte 0 = base, byte 1 = multiplier << 4 | table, bytes 2..7 =
+        *       sixteen 3-bit indices, big-endian, texel i = 4 x + y in bits 47 - 3 i .. 45 - 3 i.  The alpha of texel (x, y) is
+        *       byte 3 of the RGBA texel the colour half is given for that position (same edge replication, same padded-grid
+        *       fetch).  Decode (Khronos ETC2 / EAC): alpha = clamp(base + M[table][index] * multiplier, 0, 255) with the 16 x 8
+        *       modifier table of the specification (csrc/etc2_block.h); multiplier 0 is legal on decode and gives base.
+        *       Encode is a definition, not a heuristic: with lo / hi the smallest / largest of the 16 alphas,
+        *       R = hi - lo and span[t] = M[t][7] - M[t][3], the candidates are, for every table t, the multipliers
+        *       m in {m0 - 1, m0, m0 + 1} clamped to 1..15 with m0 = clamp((2 R + span[t]) / (2 span[t]), 1, 15), and for each m
+        *       the bases b in {b0 - 1, b0, b0 + 1} clamped to 0..255 with b0 = (lo + hi + m + 1) >> 1; every texel takes the
+        *       smallest index that minimises |clamp(b + M[t][k] m, 0, 255) - alpha|, sse is the sum of the squared minima, and
+        *       the block is the candidate with the lexicographically smallest (sse, t, m, b).  Multiplier 0 is never written.
+        * icamd_encode_device needs src_components == 4 (else ICAMD_ERR_ARG) and honours etc_strategy, grids, strides and batches
+        * as for ETC1.  icamd_decode_device writes RGBA8 rows (swap_rb: stored R goes to the third byte, as for DXT5) and decodes
+        * blocks whose colour word is in an ETC1-compatible mode (individual, or differential without overflow) -- everything
+        * this library writes; T, H and planar colour words are NOT decoded (their pixels are unspecified).
+        * icamd_measure_error_device compares all four channels.  Reachable through icamd_encode_device,
+        * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device, icamd_encoded_size,
+        * icamd_kernel_name, icamd_metric_kernel_name and the container functions only: no Compressor + format pair selects it
+        * (icamd_supports_format and the host-buffer entry points keep the reference's semantics, so icamd_measure_error does
+        * not reach it), and the mip entry points answer ICAMD_ERR_ARG as they do for PVRTC. */
+       ICAMD_ETC2_RGBA8 = 16 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -169,7 +198,8 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
  * Any uint32 geometry runs (grids, batches and strides beyond one launch's limits are chunked internally).
  * Alignment: DXT / ETC accept any pointers and strides; PVRTC reads 16 bytes at a time and requires d_src (and
  * src_image_stride_bytes) 16-byte aligned, d_dst (and dst_image_stride_bytes) 8-byte aligned, else ICAMD_ERR_ARG.
- * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT. */
+ * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT.
+ * ETC2 RGBA8 (extension, see ICAMD_ETC2_RGBA8): src_components must be 4; otherwise as ETC1. */
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
                         uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
                         uint32_t row_stride_bytes, uint32_t n_images,
@@ -186,7 +216,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
  * decoder of the 4 bpp extension encoder, under the same conditions and as unpinned as that: 4 x 4 blocks, every pixel its
  * own 2-bit value (weights 0, 3, 5, 8; a block with colour-word bit 0 set -- the encoder never writes one -- takes PVRTC1's
  * punch-through weights 0, 4, 4, 8 with alpha 0 for value 2).  ICAMD_BC4 / ICAMD_BC5 (extension, see ICAMD_BC4) write
- * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG. */
+ * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG.  ICAMD_ETC2_RGBA8 (extension)
+ * writes width*4 bytes per row plus the padding; its domain is stated at the codec enumeration. */
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t padding_bytes_per_row, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
@@ -347,7 +378,7 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
  * The reference ends at the raw block stream (compressed_image.h:52-66); it has no file-container code, so there is
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
  * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
- * PVRTC2, BC4, BC5), PKM (ETC1, one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
+ * PVRTC2, BC4, BC5, ETC2 RGBA8), PKM (ETC1 as "PKM 10" type 0, ETC2 RGBA8 as "PKM 20" type 3; one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
  * icamd_compress / icamd_downsample return for that size (PVRTC: square power-of-two levels of 8 x 8 and up only). */
 enum { ICAMD_CONTAINER_DDS = 0, ICAMD_CONTAINER_KTX = 1, ICAMD_CONTAINER_PKM = 2, ICAMD_CONTAINER_PVR = 3 };
@@ -478,6 +509,7 @@ const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
  * The compared channels are the decoder's output channels; the others are 0 in both arrays:
  *     DXT1, ETC1            bytes 0..2 of the source pixel   src_components 3 or 4 (alpha ignored, sse[3] = 0)
  *     DXT5, PVRTC2, PVRTC4  bytes 0..3                        src_components 4
+ *     ETC2 RGBA8            bytes 0..3                        src_components 4
  *     BC4                   k = 0 is R                        src_components 1..4  (R, G located by the rules at ICAMD_BC4:
  *     BC5                   k = 0, 1 are R, G                 src_components 2..4   R = byte 0, or byte 2 with swap_rb)
  * Everything is integer arithmetic: the result is exact and the same from run to run.  PSNR over N pixels and C channels is
