@@ -44,7 +44,7 @@ EXPORTS = [
     "icamd_compute_compressed_data_size", "icamd_supports_format", "icamd_encoded_size", "icamd_compress",
     "icamd_compress_and_pad", "icamd_compress_device", "icamd_compress_and_pad_device", "icamd_encode_device",
     "icamd_decode_device", "icamd_decompress", "icamd_pad_device", "icamd_pad", "icamd_downsample_device",
-    "icamd_downsample", "icamd_downsample_batch_device", "icamd_pad_batch_device", "icamd_create_solid_batch_device", "icamd_copy_subimage_batch_device", "icamd_transcode_dxt1_to_etc1_device", "icamd_transcode_dxt1_to_etc1", "icamd_compress_batch", "icamd_pvrtc2_encode_region_device", "icamd_pvrtc2_workspace_size", "icamd_pvrtc4_workspace_size",
+    "icamd_downsample", "icamd_downsample_batch_device", "icamd_pad_batch_device", "icamd_create_solid_batch_device", "icamd_copy_subimage_batch_device", "icamd_transcode_dxt1_to_etc1_device", "icamd_transcode_dxt1_to_etc1", "icamd_transcode_dxt5_to_etc2_rgba8_device", "icamd_transcode_dxt5_to_etc2_rgba8", "icamd_compress_batch", "icamd_pvrtc2_encode_region_device", "icamd_pvrtc2_workspace_size", "icamd_pvrtc4_workspace_size",
     "icamd_pvrtc2_set_workspace", "icamd_pvrtc2_tune", "icamd_host_register", "icamd_host_unregister", "icamd_pvrtc2_decompress", "icamd_device_count", "icamd_last_error", "icamd_version", "icamd_kernel_name",
     "icamd_create_solid_device", "icamd_create_solid", "icamd_copy_subimage_device", "icamd_copy_subimage",
     "icamd_encode_batch_sharded_device", "icamd_clock_probe_device", "icamd_wall_clock_rate_khz",
@@ -118,6 +118,11 @@ def lib():
         L.icamd_transcode_dxt1_to_etc1.argtypes = [_vp, _sz]
         L.icamd_transcode_dxt1_to_etc1_device.restype = _ci
         L.icamd_transcode_dxt1_to_etc1_device.argtypes = [_vp, _sz, _vp]
+        if not LIB_OVERRIDDEN or hasattr(L, "icamd_transcode_dxt5_to_etc2_rgba8"):  # DXT5 -> ETC2 RGBA8 entry points
+            L.icamd_transcode_dxt5_to_etc2_rgba8.restype = _ci
+            L.icamd_transcode_dxt5_to_etc2_rgba8.argtypes = [_vp, _sz]
+            L.icamd_transcode_dxt5_to_etc2_rgba8_device.restype = _ci
+            L.icamd_transcode_dxt5_to_etc2_rgba8_device.argtypes = [_vp, _sz, _vp]
         L.icamd_compress_batch.restype = _ci
         L.icamd_compress_batch.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _ci, _vp]
         L.icamd_pvrtc2_encode_region_device.restype = _ci
@@ -390,6 +395,23 @@ def transcode_dxt1_to_etc1_host(blocks):
     b = np.frombuffer(blocks, np.uint8).copy()
     st = lib().icamd_transcode_dxt1_to_etc1(b.ctypes.data, b.size)
     return b.tobytes() if _check(st, "icamd_transcode_dxt1_to_etc1") else None
+
+
+def transcode_dxt5_to_etc2_rgba8_host(blocks):
+    """icamd_transcode_dxt5_to_etc2_rgba8 (extension): DXT5 blocks (bytes-like) -> ETC2 RGBA8 blocks of the same size; bytes
+    past the last whole 16-byte block come back unchanged."""
+    import numpy as np
+    b = np.frombuffer(blocks, np.uint8).copy()
+    st = lib().icamd_transcode_dxt5_to_etc2_rgba8(b.ctypes.data, b.size)
+    return b.tobytes() if _check(st, "icamd_transcode_dxt5_to_etc2_rgba8") else None
+
+
+def transcode_dxt5_to_etc2_rgba8_device(t, stream=None):
+    """icamd_transcode_dxt5_to_etc2_rgba8_device (extension): the DXT5 blocks in `t` (a contiguous torch.uint8 CUDA tensor whose
+    storage is 16-byte aligned) become ETC2 RGBA8 blocks IN PLACE; returns `t`.  No synchronisation."""
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    st = lib().icamd_transcode_dxt5_to_etc2_rgba8_device(ctypes.c_void_p(t.data_ptr()), t.numel(), _stream_handle(stream))
+    return t if _check(st, "icamd_transcode_dxt5_to_etc2_rgba8_device") else None
 
 
 def pvrtc_encode_region_device(src, size, first_block, n_blocks, *, out=None, stream=None):

@@ -416,9 +416,11 @@ ICAMD_DEV void decode_block_rows(const uint32_t *w, bool swap, uint32_t rows[4][
 //     are gathered straight into ETC bit order (bit 4x + y, etc.cc:131-137) by v_dot4 with power-of-two weights, and the
 //     table look-up is three v_bfi per plane and sub-block.
 // Bit-exact with decode_dxt_colors + encode_etc1_block(px, 3) (checked block by block in tests/host_emul).
+// ALWAYS4: the palette of a DXT5 colour word, which has no three-colour mode (transcode5_block.h); nothing else differs.
+template <bool ALWAYS4 = false>
 ICAMD_DEV Out8 transcode_dxt1_block_to_etc1(uint32_t w0, uint32_t bits) {
   uint32_t P[3];
-  dxt_palette_planes(w0, false, P);
+  dxt_palette_planes(w0, ALWAYS4, P);
   // the four palette colours as pixels (R | G << 8 | B << 16)
   const uint32_t t01 = perm(P[1], P[0], 0x05010400u), t23 = perm(P[1], P[0], 0x07030602u);  // R G R G of entries (0, 1) / (2, 3)
   const uint32_t col[4] = { perm(P[2], t01, 0x0c040100u), perm(P[2], t01, 0x0c050302u),

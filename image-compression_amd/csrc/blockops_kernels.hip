@@ -1,8 +1,9 @@
-// blockops_kernels.hip -- Pad / Downsample / DXT1->ETC1 transcode kernels: one output
+// blockops_kernels.hip -- Pad / Downsample / DXT1->ETC1 and DXT5->ETC2 RGBA8 transcode kernels: one output
 // block per lane, coalesced 8/16-byte block loads and stores.  See blockops_block.h for the per-block math and
 // blockops_plan.h for which kernel a call gets, with which grid: the launchers at the end of this file run what the plan says.
 #include <cstdlib>
 #include "blockops_block.h"
+#include "transcode5_block.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
@@ -280,6 +281,21 @@ extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_to
   blocks[k] = make_uint2(o.lo, o.hi);
 }
 
+// DXT5 -> ETC2 RGBA8 in place (EXTENSION; transcode5_block.h): one block per lane, one 16-byte load and one
+// 16-byte store.  One-wave workgroups, as the kernels that run an ETC1 search (blockops_plan.h runs_etc1_search): the kernel is
+// the EAC search -- up to 144 candidates of 139 VALU instructions each as compiled, nothing in LDS, two dwords of state -- whose length depends on
+// the content (a wave of flat or 0 / 255 alpha leaves after the first candidates), and a one-wave workgroup gives its slot back
+// when it is done instead of waiting for the slowest of four.
+extern "C" __global__ void __launch_bounds__(kSearchLanes) icamd_transcode_dxt5_to_etc2_rgba8_kernel(uint4 *blocks, uint32_t n) {
+  const uint32_t k = blockIdx.x * kSearchLanes + threadIdx.x;
+  if (k >= n) return;
+  const uint4 b = blocks[k];
+  const uint32_t w[4] = { b.x, b.y, b.z, b.w };
+  uint32_t o[4];
+  transcode_dxt5_block_to_etc2_rgba8(w, o);
+  blocks[k] = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 // ICAMD_PAD_BORDER_QUAD=0: one lane per pad block, the r04 form; read once.  Kept: the GPU tests run both forms through it.
 static bool pad_border_quad() {
   static const bool on = [] { const char *e = getenv("ICAMD_PAD_BORDER_QUAD"); return !(e && e[0] == '0'); }();
@@ -350,6 +366,17 @@ hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint64_t n_blocks, hipStr
     if (err != hipSuccess) return;
     hipLaunchKernelGGL(icamd_dxt1_to_etc1_kernel, dim3((uint32_t)((count + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup)),
                        dim3(kThreadsPerWorkgroup), 0, stream, static_cast<uint2 *>(blocks) + first, (uint32_t)count);
+    err = hipGetLastError();
+  });
+  return err;
+}
+
+hipError_t launch_transcode_dxt5_to_etc2_rgba8(void *blocks, uint64_t n_blocks, hipStream_t stream) {
+  hipError_t err = hipSuccess;
+  for_chunks(n_blocks, kTranscode16Chunk, [&](uint64_t first, uint64_t count) {
+    if (err != hipSuccess) return;
+    hipLaunchKernelGGL(icamd_transcode_dxt5_to_etc2_rgba8_kernel, dim3((uint32_t)((count + kSearchLanes - 1) / kSearchLanes)),
+                       dim3(kSearchLanes), 0, stream, static_cast<uint4 *>(blocks) + first, (uint32_t)count);
     err = hipGetLastError();
   });
   return err;

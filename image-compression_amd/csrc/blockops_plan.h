@@ -24,6 +24,8 @@ constexpr uint64_t kLaunchBlockLimit = 1ull << 31;     // a launch indexes its w
 constexpr uint32_t kDownsampleQuadMaxBlocks = 36864;
 constexpr uint32_t kRowTileMinCols = kBlockOpLanes;    // row tiles where an output row fills a workgroup
 constexpr uint64_t kTranscodeChunk = 1ull << 30;       // blocks per transcode launch (32-bit block index in the kernel)
+// blocks per DXT5 -> ETC2 RGBA8 transcode launch: 16-byte blocks, 32-bit block index in the kernel, 2^24 one-wave workgroups
+constexpr uint64_t kTranscode16Chunk = 1ull << 30;
 constexpr uint32_t kFillBatch = 64;                    // images per batched fill launch (their blocks travel as kernel arguments)
 constexpr uint32_t kFillWorkgroups = 256u * 64u;       // single fill: 8 waves on every SIMD several times over; the loop covers the rest
 constexpr uint32_t kFillBatchWorkgroups = 256u * 32u;  // batched fill: ~8 waves on every SIMD over the whole launch

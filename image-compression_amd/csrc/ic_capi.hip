@@ -1023,6 +1023,18 @@ int icamd_transcode_dxt1_to_etc1_device(void *d_blocks, size_t n_bytes, void *hi
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 
+// EXTENSION (include/ic_amd.h): DXT5 -> ETC2 RGBA8, 16-byte blocks in place
+int icamd_transcode_dxt5_to_etc2_rgba8_device(void *d_blocks, size_t n_bytes, void *hip_stream) try {
+  if (!d_blocks) return ICAMD_FALSE;
+  if (reinterpret_cast<uintptr_t>(d_blocks) % 16u) return fail(ICAMD_ERR_ARG, "block pointer must be 16-byte aligned");
+  if (n_bytes < 16) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  ICAMD_HIP(icamd::launch_transcode_dxt5_to_etc2_rgba8(d_blocks, n_bytes / 16, static_cast<hipStream_t>(hip_stream)),
+            "launch transcode dxt5 -> etc2 rgba8");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
 int icamd_pad(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, const uint8_t *blocks,
               uint32_t ph, uint32_t pw, uint8_t *out, size_t out_size) try {
   int codec;
@@ -1051,6 +1063,15 @@ int icamd_transcode_dxt1_to_etc1(uint8_t *blocks, size_t n_bytes) try {
   const size_t whole = n_bytes - n_bytes % 8;
   return staged_blockop(tls_staging(), blocks, n_bytes, blocks, whole, whole, true, [&](void *din, void *, hipStream_t s) {
     return icamd_transcode_dxt1_to_etc1_device(din, n_bytes, s);
+  });
+} ICAMD_ABI_CATCH
+
+int icamd_transcode_dxt5_to_etc2_rgba8(uint8_t *blocks, size_t n_bytes) try {
+  if (!blocks) return ICAMD_FALSE;
+  if (n_bytes < 16) return ICAMD_OK;
+  const size_t whole = n_bytes - n_bytes % 16;
+  return staged_blockop(tls_staging(), blocks, n_bytes, blocks, whole, whole, true, [&](void *din, void *, hipStream_t s) {
+    return icamd_transcode_dxt5_to_etc2_rgba8_device(din, n_bytes, s);
   });
 } ICAMD_ABI_CATCH
 

@@ -10,6 +10,11 @@ namespace image_codec_compression {
 
 void TranscodeDxt1ToEtc1(CompressedImage *image);
 
+// EXTENSION (the reference has no such function): in-place DXT5 -> ETC2 RGBA8.  Every 16-byte DXT5 block of the image data becomes
+// the ETC2 RGBA8 block (EAC alpha word + ETC1-compatible colour word, kHeuristic) of the pixels it decodes to; see
+// icamd_transcode_dxt5_to_etc2_rgba8 in ic_amd.h.  Data only: the metadata, format name included, is left untouched.
+void TranscodeDxt5ToEtc2Rgba8(CompressedImage *image);
+
 }  // namespace image_codec_compression
 
 #endif  // IMAGE_COMPRESSION_PUBLIC_DXTC_TO_ETC_TRANSCODER

@@ -455,4 +455,9 @@ void TranscodeDxt1ToEtc1(CompressedImage *image) {  // dxtc_to_etc_transcoder.cc
                "icamd_transcode_dxt1_to_etc1");
 }
 
+void TranscodeDxt5ToEtc2Rgba8(CompressedImage *image) {  // EXTENSION: in place, data only
+  ReportStatus(icamd_transcode_dxt5_to_etc2_rgba8(image->GetMutableData(), image->GetDataSize()),
+               "icamd_transcode_dxt5_to_etc2_rgba8");
+}
+
 }  // namespace image_codec_compression

@@ -240,7 +240,8 @@ int icamd_pvrtc2_decompress(uint32_t size, const uint8_t *blocks, size_t blocks_
  * Compressor::Pad (compressor.h:104-106; helper.h:393-477; pad functors dxtc.cc:594-696, etc.cc:645-698) for the
  * case that really pads: the source grid covers (compressed_height, compressed_width) pixels, the result
  * (padded_height, padded_width); out_size must be the result's data size.  Device pointers of the block-domain
- * operations (pad, downsample: 4-byte; transcode: 8-byte) must be aligned, else ICAMD_ERR_ARG; the decoders accept
+ * operations (pad, downsample: 4-byte; DXT1 -> ETC1 transcode: 8-byte; DXT5 -> ETC2 RGBA8 transcode: 16-byte) must be aligned,
+ * else ICAMD_ERR_ARG; the decoders accept
  * any pointer.  Returns ICAMD_FALSE for PVRTC and when a
  * padded dimension has fewer blocks than the source (the reference either just duplicates the image, which the caller
  * does itself, or overruns its buffer). */
@@ -308,6 +309,24 @@ int icamd_copy_subimage(int compressor, int format, uint32_t compressed_height, 
 /* TranscodeDxt1ToEtc1 (public/dxtc_to_etc_transcoder.h:24; dxtc_to_etc_transcoder.cc:29-40): in place. */
 int icamd_transcode_dxt1_to_etc1_device(void *d_blocks, size_t n_bytes, void *hip_stream);
 int icamd_transcode_dxt1_to_etc1(uint8_t *blocks, size_t n_bytes);
+
+/* EXTENSION (the reference's only transcoder is DXT1 -> ETC1): DXT5 -> ETC2 RGBA8 (ICAMD_ETC2_RGBA8) in place, in the compressed
+ * domain.  Both formats keep a block in 16 bytes, alpha word first, colour word second.  DEFINITION: every whole
+ * 16-byte block B of the buffer is replaced by exactly the 16 bytes that
+ *   icamd_encode_device(ICAMD_ETC2_RGBA8, ICAMD_ETC_HEURISTIC, 4 components, swap_rb = 0, ...)
+ * writes for the 4 x 4 RGBA8 image that icamd_decode_device(ICAMD_DXT5, swap_rb = 0) produces from B:
+ *   bytes 8..15  EncodeEtc1Block(kHeuristic) of the decoded colours (a DXT5 colour word always has four colours, so for c0 <= c1
+ *                this differs from icamd_transcode_dxt1_to_etc1 of the same eight bytes; for c0 > c1 it is the same);
+ *   bytes 0..7   the EAC search of ICAMD_ETC2_RGBA8 on the sixteen decoded alphas (the reference's truncating DecodeAlphaValues,
+ *                0 and 255 in the six-value mode): lo and hi are the extremes of the alphas the texels use, the smallest
+ *                (sse, table, multiplier, base) wins, every texel takes the smallest index at its minimum, multiplier 0 is never
+ *                written.
+ * No pixel is materialised: the search runs on the alpha word's eight palette values weighted by their use.
+ * NULL -> ICAMD_FALSE; a device pointer that is not 16-byte aligned -> ICAMD_ERR_ARG; n_bytes < 16 -> ICAMD_OK, nothing touched;
+ * otherwise n_bytes / 16 blocks are transcoded and the trailing n_bytes % 16 bytes are left as they were.  The device form is
+ * stream-ordered, does not synchronise and can be captured into a graph. */
+int icamd_transcode_dxt5_to_etc2_rgba8_device(void *d_blocks, size_t n_bytes, void *hip_stream);
+int icamd_transcode_dxt5_to_etc2_rgba8(uint8_t *blocks, size_t n_bytes);
 
 /* ---- multi-GPU from one process: a batch of independent images, host buffers ----
  * Image i is compressed exactly like icamd_compress(compressor, ..., buffers[i], outs[i], out_size) on device
