@@ -1,7 +1,7 @@
 """image-compression_amd: MI355X (gfx950) block-encode backend -- Python plumbing over the C ABI.
 
-This module only *binds* libic_amd.so (include/ic_amd.h) with ctypes and passes torch device
-pointers / streams through it.  All encoding happens in the hand-written HIP kernels inside the
+This module only *binds* libic_amd.so (include/ic_amd.h) with ctypes -- the prototypes are the table in abi.py -- and
+passes torch device pointers / streams through it.  All encoding happens in the hand-written HIP kernels inside the
 shared library; there is no Python or CPU implementation here, and importing fails loudly if the
 library has not been built (python __graft_entry__.py / make -C image-compression_amd).
 
@@ -13,6 +13,8 @@ import os
 import threading
 
 import torch  # must precede CDLL: libic_amd.so then binds to the HIP runtime torch already loaded
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT_LIB_PATH = os.path.join(_HERE, "libic_amd.so")
@@ -40,22 +42,7 @@ BC4, BC5 = 5, 6
 ETC2_RGBA8 = 16
 OK, FALSE = 0, 1
 
-EXPORTS = [
-    "icamd_compute_compressed_data_size", "icamd_supports_format", "icamd_encoded_size", "icamd_compress",
-    "icamd_compress_and_pad", "icamd_compress_device", "icamd_compress_and_pad_device", "icamd_encode_device",
-    "icamd_decode_device", "icamd_decompress", "icamd_pad_device", "icamd_pad", "icamd_downsample_device",
-    "icamd_downsample", "icamd_downsample_batch_device", "icamd_pad_batch_device", "icamd_create_solid_batch_device", "icamd_copy_subimage_batch_device", "icamd_transcode_dxt1_to_etc1_device", "icamd_transcode_dxt1_to_etc1", "icamd_transcode_dxt5_to_etc2_rgba8_device", "icamd_transcode_dxt5_to_etc2_rgba8", "icamd_compress_batch", "icamd_pvrtc2_encode_region_device", "icamd_pvrtc2_workspace_size", "icamd_pvrtc4_workspace_size",
-    "icamd_pvrtc2_set_workspace", "icamd_pvrtc2_tune", "icamd_host_register", "icamd_host_unregister", "icamd_pvrtc2_decompress", "icamd_device_count", "icamd_last_error", "icamd_version", "icamd_kernel_name",
-    "icamd_create_solid_device", "icamd_create_solid", "icamd_copy_subimage_device", "icamd_copy_subimage",
-    "icamd_encode_batch_sharded_device", "icamd_clock_probe_device", "icamd_wall_clock_rate_khz",
-    "icamd_container_size", "icamd_container_write",
-    "icamd_rccl_available", "icamd_rccl_get_unique_id", "icamd_rccl_comm_init", "icamd_rccl_comm_destroy", "icamd_gather_blocks_rccl",
-    "icamd_mip_max_levels", "icamd_mip_chain_size", "icamd_mip_workspace_size", "icamd_encode_mips_device",
-    "icamd_mip_pyramid_device", "icamd_compress_mips",
-    "icamd_encode_mips_filtered_device", "icamd_mip_pyramid_filtered_device", "icamd_compress_mips_filtered",
-    "icamd_mip_kernel_name",
-    "icamd_measure_error_device", "icamd_measure_error", "icamd_metric_kernel_name",
-]
+EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
 RCCL_UNIQUE_ID_BYTES = 128
 # mip filters (bits; include/ic_amd.h, "mip filters"): 0 is the box filter of the plain mip entry points
 MIP_FILTER_BOX, MIP_FILTER_SRGB, MIP_FILTER_ALPHA_WEIGHTED = 0, 1, 2
@@ -63,7 +50,6 @@ MIP_FILTER_NORMAL = 4  # BC5 chains and the RG8 pyramid only; not combinable
 MIP_PYRAMID = -1  # `codec` of mip_kernel_name for the pixel pyramid
 CONTAINER_DDS, CONTAINER_KTX, CONTAINER_PKM, CONTAINER_PVR = 0, 1, 2, 3
 
-_u32, _sz, _vp, _ci = ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
 _lib = None
 _tls = threading.local()  # per-thread state mirrored from the C side (the PVRTC workspace override is thread-local there)
 
@@ -78,151 +64,25 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError("libic_amd.so is not built (%s); run `python __graft_entry__.py` or "
                               "`make -C image-compression_amd` -- there is no fallback path" % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        L.icamd_compute_compressed_data_size.restype = _sz
-        L.icamd_compute_compressed_data_size.argtypes = [_ci, _ci, _u32, _u32]
-        L.icamd_supports_format.restype = _ci
-        L.icamd_supports_format.argtypes = [_ci, _ci]
-        L.icamd_encoded_size.restype = _sz
-        L.icamd_encoded_size.argtypes = [_ci, _u32, _u32]
-        L.icamd_compress.restype = _ci
-        L.icamd_compress.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz]
-        L.icamd_compress_and_pad.restype = _ci
-        L.icamd_compress_and_pad.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
-        L.icamd_compress_device.restype = _ci
-        L.icamd_compress_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _vp]
-        L.icamd_compress_and_pad_device.restype = _ci
-        L.icamd_compress_and_pad_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp]
-        L.icamd_container_size.restype = _sz
-        L.icamd_container_size.argtypes = [_ci, _ci, _u32, _u32, _u32]
-        L.icamd_container_write.restype = _ci
-        L.icamd_container_write.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _vp, _sz]
-        L.icamd_encode_device.restype = _ci
-        L.icamd_encode_device.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
-        L.icamd_decode_device.restype = _ci
-        L.icamd_decode_device.argtypes = [_ci, _ci, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
-        L.icamd_decompress.restype = _ci
-        L.icamd_decompress.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _sz, _vp, _sz]
-        L.icamd_pad.restype = _ci
-        L.icamd_pad.argtypes = [_ci, _ci, _ci, _u32, _u32, _vp, _u32, _u32, _vp, _sz]
-        L.icamd_pad_device.restype = _ci
-        L.icamd_pad_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _vp, _u32, _u32, _vp, _sz, _vp]
-        L.icamd_downsample.restype = _ci
-        L.icamd_downsample.argtypes = [_ci, _ci, _ci, _u32, _u32, _vp, _vp, _sz]
-        L.icamd_downsample_device.restype = _ci
-        L.icamd_downsample_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _vp, _vp, _sz, _vp]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_downsample_batch_device"):  # r04 entry point
-            L.icamd_downsample_batch_device.restype = _ci
-            L.icamd_downsample_batch_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _sz, _vp, _sz, _sz, _vp]
-        L.icamd_transcode_dxt1_to_etc1.restype = _ci
-        L.icamd_transcode_dxt1_to_etc1.argtypes = [_vp, _sz]
-        L.icamd_transcode_dxt1_to_etc1_device.restype = _ci
-        L.icamd_transcode_dxt1_to_etc1_device.argtypes = [_vp, _sz, _vp]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_transcode_dxt5_to_etc2_rgba8"):  # DXT5 -> ETC2 RGBA8 entry points
-            L.icamd_transcode_dxt5_to_etc2_rgba8.restype = _ci
-            L.icamd_transcode_dxt5_to_etc2_rgba8.argtypes = [_vp, _sz]
-            L.icamd_transcode_dxt5_to_etc2_rgba8_device.restype = _ci
-            L.icamd_transcode_dxt5_to_etc2_rgba8_device.argtypes = [_vp, _sz, _vp]
-        L.icamd_compress_batch.restype = _ci
-        L.icamd_compress_batch.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _ci, _vp]
-        L.icamd_pvrtc2_encode_region_device.restype = _ci
-        L.icamd_pvrtc2_encode_region_device.argtypes = [_u32, _u32, _u32, _vp, _vp, _vp]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_pvrtc2_workspace_size"):  # older A/B builds lack it
-            L.icamd_pvrtc2_workspace_size.restype = _sz
-            L.icamd_pvrtc2_workspace_size.argtypes = [_u32, _u32]
-            if hasattr(L, "icamd_pvrtc4_workspace_size"):
-                L.icamd_pvrtc4_workspace_size.restype = _sz
-                L.icamd_pvrtc4_workspace_size.argtypes = [_u32, _u32]
-            L.icamd_pvrtc2_set_workspace.restype = _ci
-            L.icamd_pvrtc2_set_workspace.argtypes = [_vp, _sz]
-            L.icamd_host_register.restype = _ci
-            L.icamd_host_register.argtypes = [_vp, _sz]
-            L.icamd_host_unregister.restype = _ci
-            L.icamd_host_unregister.argtypes = [_vp]
-            L.icamd_pvrtc2_decompress.restype = _ci
-            L.icamd_pvrtc2_decompress.argtypes = [_u32, _vp, _sz, _vp, _sz]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_pvrtc2_tune"):  # r05 entry point (older A/B builds lack it)
-            L.icamd_pvrtc2_tune.restype = _ci
-            L.icamd_pvrtc2_tune.argtypes = [_ci, _ci]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_pad_batch_device"):  # r05 entry points
-            L.icamd_pad_batch_device.restype = _ci
-            L.icamd_pad_batch_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _sz, _u32, _u32, _vp, _sz, _sz, _vp]
-            L.icamd_create_solid_batch_device.restype = _ci
-            L.icamd_create_solid_batch_device.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _sz, _vp]
-            L.icamd_copy_subimage_batch_device.restype = _ci
-            L.icamd_copy_subimage_batch_device.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _sz, _u32, _u32, _u32, _u32, _vp, _sz,
-                                                           _sz, _vp]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_create_solid_device"):  # r03 entry points
-            L.icamd_create_solid_device.restype = _ci
-            L.icamd_create_solid_device.argtypes = [_ci, _ci, _u32, _u32, _vp, _vp, _sz, _vp]
-            L.icamd_create_solid.restype = _ci
-            L.icamd_create_solid.argtypes = [_ci, _ci, _u32, _u32, _vp, _vp, _sz]
-            L.icamd_copy_subimage_device.restype = _ci
-            L.icamd_copy_subimage_device.argtypes = [_ci, _ci, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]
-            L.icamd_copy_subimage.restype = _ci
-            L.icamd_copy_subimage.argtypes = [_ci, _ci, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz]
-            L.icamd_encode_batch_sharded_device.restype = _ci
-            L.icamd_encode_batch_sharded_device.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _ci,
-                                                            _ci, _vp, _sz, _vp]
-            L.icamd_clock_probe_device.restype = _ci
-            L.icamd_clock_probe_device.argtypes = [_vp, _u32, _vp]
-            L.icamd_wall_clock_rate_khz.restype = _u32
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_gather_blocks_rccl"):  # r06 entry points
-            L.icamd_rccl_available.restype = _ci
-            L.icamd_rccl_available.argtypes = []
-            L.icamd_rccl_get_unique_id.restype = _ci
-            L.icamd_rccl_get_unique_id.argtypes = [_vp]
-            L.icamd_rccl_comm_init.restype = _ci
-            L.icamd_rccl_comm_init.argtypes = [ctypes.POINTER(_vp), _ci, _ci, _vp]
-            L.icamd_rccl_comm_destroy.restype = _ci
-            L.icamd_rccl_comm_destroy.argtypes = [_vp]
-            L.icamd_gather_blocks_rccl.restype = _ci
-            L.icamd_gather_blocks_rccl.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_encode_mips_device"):  # mip-chain entry points
-            L.icamd_mip_max_levels.restype = _u32
-            L.icamd_mip_max_levels.argtypes = [_u32, _u32]
-            L.icamd_mip_chain_size.restype = _sz
-            L.icamd_mip_chain_size.argtypes = [_ci, _u32, _u32, _u32, _vp]
-            L.icamd_mip_workspace_size.restype = _sz
-            L.icamd_mip_workspace_size.argtypes = [_ci, _ci, _u32, _u32, _u32, _u32]
-            L.icamd_encode_mips_device.restype = _ci
-            L.icamd_encode_mips_device.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp,
-                                                   _sz, _vp]
-            L.icamd_mip_pyramid_device.restype = _ci
-            L.icamd_mip_pyramid_device.argtypes = [_ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
-            L.icamd_compress_mips.restype = _ci
-            L.icamd_compress_mips.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_encode_mips_filtered_device"):  # mip-filter entry points
-            L.icamd_encode_mips_filtered_device.restype = _ci
-            L.icamd_encode_mips_filtered_device.argtypes = [_ci, _ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp,
-                                                            _vp, _sz, _vp]
-            L.icamd_mip_pyramid_filtered_device.restype = _ci
-            L.icamd_mip_pyramid_filtered_device.argtypes = [_ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]
-            L.icamd_compress_mips_filtered.restype = _ci
-            L.icamd_compress_mips_filtered.argtypes = [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]
-            L.icamd_mip_kernel_name.restype = ctypes.c_char_p
-            L.icamd_mip_kernel_name.argtypes = [_ci, _ci, _ci]
-        if not LIB_OVERRIDDEN or hasattr(L, "icamd_measure_error_device"):  # quality-metric entry points
-            L.icamd_measure_error_device.restype = _ci
-            L.icamd_measure_error_device.argtypes = [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp,
-                                                     _vp]
-            L.icamd_measure_error.restype = _ci
-            L.icamd_measure_error.argtypes = [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _vp]
-            L.icamd_metric_kernel_name.restype = ctypes.c_char_p
-            L.icamd_metric_kernel_name.argtypes = [_ci, _ci]
-        L.icamd_device_count.restype = _ci
-        L.icamd_last_error.restype = ctypes.c_char_p
-        L.icamd_version.restype = ctypes.c_char_p
-        L.icamd_kernel_name.restype = ctypes.c_char_p
-        L.icamd_kernel_name.argtypes = [_ci, _ci]
-        _lib = L
+        # a library swapped in for an A/B run may lack newer entry points; the product library may not
+        _lib = abi.bind(ctypes.CDLL(LIB_PATH), allow_missing=LIB_OVERRIDDEN)
     return _lib
 
 
+def _error(status, what):
+    return BackendError("%s failed with status %d: %s" % (what, status, lib().icamd_last_error().decode()))
+
+
 def _check(status, what):
+    """True for ICAMD_OK, False for the reference's `false`; a negative status raises."""
     if status < 0:
-        raise BackendError("%s failed with status %d: %s" % (what, status, lib().icamd_last_error().decode()))
+        raise _error(status, what)
     return status == OK
+
+
+def _require_ok(status, what):
+    if status != OK:
+        raise _error(status, what)
 
 
 def compute_compressed_data_size(compressor, fmt, height, width):
@@ -242,6 +102,39 @@ def _stream_handle(stream=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _ptr(t):
+    """A tensor's device address; the prototypes' c_void_p parameters take the plain integer."""
+    return t.data_ptr()
+
+
+def _assert_u8_cuda(t):
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+
+
+def _grid_bytes(compressor, fmt, height, width):
+    """Bytes of the block grid of a height x width image of (compressor, fmt)."""
+    block = 8 if (compressor == COMPRESSOR_ETC or fmt in (RGB, BGR)) else 16
+    return ((height + 3) // 4) * ((width + 3) // 4) * block
+
+
+def _host_u8(buffer, copy=False):
+    """bytes / bytearray / memoryview / numpy array -> its bytes as a flat contiguous numpy uint8 array: a view of the
+    caller's memory where that is contiguous, a private (writable) copy with copy=True."""
+    import numpy as np
+    a = np.ascontiguousarray(buffer) if isinstance(buffer, np.ndarray) else np.frombuffer(buffer, np.uint8)
+    a = a.reshape(-1).view(np.uint8)
+    return a.copy() if copy else a
+
+
+def _compress_out_size(compressor, fmt, height, width, padded, out_size):
+    """out_size of Compress (padded None) / CompressAndPad: the caller's, else the data size of the image or padded grid."""
+    if out_size is not None:
+        return out_size
+    if padded is not None:
+        height, width = max(height, padded[0]), max(width, padded[1])
+    return compute_compressed_data_size(compressor, fmt, height, width)
+
+
 def encode_device(codec, src, height, width, src_components, *, swap_rb=False, etc_strategy=ETC_SMALLER_ERROR,
                   grid_height=None, grid_width=None, row_stride_bytes=None, n_images=1,
                   src_image_stride_bytes=None, out=None, stream=None):
@@ -249,7 +142,7 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
     Returns the output tensor [n_images, encoded_size] (device).  No synchronisation.
     BC4 reads R from 1..4-byte pixels, BC5 reads R and G from 2..4-byte pixels: R = byte 0 (byte 2 with swap_rb, which needs
     3 or 4 bytes per pixel), G = byte 1."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    _assert_u8_cuda(src)
     gh = height if grid_height is None else max(grid_height, height)
     gw = width if grid_width is None else max(grid_width, width)
     stride = width * src_components if row_stride_bytes is None else row_stride_bytes
@@ -258,8 +151,7 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
     if out is None:
         out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
     st = lib().icamd_encode_device(codec, etc_strategy, src_components, int(swap_rb), height, width, gh, gw, stride,
-                                   n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
-                                   ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
+                                   n_images, img_stride, per, _ptr(src), _ptr(out), _stream_handle(stream))
     if not _check(st, "icamd_encode_device"):
         return None
     return out
@@ -269,21 +161,14 @@ def compress_device(compressor, fmt, src, height, width, *, padding_bytes_per_ro
                     etc_strategy=ETC_SMALLER_ERROR, padded=None, out_size=None, stream=None):
     """Compressor::Compress / CompressAndPad on a device-resident image; returns a device uint8 tensor or None
     where the reference returns false."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    _assert_u8_cuda(src)
     if padded is None:
-        n = compute_compressed_data_size(compressor, fmt, height, width) if out_size is None else out_size
+        fn, dims = lib().icamd_compress_device, (height, width)
     else:
-        n = compute_compressed_data_size(compressor, fmt, max(height, padded[0]), max(width, padded[1])) \
-            if out_size is None else out_size
+        fn, dims = lib().icamd_compress_and_pad_device, (height, width, padded[0], padded[1])
+    n = _compress_out_size(compressor, fmt, height, width, padded, out_size)
     out = torch.empty((max(n, 1),), dtype=torch.uint8, device=src.device)
-    if padded is None:
-        st = lib().icamd_compress_device(compressor, etc_strategy, fmt, height, width, padding_bytes_per_row,
-                                         ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()), n,
-                                         _stream_handle(stream))
-    else:
-        st = lib().icamd_compress_and_pad_device(compressor, etc_strategy, fmt, height, width, padded[0], padded[1],
-                                                 padding_bytes_per_row, ctypes.c_void_p(src.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), n, _stream_handle(stream))
+    st = fn(compressor, etc_strategy, fmt, *dims, padding_bytes_per_row, _ptr(src), _ptr(out), n, _stream_handle(stream))
     if not _check(st, "icamd_compress_device"):
         return None
     return out[:n]
@@ -304,57 +189,42 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
     Returns bytes, or None where the reference returns false.  `out`: a caller-owned numpy uint8 array of the exact
     output size to write into (returned as is instead of bytes)."""
     import numpy as np
-    src = np.ascontiguousarray(np.frombuffer(buffer, dtype=np.uint8) if not isinstance(buffer, np.ndarray) else buffer)
+    src = _host_u8(buffer)
     if padded is None:
-        n = compute_compressed_data_size(compressor, fmt, height, width) if out_size is None else out_size
+        fn, dims = lib().icamd_compress, (height, width)
     else:
-        n = compute_compressed_data_size(compressor, fmt, max(height, padded[0]), max(width, padded[1])) \
-            if out_size is None else out_size
-    if out is not None:
+        fn, dims = lib().icamd_compress_and_pad, (height, width, padded[0], padded[1])
+    n = _compress_out_size(compressor, fmt, height, width, padded, out_size)
+    if out is None:
+        dst = np.zeros(max(n, 1), np.uint8)
+    else:
         assert out.dtype == np.uint8 and out.size == n and out.flags["C_CONTIGUOUS"]
-        if padded is None:
-            st = lib().icamd_compress(compressor, etc_strategy, fmt, height, width, padding_bytes_per_row,
-                                      src.ctypes.data, out.ctypes.data, n)
-        else:
-            st = lib().icamd_compress_and_pad(compressor, etc_strategy, fmt, height, width, padded[0], padded[1],
-                                              padding_bytes_per_row, src.ctypes.data, out.ctypes.data, n)
-        return out if _check(st, "icamd_compress") else None
-    out = np.zeros(max(n, 1), np.uint8)
-    if padded is None:
-        st = lib().icamd_compress(compressor, etc_strategy, fmt, height, width, padding_bytes_per_row,
-                                  src.ctypes.data, out.ctypes.data, n)
-    else:
-        st = lib().icamd_compress_and_pad(compressor, etc_strategy, fmt, height, width, padded[0], padded[1],
-                                          padding_bytes_per_row, src.ctypes.data, out.ctypes.data, n)
+        dst = out
+    st = fn(compressor, etc_strategy, fmt, *dims, padding_bytes_per_row, src.ctypes.data, dst.ctypes.data, n)
     if not _check(st, "icamd_compress"):
         return None
-    return out[:n].tobytes()
+    return dst[:n].tobytes() if out is None else out
 
 
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    _assert_u8_cuda(blocks)
     comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, BC4: 1, BC5: 2}.get(codec, 3)  # BC4 -> R8, BC5 -> RG8
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)
     st = lib().icamd_decode_device(codec, int(swap_rb), height, width, padding_bytes_per_row, n_images, per_in,
-                                   per_out, ctypes.c_void_p(blocks.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                   _stream_handle(stream))
+                                   per_out, _ptr(blocks), _ptr(out), _stream_handle(stream))
     if not _check(st, "icamd_decode_device"):
         return None
     return out
-
-
-def _block_bytes(compressor, fmt):
-    return 8 if (compressor == COMPRESSOR_ETC or fmt in (RGB, BGR)) else 16
 
 
 def pad_host(compressor, fmt, blocks, compressed_height, compressed_width, padded_height, padded_width,
              etc_strategy=ETC_SMALLER_ERROR):
     """Compressor::Pad for the really-padding case, host buffers.  bytes or None (reference's false)."""
     import numpy as np
-    b = np.frombuffer(blocks, np.uint8)
-    n = ((padded_height + 3) // 4) * ((padded_width + 3) // 4) * _block_bytes(compressor, fmt)
+    b = _host_u8(blocks)
+    n = _grid_bytes(compressor, fmt, padded_height, padded_width)
     out = np.zeros(max(n, 1), np.uint8)
     st = lib().icamd_pad(compressor, etc_strategy, fmt, compressed_height, compressed_width, b.ctypes.data,
                          padded_height, padded_width, out.ctypes.data, n)
@@ -363,9 +233,9 @@ def pad_host(compressor, fmt, blocks, compressed_height, compressed_width, padde
 
 def downsample_host(compressor, fmt, blocks, height, width, etc_strategy=ETC_SMALLER_ERROR):
     import numpy as np
-    b = np.frombuffer(blocks, np.uint8)
+    b = _host_u8(blocks)
     dh, dw = (height + 1) // 2, (width + 1) // 2
-    n = ((dh + 3) // 4) * ((dw + 3) // 4) * _block_bytes(compressor, fmt)
+    n = _grid_bytes(compressor, fmt, dh, dw)
     out = np.zeros(max(n, 1), np.uint8)
     st = lib().icamd_downsample(compressor, etc_strategy, fmt, height, width, b.ctypes.data, out.ctypes.data, n)
     return out[:n].tobytes() if _check(st, "icamd_downsample") else None
@@ -374,25 +244,23 @@ def downsample_host(compressor, fmt, blocks, height, width, etc_strategy=ETC_SMA
 def downsample_device(compressor, fmt, blocks, height, width, *, etc_strategy=ETC_SMALLER_ERROR, n_images=1, stream=None):
     """Compressor::Downsample on device-resident block grids: `blocks` = torch.uint8 CUDA tensor [n_images, bytes of one
     height x width image] (contiguous); returns [n_images, bytes of the halved image] or None where the reference refuses."""
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    _assert_u8_cuda(blocks)
     dh, dw = (height + 1) // 2, (width + 1) // 2
-    per_out = ((dh + 3) // 4) * ((dw + 3) // 4) * _block_bytes(compressor, fmt)
+    per_out = _grid_bytes(compressor, fmt, dh, dw)
     if n_images < 1 or blocks.numel() % n_images:
         raise ValueError("downsample_device: %d bytes do not divide into %d images" % (blocks.numel(), n_images))
     per_in = blocks.numel() // n_images
-    need = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
-    if per_in < need:  # the kernel's 16-byte block loads would run past the tensor (ADVICE r04)
+    need = _grid_bytes(compressor, fmt, height, width)
+    if per_in < need:  # the kernel's 16-byte block loads would run past the tensor
         raise ValueError("downsample_device: %d bytes per image, a %d x %d image has %d" % (per_in, height, width, need))
     out = torch.empty((n_images, per_out), dtype=torch.uint8, device=blocks.device)
     st = lib().icamd_downsample_batch_device(compressor, etc_strategy, fmt, height, width, n_images,
-                                             ctypes.c_void_p(blocks.data_ptr()), per_in, ctypes.c_void_p(out.data_ptr()),
-                                             per_out, per_out, _stream_handle(stream))
+                                             _ptr(blocks), per_in, _ptr(out), per_out, per_out, _stream_handle(stream))
     return out if _check(st, "icamd_downsample_batch_device") else None
 
 
 def transcode_dxt1_to_etc1_host(blocks):
-    import numpy as np
-    b = np.frombuffer(blocks, np.uint8).copy()
+    b = _host_u8(blocks, copy=True)
     st = lib().icamd_transcode_dxt1_to_etc1(b.ctypes.data, b.size)
     return b.tobytes() if _check(st, "icamd_transcode_dxt1_to_etc1") else None
 
@@ -400,8 +268,7 @@ def transcode_dxt1_to_etc1_host(blocks):
 def transcode_dxt5_to_etc2_rgba8_host(blocks):
     """icamd_transcode_dxt5_to_etc2_rgba8 (extension): DXT5 blocks (bytes-like) -> ETC2 RGBA8 blocks of the same size; bytes
     past the last whole 16-byte block come back unchanged."""
-    import numpy as np
-    b = np.frombuffer(blocks, np.uint8).copy()
+    b = _host_u8(blocks, copy=True)
     st = lib().icamd_transcode_dxt5_to_etc2_rgba8(b.ctypes.data, b.size)
     return b.tobytes() if _check(st, "icamd_transcode_dxt5_to_etc2_rgba8") else None
 
@@ -409,8 +276,8 @@ def transcode_dxt5_to_etc2_rgba8_host(blocks):
 def transcode_dxt5_to_etc2_rgba8_device(t, stream=None):
     """icamd_transcode_dxt5_to_etc2_rgba8_device (extension): the DXT5 blocks in `t` (a contiguous torch.uint8 CUDA tensor whose
     storage is 16-byte aligned) become ETC2 RGBA8 blocks IN PLACE; returns `t`.  No synchronisation."""
-    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
-    st = lib().icamd_transcode_dxt5_to_etc2_rgba8_device(ctypes.c_void_p(t.data_ptr()), t.numel(), _stream_handle(stream))
+    _assert_u8_cuda(t)
+    st = lib().icamd_transcode_dxt5_to_etc2_rgba8_device(_ptr(t), t.numel(), _stream_handle(stream))
     return t if _check(st, "icamd_transcode_dxt5_to_etc2_rgba8_device") else None
 
 
@@ -418,11 +285,10 @@ def pvrtc_encode_region_device(src, size, first_block, n_blocks, *, out=None, st
     """icamd_pvrtc2_encode_region_device: blocks [first_block, first_block + n_blocks) of the Z-order output of the
     size x size RGBA8 image `src` (torch.uint8 CUDA tensor).  Returns the [8 * n_blocks] uint8 device tensor, or None
     where the reference would refuse the size.  No synchronisation."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    _assert_u8_cuda(src)
     if out is None:
         out = torch.empty((8 * n_blocks,), dtype=torch.uint8, device=src.device)
-    st = lib().icamd_pvrtc2_encode_region_device(size, first_block, n_blocks, ctypes.c_void_p(src.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
+    st = lib().icamd_pvrtc2_encode_region_device(size, first_block, n_blocks, _ptr(src), _ptr(out), _stream_handle(stream))
     if not _check(st, "icamd_pvrtc2_encode_region_device"):
         return None
     return out
@@ -431,7 +297,7 @@ def pvrtc_encode_region_device(src, size, first_block, n_blocks, *, out=None, st
 def pvrtc_decompress_host(blocks, size):
     """icamd_pvrtc2_decompress (extension): bytes of size x size RGBA8, or None where the sizes are refused."""
     import numpy as np
-    b = np.frombuffer(blocks, np.uint8)
+    b = _host_u8(blocks)
     out = np.zeros(size * size * 4, np.uint8)
     st = lib().icamd_pvrtc2_decompress(size, b.ctypes.data, b.size, out.ctypes.data, out.size)
     return out.tobytes() if _check(st, "icamd_pvrtc2_decompress") else None
@@ -457,12 +323,11 @@ def pvrtc_set_workspace(workspace):
     if workspace is None:
         _tls.workspace = None
         return _check(lib().icamd_pvrtc2_set_workspace(None, 0), "icamd_pvrtc2_set_workspace")
-    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _assert_u8_cuda(workspace)
     if workspace.device.index not in (None, torch.cuda.current_device()):
         raise ValueError("PVRTC workspace lives on %s but the current device is cuda:%d"
                          % (workspace.device, torch.cuda.current_device()))
-    ok = _check(lib().icamd_pvrtc2_set_workspace(ctypes.c_void_p(workspace.data_ptr()), workspace.numel()),
-                "icamd_pvrtc2_set_workspace")
+    ok = _check(lib().icamd_pvrtc2_set_workspace(_ptr(workspace), workspace.numel()), "icamd_pvrtc2_set_workspace")
     # the C side keeps only the raw pointer (per host thread): hold the tensor until the override is cleared, so that
     # a caller dropping its reference cannot leave the library writing into freed memory
     _tls.workspace = workspace if ok else None
@@ -494,11 +359,10 @@ def create_solid_device(compressor, fmt, height, width, color, *, device=None, o
     the reference returns false."""
     c = bytes(bytearray(color))
     buf = (ctypes.c_uint8 * max(len(c), 4))(*c)
-    n = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
+    n = _grid_bytes(compressor, fmt, height, width)
     if out is None:
         out = torch.empty((max(n, 1),), dtype=torch.uint8, device=device or torch.device("cuda", torch.cuda.current_device()))
-    st = lib().icamd_create_solid_device(compressor, fmt, height, width, buf, ctypes.c_void_p(out.data_ptr()), n,
-                                         _stream_handle(stream))
+    st = lib().icamd_create_solid_device(compressor, fmt, height, width, buf, _ptr(out), n, _stream_handle(stream))
     return out[:n] if _check(st, "icamd_create_solid_device") else None
 
 
@@ -507,9 +371,9 @@ def create_solid_batch_device(compressor, fmt, height, width, colors, *, device=
     comps = 3 if fmt in (RGB, BGR) else 4
     flat = bytes(bytearray(b for c in colors for b in bytearray(c)[:comps]))
     buf = (ctypes.c_uint8 * max(len(flat), 4))(*flat)
-    per = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
+    per = _grid_bytes(compressor, fmt, height, width)
     out = torch.empty((len(colors), max(per, 1)), dtype=torch.uint8, device=device or torch.device("cuda", torch.cuda.current_device()))
-    st = lib().icamd_create_solid_batch_device(compressor, fmt, height, width, len(colors), buf, ctypes.c_void_p(out.data_ptr()),
+    st = lib().icamd_create_solid_batch_device(compressor, fmt, height, width, len(colors), buf, _ptr(out),
                                                out.shape[1], per, _stream_handle(stream))
     return out[:, :per] if _check(st, "icamd_create_solid_batch_device") else None
 
@@ -517,31 +381,32 @@ def create_solid_batch_device(compressor, fmt, height, width, colors, *, device=
 def pad_batch_device(compressor, fmt, blocks, compressed_height, compressed_width, padded_height, padded_width, *,
                      etc_strategy=ETC_SMALLER_ERROR, stream=None):
     """icamd_pad_batch_device (extension): blocks = [n, bytes] device tensor of equally shaped grids -> [n, bytes] padded."""
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.dim() == 2
-    per = ((padded_height + 3) // 4) * ((padded_width + 3) // 4) * _block_bytes(compressor, fmt)
-    need = ((compressed_height + 3) // 4) * ((compressed_width + 3) // 4) * _block_bytes(compressor, fmt)
+    _assert_u8_cuda(blocks)
+    assert blocks.dim() == 2
+    per = _grid_bytes(compressor, fmt, padded_height, padded_width)
+    need = _grid_bytes(compressor, fmt, compressed_height, compressed_width)
     if blocks.shape[1] < need:
         raise ValueError("pad_batch_device: %d bytes per image, the source grid takes %d" % (blocks.shape[1], need))
     out = torch.empty((blocks.shape[0], max(per, 1)), dtype=torch.uint8, device=blocks.device)
     st = lib().icamd_pad_batch_device(compressor, etc_strategy, fmt, compressed_height, compressed_width, blocks.shape[0],
-                                      ctypes.c_void_p(blocks.data_ptr()), blocks.shape[1], padded_height, padded_width,
-                                      ctypes.c_void_p(out.data_ptr()), out.shape[1], per, _stream_handle(stream))
+                                      _ptr(blocks), blocks.shape[1], padded_height, padded_width, _ptr(out), out.shape[1], per,
+                                      _stream_handle(stream))
     return out[:, :per] if _check(st, "icamd_pad_batch_device") else None
 
 
 def copy_subimage_batch_device(compressor, fmt, blocks, compressed_height, compressed_width, start_row, start_column, height,
                                width, *, stream=None):
     """icamd_copy_subimage_batch_device (extension): the same window of every grid of blocks = [n, bytes]."""
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.dim() == 2
-    per = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
-    need = ((compressed_height + 3) // 4) * ((compressed_width + 3) // 4) * _block_bytes(compressor, fmt)
+    _assert_u8_cuda(blocks)
+    assert blocks.dim() == 2
+    per = _grid_bytes(compressor, fmt, height, width)
+    need = _grid_bytes(compressor, fmt, compressed_height, compressed_width)
     if blocks.shape[1] < need:
         raise ValueError("copy_subimage_batch_device: %d bytes per image, the source grid takes %d" % (blocks.shape[1], need))
     out = torch.empty((blocks.shape[0], max(per, 1)), dtype=torch.uint8, device=blocks.device)
     st = lib().icamd_copy_subimage_batch_device(compressor, fmt, compressed_height, compressed_width, blocks.shape[0],
-                                                ctypes.c_void_p(blocks.data_ptr()), blocks.shape[1], start_row, start_column,
-                                                height, width, ctypes.c_void_p(out.data_ptr()), out.shape[1], per,
-                                                _stream_handle(stream))
+                                                _ptr(blocks), blocks.shape[1], start_row, start_column, height, width,
+                                                _ptr(out), out.shape[1], per, _stream_handle(stream))
     return out[:, :per] if _check(st, "icamd_copy_subimage_batch_device") else None
 
 
@@ -549,7 +414,7 @@ def create_solid_host(compressor, fmt, height, width, color):
     import numpy as np
     c = bytes(bytearray(color))
     buf = (ctypes.c_uint8 * max(len(c), 4))(*c)
-    n = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
+    n = _grid_bytes(compressor, fmt, height, width)
     out = np.zeros(max(n, 1), np.uint8)
     st = lib().icamd_create_solid(compressor, fmt, height, width, buf, out.ctypes.data, n)
     return out[:n].tobytes() if _check(st, "icamd_create_solid") else None
@@ -563,7 +428,7 @@ def container_write(container, codec, height, width, levels_data):
     """Frames the block streams of the mip levels (largest first, bytes-like each) as a DDS / KTX / PKM / PVR file image
     (extension, include/ic_amd.h: the reference has no container code); bytes, or None where the C side says false."""
     import numpy as np
-    levels = [np.frombuffer(bytes(b), np.uint8) for b in levels_data]
+    levels = [_host_u8(b) for b in levels_data]
     n = len(levels)
     total = container_size(container, codec, height, width, n)
     out = np.zeros(max(total, 1), np.uint8)
@@ -576,20 +441,19 @@ def container_write(container, codec, height, width, levels_data):
 def copy_subimage_device(compressor, fmt, blocks, compressed_height, compressed_width, start_row, start_column, height,
                          width, *, stream=None):
     """Compressor::CopySubimage on a device-resident block grid (torch.uint8 CUDA tensor); device tensor or None."""
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
-    n = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
+    _assert_u8_cuda(blocks)
+    n = _grid_bytes(compressor, fmt, height, width)
     out = torch.empty((max(n, 1),), dtype=torch.uint8, device=blocks.device)
-    st = lib().icamd_copy_subimage_device(compressor, fmt, compressed_height, compressed_width,
-                                          ctypes.c_void_p(blocks.data_ptr()), start_row, start_column, height, width,
-                                          ctypes.c_void_p(out.data_ptr()), n, _stream_handle(stream))
+    st = lib().icamd_copy_subimage_device(compressor, fmt, compressed_height, compressed_width, _ptr(blocks), start_row,
+                                          start_column, height, width, _ptr(out), n, _stream_handle(stream))
     return out[:n] if _check(st, "icamd_copy_subimage_device") else None
 
 
 def copy_subimage_host(compressor, fmt, blocks, compressed_height, compressed_width, start_row, start_column, height,
                        width):
     import numpy as np
-    b = np.frombuffer(blocks, np.uint8)
-    n = ((height + 3) // 4) * ((width + 3) // 4) * _block_bytes(compressor, fmt)
+    b = _host_u8(blocks)
+    n = _grid_bytes(compressor, fmt, height, width)
     out = np.zeros(max(n, 1), np.uint8)
     st = lib().icamd_copy_subimage(compressor, fmt, compressed_height, compressed_width, b.ctypes.data, start_row,
                                    start_column, height, width, out.ctypes.data, n)
@@ -607,12 +471,12 @@ def encode_batch_sharded_device(codec, srcs, height, width, src_components, devi
     per = encoded_size(codec, height, width)
     stride = width * src_components if row_stride_bytes is None else row_stride_bytes
     for i, s in enumerate(srcs):
-        assert s.is_cuda and s.dtype == torch.uint8 and s.is_contiguous()
+        _assert_u8_cuda(s)
         assert s.device.index == devices[i % len(devices)], "image %d is not on its listed device" % i
     if gather_device >= 0 and gathered is None:
         gathered = torch.empty((n, per), dtype=torch.uint8, device=torch.device("cuda", gather_device))
     # The sources / outputs were produced on torch streams (and come from torch's caching allocator) on EVERY listed
-    # device, the library uses its own streams: wait for all of them, not just the current device (ADVICE r03).
+    # device, the library uses its own streams: wait for all of them, not just the current device.
     involved = set(devices[i % len(devices)] for i in range(n))
     if gather_device >= 0:
         involved.add(gather_device)
@@ -625,7 +489,7 @@ def encode_batch_sharded_device(codec, srcs, height, width, src_components, devi
     statuses = (ctypes.c_int * n)()
     st = lib().icamd_encode_batch_sharded_device(codec, etc_strategy, src_components, int(swap_rb), height, width, stride,
                                                  n, in_ptrs, out_ptrs, devs, len(devices), gather_device,
-                                                 None if gathered is None else ctypes.c_void_p(gathered.data_ptr()),
+                                                 None if gathered is None else _ptr(gathered),
                                                  per if gathered is None else gathered.stride(0), statuses)
     if st < 0:
         _check(st, "icamd_encode_batch_sharded_device")
@@ -646,7 +510,7 @@ def clock_probe(duration_us, stream, out=None):
     if out is None:
         out = clock_probe_buffer()
     khz = lib().icamd_wall_clock_rate_khz()
-    st = lib().icamd_clock_probe_device(ctypes.c_void_p(out.data_ptr()), int(duration_us), _stream_handle(stream))
+    st = lib().icamd_clock_probe_device(_ptr(out), int(duration_us), _stream_handle(stream))
     _check(st, "icamd_clock_probe_device")
 
     def result():
@@ -676,9 +540,10 @@ class RcclGather:
         why = None if available else "librccl could not be bound: %s" % L.icamd_last_error().decode()
         uid = (ctypes.c_uint8 * RCCL_UNIQUE_ID_BYTES)()
         if rank == 0 and available:
-            st = L.icamd_rccl_get_unique_id(uid)
-            if st != OK:
-                available, why = False, "icamd_rccl_get_unique_id failed with status %d: %s" % (st, L.icamd_last_error().decode())
+            try:
+                _require_ok(L.icamd_rccl_get_unique_id(uid), "icamd_rccl_get_unique_id")
+            except BackendError as e:  # not raised yet: the other ranks are waiting for the broadcast
+                available, why = False, str(e)
                 uid = (ctypes.c_uint8 * RCCL_UNIQUE_ID_BYTES)()
         raw = broadcast_bytes(bytes(uid) if rank == 0 else None)
         if available and not any(raw):
@@ -686,9 +551,7 @@ class RcclGather:
         if not agree(available):
             raise BackendError(why or "another rank cannot use librccl")
         uid = (ctypes.c_uint8 * RCCL_UNIQUE_ID_BYTES)(*raw)
-        st = L.icamd_rccl_comm_init(ctypes.byref(self.comm), world, rank, uid)
-        if st != OK:
-            raise BackendError("icamd_rccl_comm_init failed with status %d: %s" % (st, L.icamd_last_error().decode()))
+        _require_ok(L.icamd_rccl_comm_init(ctypes.byref(self.comm), world, rank, uid), "icamd_rccl_comm_init")
 
     def gather(self, local, bufs, counts_bytes, root=0, stream=None):
         """local: this rank's uint8 device tensor (counts_bytes[rank] bytes); bufs: on `root`, one device tensor per rank (any
@@ -702,16 +565,13 @@ class RcclGather:
             base = ctypes.c_void_p(lo)
             offs = (ctypes.c_size_t * n)(*[(p - lo) if c > 0 else 0 for p, c in zip(ptrs, counts_bytes)])
         st = lib().icamd_gather_blocks_rccl(self.comm, self.rank, n, root, counts,
-                                            ctypes.c_void_p(local.data_ptr()) if local.numel() else None, base, offs,
-                                            _stream_handle(stream))
-        if st != OK:
-            raise BackendError("icamd_gather_blocks_rccl failed with status %d: %s" % (st, lib().icamd_last_error().decode()))
+                                            _ptr(local) if local.numel() else None, base, offs, _stream_handle(stream))
+        _require_ok(st, "icamd_gather_blocks_rccl")
 
     def destroy(self):
         if self.comm:
             lib().icamd_rccl_comm_destroy(self.comm)
             self.comm = ctypes.c_void_p()
-
 
 
 # ---- mip chains (EXTENSION, include/ic_amd.h): one source image -> every level, each encoded from its own pixels ----
@@ -757,7 +617,7 @@ def encode_mips_device(codec, src, height, width, src_components, *, levels=None
     Returns (flat, views): flat is [n_images, dst_image_stride] (device), views[l] = flat[:, offset[l]:offset[l + 1]], the
     blocks of level l.  The workspace is allocated here unless the caller passes one (a uint8 CUDA tensor of at least
     mip_workspace_size bytes).  No synchronisation."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    _assert_u8_cuda(src)
     if levels is None:
         levels = mip_max_levels(height, width)
     stride = width * src_components if row_stride_bytes is None else row_stride_bytes
@@ -772,10 +632,10 @@ def encode_mips_device(codec, src, height, width, src_components, *, levels=None
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=src.device)
     if workspace is not None and not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
         raise ValueError("encode_mips_device: workspace must be a contiguous uint8 CUDA tensor")
-    ws_ptr = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+    ws_ptr = _ptr(workspace) if workspace is not None else None
     ws_len = workspace.numel() if workspace is not None else 0
-    tail = (height, width, stride, levels, n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
-            ctypes.c_void_p(out.data_ptr()), ws_ptr, ws_len, _stream_handle(stream))
+    tail = (height, width, stride, levels, n_images, img_stride, per, _ptr(src), _ptr(out), ws_ptr, ws_len,
+            _stream_handle(stream))
     if mip_filter == 0:
         st = lib().icamd_encode_mips_device(codec, etc_strategy, src_components, int(swap_rb), *tail)
     else:
@@ -800,7 +660,7 @@ def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_ima
                        src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, stream=None, mip_filter=0):
     """The pixel pyramid alone (icamd_mip_pyramid_device; icamd_mip_pyramid_filtered_device with mip_filter other than 0).
     Returns (flat, views): views[l - 1] is level l as a [n_images, h_l, w_l, src_components] view, for l = 1 .. levels-1."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    _assert_u8_cuda(src)
     if levels is None:
         levels = mip_max_levels(height, width)
     stride = width * src_components if row_stride_bytes is None else row_stride_bytes
@@ -810,8 +670,7 @@ def mip_pyramid_device(src, height, width, src_components, *, levels=None, n_ima
     if out is None:
         out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
     _check_out(out, n_images, per, "mip_pyramid_device")
-    tail = (height, width, stride, levels, n_images, img_stride, per, ctypes.c_void_p(src.data_ptr()),
-            ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
+    tail = (height, width, stride, levels, n_images, img_stride, per, _ptr(src), _ptr(out), _stream_handle(stream))
     if mip_filter == 0:
         st = lib().icamd_mip_pyramid_device(src_components, *tail)
     else:
@@ -832,7 +691,7 @@ def compress_mips_host(compressor, fmt, buffer, height, width, *, levels=None, p
     import numpy as np
     if levels is None:
         levels = mip_max_levels(height, width)
-    src = np.frombuffer(bytes(buffer), dtype=np.uint8) if not isinstance(buffer, np.ndarray) else np.ascontiguousarray(buffer)
+    src = _host_u8(buffer)
     if out_size is None:
         codec = {(COMPRESSOR_DXTC, RGB): DXT1, (COMPRESSOR_DXTC, BGR): DXT1, (COMPRESSOR_DXTC, RGBA): DXT5,
                  (COMPRESSOR_DXTC, BGRA): DXT5, (COMPRESSOR_ETC, RGB): ETC1}.get((compressor, fmt))
@@ -875,8 +734,8 @@ def measure_error_device(codec, src, blocks, height, width, src_components, *, s
     squared differences, [n, 4] int32 largest absolute differences) as device tensors, or None where the call answers false.
     `out`: a caller-owned [n_images, 48] uint8 device tensor for the raw records (e.g. under graph capture).  No
     synchronisation; the records are overwritten by stream-ordered work of the call."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
-    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    _assert_u8_cuda(src)
+    _assert_u8_cuda(blocks)
     gh = height if grid_height is None else grid_height
     gw = width if grid_width is None else grid_width
     stride = width * src_components if row_stride_bytes is None else row_stride_bytes
@@ -888,9 +747,7 @@ def measure_error_device(codec, src, blocks, height, width, src_components, *, s
     else:
         _check_out(out, n_images, ERROR_STATS_BYTES, "measure_error_device")
     st = lib().icamd_measure_error_device(codec, src_components, int(swap_rb), height, width, gh, gw, stride, n_images,
-                                          img_stride, blk_stride, ctypes.c_void_p(src.data_ptr()),
-                                          ctypes.c_void_p(blocks.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                          _stream_handle(stream))
+                                          img_stride, blk_stride, _ptr(src), _ptr(blocks), _ptr(out), _stream_handle(stream))
     if not _check(st, "icamd_measure_error_device"):
         return None
     return _split_stats(out)
@@ -899,8 +756,7 @@ def measure_error_device(codec, src, blocks, height, width, src_components, *, s
 def measure_error_host(compressor, fmt, buffer, blocks, height, width, *, padding_bytes_per_row=0):
     """icamd_measure_error (host buffers): (sse, max_abs) as two numpy arrays of 4, or None where the call answers false."""
     import numpy as np
-    src = np.ascontiguousarray(np.frombuffer(buffer, dtype=np.uint8) if not isinstance(buffer, np.ndarray) else buffer)
-    b = np.frombuffer(bytes(blocks), np.uint8)
+    src, b = _host_u8(buffer), _host_u8(blocks)
     rec = np.zeros(ERROR_STATS_BYTES, np.uint8)
     st = lib().icamd_measure_error(compressor, fmt, height, width, padding_bytes_per_row, src.ctypes.data, b.ctypes.data,
                                    b.size, rec.ctypes.data)

@@ -31,6 +31,112 @@ def test_every_declared_symbol_is_exported(pkg):
     assert sorted(pkg.EXPORTS) == names  # the Python binding list is complete too
 
 
+SCALARS = {"int": ctypes.c_int, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t}
+POINTER = "pointer"  # any pointer parameter: the table may bind it as c_void_p, c_char_p or a POINTER(...)
+
+
+def header_prototypes():
+    """{name: (restype, [argtypes])} of every icamd_ function include/ic_amd.h declares, as ctypes classes (pointer
+    parameters as POINTER).  A declaration or a type this cannot read is an error, never a gap."""
+    text = open(os.path.join(T.ROOT, "include", "ic_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)  # preprocessor lines (none is continued)
+    protos = {}
+    for ret, name, params in re.findall(r"(?:^|[;{}])\s*([\w\s*]+?)\s*\b(icamd_\w+)\s*\(([^()]*)\)\s*(?=;)", text):
+        assert name not in protos, "%s is declared twice" % name
+        ret = " ".join(ret.replace("*", " * ").split())
+        if "*" in ret:
+            assert ret == "const char *", "%s: return type %r is not in the mapping" % (name, ret)
+            restype = ctypes.c_char_p
+        else:
+            assert ret in SCALARS, "%s: return type %r is not in the mapping" % (name, ret)
+            restype = SCALARS[ret]
+        argtypes = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            if "*" in param:
+                argtypes.append(POINTER)
+                continue
+            words = param.split()  # type words, then the parameter's name
+            assert len(words) >= 2 and " ".join(words[:-1]) in SCALARS, "%s: parameter %r is not in the mapping" % (name, param)
+            argtypes.append(SCALARS[" ".join(words[:-1])])
+        protos[name] = (restype, argtypes)
+    unread = sorted(set(declared_functions()) ^ set(protos))
+    assert not unread, "declarations the prototype parser and declared_functions() do not both find: %s" % unread
+    return protos
+
+
+def is_pointer_type(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def prototype_mismatches(header, table):
+    """One line per function whose (name, restype, argtypes) entry in `table` differs from the header's prototype."""
+    bound = {name: (restype, argtypes) for name, restype, argtypes in table}
+    assert len(bound) == len(table), "a function is listed twice"
+    bad = ["%s: in the header, not in the table" % n for n in sorted(set(header) - set(bound))]
+    bad += ["%s: in the table, not in the header" % n for n in sorted(set(bound) - set(header))]
+    for name in sorted(set(header) & set(bound)):
+        (want_res, want_args), (res, args) = header[name], bound[name]
+        if res is not want_res:
+            bad.append("%s: returns %s, the table says %s" % (name, want_res.__name__, getattr(res, "__name__", res)))
+        if len(args) != len(want_args):
+            bad.append("%s: %d parameters, the table lists %d" % (name, len(want_args), len(args)))
+            continue
+        for k, (want, got) in enumerate(zip(want_args, args)):
+            if not (is_pointer_type(got) if want is POINTER else got is want):
+                bad.append("%s: parameter %d is %s, the table says %s"
+                           % (name, k, want if want is POINTER else want.__name__, getattr(got, "__name__", got)))
+    return bad
+
+
+def test_prototype_table_matches_the_header(pkg):
+    header = header_prototypes()
+    assert sorted(header) == declared_functions() and len(header) >= 62
+    assert prototype_mismatches(header, pkg.abi.PROTOTYPES) == []
+    assert pkg.EXPORTS == [name for name, _, _ in pkg.abi.PROTOTYPES]
+    # what lib() hands out carries exactly the table
+    lib = pkg.lib()
+    for name, restype, argtypes in pkg.abi.PROTOTYPES:
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def altered(table, name, change):
+    return [(n, r, change(list(a)) if n == name else a) for n, r, a in table]
+
+
+def test_prototype_comparison_sees_a_widened_argument(pkg):
+    """a uint32_t bound as c_size_t: same width class on the stack, so nothing else would notice"""
+    def widen(args):
+        k = args.index(ctypes.c_uint32)
+        return args[:k] + [ctypes.c_size_t] + args[k + 1:]
+    bad = prototype_mismatches(header_prototypes(), altered(pkg.abi.PROTOTYPES, "icamd_encode_device", widen))
+    assert len(bad) == 1 and bad[0].startswith("icamd_encode_device: parameter 4 is c_uint"), bad
+
+
+def test_prototype_comparison_sees_a_dropped_argument(pkg):
+    bad = prototype_mismatches(header_prototypes(), altered(pkg.abi.PROTOTYPES, "icamd_pad", lambda args: args[:-1]))
+    assert bad == ["icamd_pad: 10 parameters, the table lists 9"], bad
+
+
+def test_bind_skips_missing_symbols_only_when_allowed(pkg):
+    """an A/B library may lack newer entry points (allow_missing); the product library may not"""
+    class Partial:
+        def __init__(self, real, without):
+            self.real, self.without = real, without
+
+        def __getattr__(self, name):
+            if name == self.without:
+                raise AttributeError(name)
+            return getattr(self.real, name)
+    partial = Partial(ctypes.CDLL(pkg.LIB_PATH), "icamd_measure_error")
+    assert pkg.abi.bind(partial, allow_missing=True) is partial
+    assert partial.icamd_version.restype is ctypes.c_char_p and partial.icamd_version.argtypes == []
+    with pytest.raises(AttributeError):
+        pkg.abi.bind(partial, allow_missing=False)
+
+
 def test_host_only_queries_match_the_oracle(pkg):
     for compressor in (T.DXTC, T.ETC, T.PVRTC):
         for fmt in (T.RGB, T.BGR, T.RGBA, T.BGRA):

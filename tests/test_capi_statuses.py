@@ -19,53 +19,6 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "capi_statuses.json")
 
-_ci, _u32, _sz, _vp = ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p
-SIGNATURES = {
-    "icamd_compute_compressed_data_size": (_sz, [_ci, _ci, _u32, _u32]),
-    "icamd_supports_format": (_ci, [_ci, _ci]),
-    "icamd_encoded_size": (_sz, [_ci, _u32, _u32]),
-    "icamd_pvrtc2_workspace_size": (_sz, [_u32, _u32]),
-    "icamd_pvrtc4_workspace_size": (_sz, [_u32, _u32]),
-    "icamd_container_size": (_sz, [_ci, _ci, _u32, _u32, _u32]),
-    "icamd_container_write": (_ci, [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _vp, _sz]),
-    "icamd_encode_device": (_ci, [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]),
-    "icamd_pvrtc2_encode_region_device": (_ci, [_u32, _u32, _u32, _vp, _vp, _vp]),
-    "icamd_compress_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
-    "icamd_compress_and_pad_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp]),
-    "icamd_compress": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz]),
-    "icamd_compress_and_pad": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _sz]),
-    "icamd_decode_device": (_ci, [_ci, _ci, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]),
-    "icamd_decompress": (_ci, [_ci, _ci, _u32, _u32, _u32, _vp, _sz, _vp, _sz]),
-    "icamd_pvrtc2_decompress": (_ci, [_u32, _vp, _sz, _vp, _sz]),
-    "icamd_pad_batch_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _sz, _u32, _u32, _vp, _sz, _sz, _vp]),
-    "icamd_pad_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _vp, _u32, _u32, _vp, _sz, _vp]),
-    "icamd_pad": (_ci, [_ci, _ci, _ci, _u32, _u32, _vp, _u32, _u32, _vp, _sz]),
-    "icamd_downsample_batch_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _vp, _sz, _vp, _sz, _sz, _vp]),
-    "icamd_downsample_device": (_ci, [_ci, _ci, _ci, _u32, _u32, _vp, _vp, _sz, _vp]),
-    "icamd_downsample": (_ci, [_ci, _ci, _ci, _u32, _u32, _vp, _vp, _sz]),
-    "icamd_transcode_dxt1_to_etc1_device": (_ci, [_vp, _sz, _vp]),
-    "icamd_transcode_dxt1_to_etc1": (_ci, [_vp, _sz]),
-    "icamd_create_solid_batch_device": (_ci, [_ci, _ci, _u32, _u32, _u32, _vp, _vp, _sz, _sz, _vp]),
-    "icamd_create_solid_device": (_ci, [_ci, _ci, _u32, _u32, _vp, _vp, _sz, _vp]),
-    "icamd_create_solid": (_ci, [_ci, _ci, _u32, _u32, _vp, _vp, _sz]),
-    "icamd_copy_subimage_batch_device": (_ci, [_ci, _ci, _u32, _u32, _u32, _vp, _sz, _u32, _u32, _u32, _u32, _vp, _sz, _sz,
-                                               _vp]),
-    "icamd_copy_subimage_device": (_ci, [_ci, _ci, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
-    "icamd_copy_subimage": (_ci, [_ci, _ci, _u32, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz]),
-    "icamd_compress_batch": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp, _ci, _vp]),
-    "icamd_encode_batch_sharded_device": (_ci, [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _ci, _ci, _vp,
-                                                _sz, _vp]),
-    "icamd_mip_max_levels": (_u32, [_u32, _u32]),
-    "icamd_mip_chain_size": (_sz, [_ci, _u32, _u32, _u32, _vp]),
-    "icamd_mip_workspace_size": (_sz, [_ci, _ci, _u32, _u32, _u32, _u32]),
-    "icamd_encode_mips_device": (_ci, [_ci, _ci, _ci, _ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp, _sz,
-                                       _vp]),
-    "icamd_mip_pyramid_device": (_ci, [_ci, _u32, _u32, _u32, _u32, _u32, _sz, _sz, _vp, _vp, _vp]),
-    "icamd_compress_mips": (_ci, [_ci, _ci, _ci, _u32, _u32, _u32, _u32, _vp, _vp, _sz]),
-    "icamd_clock_probe_device": (_ci, [_vp, _u32, _vp]),
-    "icamd_wall_clock_rate_khz": (_u32, []),
-    "icamd_device_count": (_ci, []),
-}
 # entry points whose result is a size or a count, not a status: recorded as plain numbers
 SIZE_RESULTS = {"icamd_compute_compressed_data_size", "icamd_supports_format", "icamd_encoded_size",
                 "icamd_pvrtc2_workspace_size", "icamd_pvrtc4_workspace_size", "icamd_container_size", "icamd_mip_max_levels",
@@ -102,12 +55,9 @@ def levels_of(h, w):
 
 
 class Lib:
-    def __init__(self, path):
-        self.L = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
-            f = getattr(self.L, name)
-            f.restype, f.argtypes = res, args
-        self.L.icamd_last_error.restype = ctypes.c_char_p
+    def __init__(self, pkg):
+        """a library handle of its own, with the package's prototypes (image-compression_amd/abi.py)"""
+        self.L = pkg.abi.bind(ctypes.CDLL(pkg.LIB_PATH))
         self.keep = []  # host buffers of the current call
 
     def __getattr__(self, name):
@@ -433,7 +383,7 @@ def decode(table, name, i):
 def load_lib():
     sys.path.insert(0, os.path.dirname(HERE))
     import ic_amd_loader
-    return Lib(ic_amd_loader.load_package().LIB_PATH)
+    return Lib(ic_amd_loader.load_package())
 
 
 def test_statuses_and_error_texts_match_the_recorded_table():

@@ -1364,6 +1364,24 @@ def test_host_api_band_pipeline(pkg):
     assert pkg.compress_host(T.DXTC, T.RGB, img, h, w, out_size=8) is None
 
 
+def test_host_api_caller_buffer_with_padded_grid(pkg):
+    """compress_host(..., padded=..., out=buf): the caller's buffer together with CompressAndPad.  9 x 5 into 12 x 8 is two
+    block rows (the second ragged) and three block columns with pad blocks right of and below the image."""
+    h, w, padded = 9, 5, (12, 8)
+    img = T.s_noise(h, w, 3, index=4)
+    want = T.oracle_encode(T.DXT1, img, h, w, 3, gh=padded[0], gw=padded[1])
+    assert len(want) == 3 * 2 * 8
+    buf = np.zeros(len(want), np.uint8)
+    assert pkg.compress_host(T.DXTC, T.RGB, img, h, w, padded=padded, out=buf) is buf
+    assert buf.tobytes() == want
+    assert pkg.compress_host(T.DXTC, T.RGB, img, h, w, padded=padded) == want
+    # PVRTC has no CompressAndPad (the reference's false), whichever buffer the result would go to
+    rgba = T.s_noise(8, 8, 4, index=4)
+    out = np.zeros(pkg.compute_compressed_data_size(T.PVRTC, T.RGBA, 16, 16), np.uint8)
+    assert pkg.compress_host(T.PVRTC, T.RGBA, rgba, 8, 8, padded=(16, 16), out=out) is None
+    assert pkg.compress_host(T.PVRTC, T.RGBA, rgba, 8, 8, padded=(16, 16)) is None
+
+
 # ---- SURVEY 8f row 2 on device: CreateSolidImage / CopySubimage on device-resident block grids
 
 def test_create_solid_and_copy_subimage_on_device_match_oracle(pkg):
