@@ -40,6 +40,10 @@ BC4, BC5 = 5, 6
 # from RGBA8 sources; colour half pinned to the ETC1 encoder byte for byte, alpha half defined in DESIGN.md 3.11.  7..15 are
 # unassigned and rejected.  encode_device / decode_device / measure_error_device / containers only
 ETC2_RGBA8 = 16
+# EXTENSION (include/ic_amd.h ICAMD_ETC2_RGB8): ETC2 RGB8, 8 bytes per block, from RGB888 or RGBA8 sources: per block the ETC1
+# encoder's word or the least-squares planar word, whichever is strictly closer.  17 is unassigned and rejected.
+# encode_device / decode_device / measure_error_device / containers only
+ETC2_RGB8 = 18
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py

@@ -57,8 +57,8 @@ inline bool container_supports(int container, int codec) {
     case ICAMD_CONTAINER_KTX:
     case ICAMD_CONTAINER_PVR:
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
-             codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8;
-    case ICAMD_CONTAINER_PKM: return codec == ICAMD_ETC1 || codec == ICAMD_ETC2_RGBA8;
+             codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8;
+    case ICAMD_CONTAINER_PKM: return codec == ICAMD_ETC1 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8;
     default: return false;
   }
 }
@@ -105,7 +105,7 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 24, 0);            // glFormat (compressed)
       const uint32_t internal = codec == ICAMD_DXT1 ? 0x83F0u : codec == ICAMD_DXT5 ? 0x83F3u : codec == ICAMD_ETC1 ? 0x8D64u
                                 : codec == ICAMD_BC4 ? 0x8DBBu : codec == ICAMD_BC5 ? 0x8DBDu
-                                : codec == ICAMD_ETC2_RGBA8 ? 0x9278u : 0x8C03u;
+                                : codec == ICAMD_ETC2_RGBA8 ? 0x9278u : codec == ICAMD_ETC2_RGB8 ? 0x9274u : 0x8C03u;
       put_le32(out + 28, internal);
       const uint32_t base = codec == ICAMD_BC4 ? 0x1903u : codec == ICAMD_BC5 ? 0x8227u                    // GL_RED / GL_RG
                             : (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2 || codec == ICAMD_ETC2_RGBA8) ? 0x1908u : 0x1907u;         // GL_RGBA / GL_RGB
@@ -120,8 +120,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       break;
     }
     case ICAMD_CONTAINER_PKM: {
-      memcpy(out, codec == ICAMD_ETC2_RGBA8 ? "PKM 20" : "PKM 10", 6);
-      put_be16(out + 6, codec == ICAMD_ETC2_RGBA8 ? 3 : 0);  // ETC2_RGBA_NO_MIPMAPS / ETC1_RGB_NO_MIPMAPS
+      memcpy(out, codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 ? "PKM 20" : "PKM 10", 6);
+      put_be16(out + 6, codec == ICAMD_ETC2_RGBA8 ? 3 : codec == ICAMD_ETC2_RGB8 ? 1 : 0);  // ETC2_RGBA / ETC2_RGB / ETC1_RGB _NO_MIPMAPS
       put_be16(out + 8, (width + 3u) & ~3u);       // encoded (block-aligned) size
       put_be16(out + 10, (height + 3u) & ~3u);
       put_be16(out + 12, width);                   // original size
@@ -132,7 +132,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out, 0x03525650u);  // "PVR\3"
       put_le32(out + 4, 0);        // flags
       put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u
-                        : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_ETC2_RGBA8 ? 23u : 11u);
+                        : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_ETC2_RGBA8 ? 23u
+                        : codec == ICAMD_ETC2_RGB8 ? 22u : 11u);
       put_le32(out + 16, 0);       // colour space: linear RGB
       put_le32(out + 20, 0);       // channel type: unsigned byte, normalised
       put_le32(out + 24, height);

@@ -26,6 +26,7 @@
 
 #include "decode_block.h"  // decode_etc1
 #include "dxt_block.h"     // Out8
+#include "etc2_colour_block.h"  // decode_etc2_colour
 #include "ic_device.h"
 
 namespace icamd {
@@ -188,10 +189,10 @@ ICAMD_DEV void decode_eac_alpha(uint32_t w0, uint32_t w1, uint32_t px[16]) {
   }
 }
 
-// A whole ETC2 RGBA8 block (w[0..1] the EAC word, w[2..3] the colour word in an ETC1-compatible mode) as R,G,B,A dwords.
-// swap: stored R goes to the third byte, as the DXT5 decoder's swap does.
+// A whole ETC2 RGBA8 block (w[0..1] the EAC word, w[2..3] the colour word in any of the five modes: etc2_colour_block.h) as
+// R,G,B,A dwords.  swap: stored R goes to the third byte, as the DXT5 decoder's swap does.
 ICAMD_DEV void decode_etc2_rgba8(const uint32_t w[4], bool swap, uint32_t px[16]) {
-  decode_etc1(w[2], w[3], px);
+  decode_etc2_colour(w[2], w[3], px);
   decode_eac_alpha(w[0], w[1], px);
   if (swap) {
     ICAMD_UNROLL

@@ -1,0 +1,141 @@
+// etc2_rgb8_kernels.hip -- ETC2 RGB8 (ETC1 block or planar block, whichever is closer) encode and decode kernels for gfx950
+// (EXTENSION, include/ic_amd.h ICAMD_ETC2_RGB8); see etc2_colour_block.h for the block math and DESIGN.md 3.13.
+//
+// Encode: one block per lane on 16 x 16-block tiles, four-wave workgroups, as the ETC2 RGBA8 kernels.  Phase one is the ETC1
+// block routine of etc1_block.h unchanged (same templates, same wave-uniform shortcuts, so an ETC1 outcome is the ETC1
+// kernels' word byte for byte).  Phase two -- the ETC1 word's error, the least-squares plane, its error, the choice -- needs the
+// sixteen texels again, and the ETC1 search alone fills the 128-VGPR budget: the lane RELOADS its block (the lines were read by
+// this wave a few thousand instructions earlier) instead of holding sixteen registers across the search, which keeps every
+// strategy at four waves per SIMD and without scratch.  Phase two has no wave-uniform decision.
+// The block leaves as one 8-byte store.
+// Decode: one block per lane, an 8-byte block load and four 12-byte row stores (RGB888), clipped at the image's edge.
+#include "etc1_block.h"
+#include "etc2_colour_block.h"
+#include "codec_info.h"
+#include "ic_launch.h"
+#include "ic_amd.h"
+
+namespace icamd {
+
+// locate_tile<false> for lane `tid` of the workgroup
+__device__ __forceinline__ TileCoord etc2_rgb8_tile(const GridParams &P, uint32_t tid) {
+  TileCoord t;
+  const uint32_t cols = 1u << P.log2_tile_cols, rows = 256u >> P.log2_tile_cols;
+  t.lx = tid & (cols - 1u);
+  t.ly = tid >> P.log2_tile_cols;
+  t.bcol0 = blockIdx.x * cols;
+  t.brow0 = (blockIdx.y + P.tile_row0) * rows;
+  t.bcol = t.bcol0 + t.lx;
+  t.brow = t.brow0 + t.ly;
+  t.img = blockIdx.z;
+  t.full = t.bcol0 + cols <= P.block_cols && t.brow0 + rows <= P.block_rows;
+  t.interior = (t.bcol0 + cols) * 4u <= P.width && (t.brow0 + rows) * 4u <= P.height;
+  t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
+  return t;
+}
+
+template <int COMPS, int STRATEGY>
+__device__ __forceinline__ void etc2_rgb8_encode_one(const GridParams &P) {
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: a scalar register
+  Out8 c;
+  {
+    const TileCoord t = etc2_rgb8_tile(P, threadIdx.x);
+    if (!t.valid) return;
+    uint32_t px[16];
+    load_tile_block<COMPS>(P, t, px);
+    if (STRATEGY == 3) {
+      c = encode_etc1_block<false>(px, 3u);
+    } else {
+      const uint32_t spread = etc1_block_spread(px);
+      c = etc1_encode_classified<STRATEGY>(px, etc1_constant_block(px, spread), spread >= ICAMD_ETC1_BUSY_SPREAD);
+    }
+  }
+  // Phase two holds NO vector register across the search: the lane index comes from the hardware (mbcnt) and the wave's from
+  // a scalar register, the block's coordinates and addresses are derived again from them, and the texels are read again (the
+  // compiler barrier keeps the second read apart from the first).  With as little as the lane index kept alive the RGBA8
+  // kSmallerError kernel spills 8 bytes at 128 VGPRs.
+  asm volatile("" ::: "memory");
+  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const TileCoord t = etc2_rgb8_tile(P, lane + 64u * wave);
+  if (!t.valid) return;  // (the same lanes as above; the store below is bounded by THIS coordinate)
+  uint32_t px[16];
+  load_tile_block<COMPS>(P, t, px);
+  const Out8 o = etc2_rgb8_choose(px, c);
+  store_stream8(tile_dst<8>(P, t), o.lo, o.hi);
+}
+
+__device__ __forceinline__ void etc2_rgb8_decode_one(const DecodeParams &P, uint32_t k) {
+  const uint32_t img = fastdiv(k, P.div_bpi);
+  const uint32_t rem = k - img * P.blocks_per_image;
+  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const U2 v = load_stream(reinterpret_cast<const U2 *>(P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * 8u));
+  uint32_t px[16];
+  decode_etc2_colour(v.x, v.y, px);
+  uint8_t *dst = P.pixels + (size_t)img * P.dst_image_stride;
+  const uint32_t row = brow * 4u, col = bcol * 4u;
+  if (row + 4u <= P.height && col + 4u <= P.width) {
+#pragma unroll
+    for (int y = 0; y < 4; ++y)  // four 3-byte texels as the twelve bytes R G B R | G B R G | B R G B
+      store_stream12(dst + (size_t)(row + y) * P.row_stride + (size_t)col * 3u, px[4 * y] | px[4 * y + 1] << 24,
+                     px[4 * y + 1] >> 8 | px[4 * y + 2] << 16, px[4 * y + 2] >> 16 | px[4 * y + 3] << 8);
+  } else {  // clipped at the image's edge, pixel by pixel
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (row + y < P.height && col + x < P.width) {
+          uint8_t *q = dst + (size_t)(row + y) * P.row_stride + (size_t)(col + x) * 3u;
+          const uint32_t p = px[4 * y + x];
+          q[0] = (uint8_t)p; q[1] = (uint8_t)(p >> 8); q[2] = (uint8_t)(p >> 16);
+        }
+  }
+}
+
+extern "C" {
+
+// (amdgpu_waves_per_eu(4): as the ETC1 kernels -- the colour search must fit 128 VGPRs)
+#define ICAMD_ETC2_RGB8_KERNEL(name, comps, strategy)                                                                  \
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) __attribute__((amdgpu_waves_per_eu(4))) name(GridParams P) { \
+    etc2_rgb8_encode_one<comps, strategy>(P);                                                                          \
+  }
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgb888_kernel, 3, 2)            // kSmallerError (the reference's default)
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgba8_kernel, 4, 2)
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgb888_split_h_kernel, 3, 0)    // kSplitHorizontally
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgba8_split_h_kernel, 4, 0)
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgb888_split_v_kernel, 3, 1)    // kSplitVertically
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgba8_split_v_kernel, 4, 1)
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgb888_heuristic_kernel, 3, 3)  // kHeuristic
+ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgba8_heuristic_kernel, 4, 3)
+#undef ICAMD_ETC2_RGB8_KERNEL
+
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_etc2_rgb8_decode_kernel(DecodeParams P) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k < P.total_blocks) etc2_rgb8_decode_one(P, k);
+}
+
+}  // extern "C"
+
+const char *etc2_rgb8_kernel_name(int comps) {
+  return comps == 4 ? "icamd_etc2_rgb8_rgba8_kernel" : comps == 3 ? "icamd_etc2_rgb8_rgb888_kernel" : "";
+}
+
+hipError_t launch_etc2_rgb8(int comps, const GridParams &P, hipStream_t stream) {
+  typedef void (*Kernel)(GridParams);
+  static const Kernel kernels[2][4] = {
+    { icamd_etc2_rgb8_rgb888_split_h_kernel, icamd_etc2_rgb8_rgb888_split_v_kernel, icamd_etc2_rgb8_rgb888_kernel,
+      icamd_etc2_rgb8_rgb888_heuristic_kernel },
+    { icamd_etc2_rgb8_rgba8_split_h_kernel, icamd_etc2_rgb8_rgba8_split_v_kernel, icamd_etc2_rgb8_rgba8_kernel,
+      icamd_etc2_rgb8_rgba8_heuristic_kernel } };
+  const Kernel k = kernels[comps == 4 ? 1 : 0][P.etc_strategy < 4u ? P.etc_strategy : 2u];  // any other value is kSmallerError
+  return launch_tiled(k, k, P, stream, 4u);
+}
+
+hipError_t launch_etc2_rgb8_decode(const DecodeParams &P, hipStream_t stream) {
+  if (P.total_blocks == 0) return hipSuccess;
+  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+  hipLaunchKernelGGL(icamd_etc2_rgb8_decode_kernel, dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup),
+                     dim3(kThreadsPerWorkgroup), 0, stream, P);
+  return hipGetLastError();
+}
+
+}  // namespace icamd

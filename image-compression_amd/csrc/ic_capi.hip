@@ -218,11 +218,11 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr,
   return false;
 }
 
-// Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 3 or 4, DXT5 / ETC2 RGBA8 4, BC4 1..4,
-// BC5 2..4.
+// Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 4,
+// BC4 1..4, BC5 2..4.
 bool codec_accepts_components(int codec, int comps) {
   switch (codec) {
-    case ICAMD_DXT1: case ICAMD_ETC1: return comps == 3 || comps == 4;
+    case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: return comps == 3 || comps == 4;
     case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: return comps == 4;
     case ICAMD_BC4: return comps >= 1 && comps <= 4;
     case ICAMD_BC5: return comps >= 2 && comps <= 4;
@@ -474,6 +474,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_DXT1: case ICAMD_DXT5: return icamd::dxt_kernel_name(codec, src_components);
     case ICAMD_ETC1: return icamd::etc1_kernel_name(src_components);
     case ICAMD_ETC2_RGBA8: return icamd::etc2_kernel_name(src_components);
+    case ICAMD_ETC2_RGB8: return icamd::etc2_rgb8_kernel_name(src_components);
     case ICAMD_PVRTC2: return icamd::pvrtc2_kernel_name();
     case ICAMD_PVRTC4: return icamd::pvrtc4_kernel_name();
     case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
@@ -524,7 +525,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return pvrtc_encode_device_impl(codec, src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
                                     dst_image_stride_bytes, d_src, d_dst, stream, false);
-  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8)
+  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8)
     return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!codec_accepts_components(codec, src_components)) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
   if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
@@ -535,6 +536,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     ICAMD_HIP(icamd::launch_etc1(src_components, P, stream), "launch etc1");
   else if (codec == ICAMD_ETC2_RGBA8)
     ICAMD_HIP(icamd::launch_etc2(P, stream), "launch etc2");
+  else if (codec == ICAMD_ETC2_RGB8)
+    ICAMD_HIP(icamd::launch_etc2_rgb8(src_components, P, stream), "launch etc2 rgb8");
   else
     ICAMD_HIP(icamd::launch_dxt(codec, src_components, P, stream), "launch dxt");
   return ICAMD_OK;
@@ -744,6 +747,8 @@ static int decode_launch(int codec, int swap_rb, uint32_t height, uint32_t width
   P.div_cols = icamd::make_fastdiv(P.block_cols);
   if (codec == ICAMD_ETC2_RGBA8)
     ICAMD_HIP(icamd::launch_etc2_decode(P, stream), "launch etc2 decode");
+  else if (codec == ICAMD_ETC2_RGB8)
+    ICAMD_HIP(icamd::launch_etc2_rgb8_decode(P, stream), "launch etc2 rgb8 decode");
   else
     ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
   return ICAMD_OK;
@@ -755,7 +760,7 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
   const bool bc45 = codec == ICAMD_BC4 || codec == ICAMD_BC5;
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 &&
-      codec != ICAMD_ETC2_RGBA8 && !bc45)
+      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && !bc45)
     return ICAMD_FALSE;
   if (bc45 && swap_rb) return fail(ICAMD_ERR_ARG, "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
@@ -1439,7 +1444,8 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
                           const uint8_t *const *level_data, const size_t *level_sizes, uint8_t *out, size_t out_size) try {
   using namespace icamd;
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
-  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && codec != ICAMD_BC4 && codec != ICAMD_BC5 && codec != ICAMD_ETC2_RGBA8))
+  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && codec != ICAMD_BC4 && codec != ICAMD_BC5 && codec != ICAMD_ETC2_RGBA8 &&
+                             codec != ICAMD_ETC2_RGB8))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);
@@ -1481,8 +1487,8 @@ static int encode_mips(int codec, int etc_strategy, int src_components, int swap
   if (filter == ICAMD_MIP_FILTER_NORMAL && codec != ICAMD_BC5) return mip_check_filter(codec, src_components, filter);
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
-  if (codec == ICAMD_ETC2_RGBA8)
-    return fail(ICAMD_ERR_ARG, "ETC2 RGBA8 has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
+  if (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8)
+    return fail(ICAMD_ERR_ARG, "ETC2 has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
   int rc = mip_check_components(codec, src_components, swap_rb);

@@ -82,14 +82,45 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         *       the block is the candidate with the lexicographically smallest (sse, t, m, b).  Multiplier 0 is never written.
         * icamd_encode_device needs src_components == 4 (else ICAMD_ERR_ARG) and honours etc_strategy, grids, strides and batches
         * as for ETC1.  icamd_decode_device writes RGBA8 rows (swap_rb: stored R goes to the third byte, as for DXT5) and decodes
-        * blocks whose colour word is in an ETC1-compatible mode (individual, or differential without overflow) -- everything
-        * this library writes; T, H and planar colour words are NOT decoded (their pixels are unspecified).
+        * colour words in all five modes (individual, differential, T, H, planar: see ICAMD_ETC2_RGB8 below); the encoder
+        * itself writes the two ETC1-compatible ones only.
         * icamd_measure_error_device compares all four channels.  Reachable through icamd_encode_device,
         * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device, icamd_encoded_size,
         * icamd_kernel_name, icamd_metric_kernel_name and the container functions only: no Compressor + format pair selects it
         * (icamd_supports_format and the host-buffer entry points keep the reference's semantics, so icamd_measure_error does
         * not reach it), and the mip entry points answer ICAMD_ERR_ARG as they do for PVRTC. */
-       ICAMD_ETC2_RGBA8 = 16 };
+       ICAMD_ETC2_RGBA8 = 16,
+       /* Value 17 is unassigned and rejected by every entry point. */
+       /* EXTENSION: ETC2 RGB8 (COMPRESSED_RGB8_ETC2), 8 bytes per 4 x 4 block in the raster block order of ETC1: one ETC2
+        * colour word.  Big-endian, bit 63 = top bit of byte 0; diff = bit 33.
+        *   Decode, all five modes (Khronos ETC2).  diff = 0: individual, as ETC1.  Otherwise s_c = 5-bit base + sign-extended
+        *       3-bit delta of byte c (R, G, B = bytes 0, 1, 2): s_R outside 0..31 selects T, else s_G outside H, else s_B outside
+        *       planar, else differential as ETC1.  The two ETC1 modes decode exactly as ICAMD_ETC1 does (pinned to the reference).
+        *       T: two 4-bit colours C1, C2 (expanded v * 17) and a distance d[di], d = 3, 6, 11, 16, 23, 32, 41, 64; paint colours
+        *       C1, clamp(C2 + d), C2, clamp(C2 - d).  H: paint colours clamp(C1 + d), clamp(C1 - d), clamp(C2 + d), clamp(C2 - d),
+        *       the lowest bit of di being (C1 >= C2 as R << 16 | G << 8 | B).  In both, texel (x, y) takes the paint colour
+        *       bit(p) | bit(p + 16) << 1 of the low 32 bits, p = 4 x + y.  Planar: three colours O, H, V of 6 / 7 / 6 bits
+        *       (expanded v << 2 | v >> 4 and v << 1 | v >> 6), texel (x, y) = clamp((x (H - O) + y (V - O) + 4 O + 2) >> 2, 0,
+        *       255) per channel.  Field positions: csrc/etc2_colour_block.h.
+        *   Encode, a definition and not a heuristic.  With px the sixteen texels the ETC1 block routine is handed
+        *       for the block (same edge replication and padded-grid fetch; bytes 0..2 of a pixel as they lie in memory, whatever
+        *       swap_rb):
+        *       E = the 8 bytes icamd_encode_device(ICAMD_ETC1, etc_strategy, ...) writes for the block (PARITY PINNED through ETC1);
+        *       P = the planar word of the least-squares plane: per channel S = Sum v, Sx = Sum (2 x - 3) v, Sy = Sum (2 y - 3) v,
+        *       N_O = 5 S - 3 Sx - 3 Sy, N_H = 5 S + 5 Sx - 3 Sy, N_V = 5 S - 3 Sx + 5 Sy (80 times the plane at (0, 0), (4, 0),
+        *       (0, 4)), and the n-bit code (6 for R and B, 7 for G) q = (2 clamp(N, 0, 20400) (2^n - 1) + 20400) / 40800,
+        *       truncating; no refinement.  The ignored bits 63, 55, 47..45, 42 are set so that bytes 0 and 1 do not overflow and
+        *       byte 2 does (bit 63 / 55 = the top bit of the byte's delta field; with b = BO bits 4..3 and t = BO bits 2..1, bits
+        *       47..45 = 111 and bit 42 = 0 where b + t >= 4, else 000 and 1).
+        *       The block is P if its squared error summed over the 16 texels and 3 channels is STRICTLY smaller than E's, else E
+        *       byte for byte.  So the summed error never exceeds ETC1's, block by block.  T and H are decoded, never written.
+        * icamd_encode_device takes src_components 3 or 4 and honours etc_strategy, grids, strides and batches as for ETC1.
+        * icamd_decode_device writes RGB888 rows and, like ICAMD_ETC1, stores the word's channels in their stored order whatever
+        * swap_rb.  icamd_measure_error_device compares three channels, sources of 3 or 4 components.  Reachable through
+        * icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device,
+        * icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions (KTX 0x9274, PKM 2.0 type 1,
+        * PVR 22; no DDS) only: no Compressor + format pair selects it, and the mip entry points answer ICAMD_ERR_ARG. */
+       ICAMD_ETC2_RGB8 = 18 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -199,7 +230,8 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
  * Alignment: DXT / ETC accept any pointers and strides; PVRTC reads 16 bytes at a time and requires d_src (and
  * src_image_stride_bytes) 16-byte aligned, d_dst (and dst_image_stride_bytes) 8-byte aligned, else ICAMD_ERR_ARG.
  * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT.
- * ETC2 RGBA8 (extension, see ICAMD_ETC2_RGBA8): src_components must be 4; otherwise as ETC1. */
+ * ETC2 RGBA8 (extension, see ICAMD_ETC2_RGBA8): src_components must be 4; otherwise as ETC1.
+ * ETC2 RGB8 (extension, see ICAMD_ETC2_RGB8): src_components 3 or 4; as ETC1. */
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
                         uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
                         uint32_t row_stride_bytes, uint32_t n_images,
@@ -217,7 +249,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
  * own 2-bit value (weights 0, 3, 5, 8; a block with colour-word bit 0 set -- the encoder never writes one -- takes PVRTC1's
  * punch-through weights 0, 4, 4, 8 with alpha 0 for value 2).  ICAMD_BC4 / ICAMD_BC5 (extension, see ICAMD_BC4) write
  * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG.  ICAMD_ETC2_RGBA8 (extension)
- * writes width*4 bytes per row plus the padding; its domain is stated at the codec enumeration. */
+ * writes width*4 bytes per row plus the padding, ICAMD_ETC2_RGB8 (extension) width*3 like ICAMD_ETC1 (and like it stores the
+ * channels in their stored order whatever swap_rb); both decode all five ETC2 colour modes. */
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t padding_bytes_per_row, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
@@ -397,7 +430,7 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
  * The reference ends at the raw block stream (compressed_image.h:52-66); it has no file-container code, so there is
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
  * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
- * PVRTC2, BC4, BC5, ETC2 RGBA8), PKM (ETC1 as "PKM 10" type 0, ETC2 RGBA8 as "PKM 20" type 3; one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
+ * PVRTC2, BC4, BC5, ETC2 RGBA8, ETC2 RGB8), PKM (ETC1 as "PKM 10" type 0, ETC2 RGB8 / RGBA8 as "PKM 20" type 1 / 3; one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
  * icamd_compress / icamd_downsample return for that size (PVRTC: square power-of-two levels of 8 x 8 and up only). */
 enum { ICAMD_CONTAINER_DDS = 0, ICAMD_CONTAINER_KTX = 1, ICAMD_CONTAINER_PKM = 2, ICAMD_CONTAINER_PVR = 3 };
@@ -526,7 +559,7 @@ const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
  *     stats[i].max_abs[k] = the largest |S[y][x][k] - D[y][x][k]| over the same pixels.
  * Pixels of edge blocks outside the image do not count, nor do blocks of a padded grid wholly outside it (they are not read).
  * The compared channels are the decoder's output channels; the others are 0 in both arrays:
- *     DXT1, ETC1            bytes 0..2 of the source pixel   src_components 3 or 4 (alpha ignored, sse[3] = 0)
+ *     DXT1, ETC1, ETC2 RGB8 bytes 0..2 of the source pixel   src_components 3 or 4 (alpha ignored, sse[3] = 0)
  *     DXT5, PVRTC2, PVRTC4  bytes 0..3                        src_components 4
  *     ETC2 RGBA8            bytes 0..3                        src_components 4
  *     BC4                   k = 0 is R                        src_components 1..4  (R, G located by the rules at ICAMD_BC4:
