@@ -21,6 +21,8 @@
 #include <stddef.h>
 
 #if defined(ICAMD_HOST_EMULATION)
+#include <stdio.h>
+#include <atomic>
 #define ICAMD_DEV static inline
 #define ICAMD_UNROLL
 #define ICAMD_NOUNROLL
@@ -33,8 +35,8 @@
 
 namespace icamd {
 
-// Host-precomputed unsigned division n / d for n < 2^31 (block ids), d >= 1:
-// q = (umulhi(n, mul) + n) >> shift.
+// Host-precomputed unsigned division n / d.  PRECONDITION n < 2^31 (block ids; umulhi(n, mul) + n must fit 32 bits) and
+// 1 <= d <= 2^31 (shift <= 31): q = (umulhi(n, mul) + n) >> shift.
 struct FastDiv {
   uint32_t mul, shift, d;
 };
@@ -67,17 +69,52 @@ struct GridParams {
 };
 
 // ---- thin wrappers over the gfx950 instructions the kernels rely on ----
+// Every wrapper states its operand domain.  The host twin returns what the instruction returns for EVERY 32-bit operand
+// (tests/test_gpu_wrappers.py holds the two together, op by op), so an operand outside the domain gives the hardware's
+// answer in the host tier too -- and it is counted: each twin reports an operand outside its stated domain to
+// emul::violate(), and the fixtures of the host tier assert at teardown that nothing was reported.
 #if defined(ICAMD_HOST_EMULATION)
+
+// (internal linkage throughout: one counter per host-emulation library -- each is one translation unit -- and none shared
+// between two libraries loaded into one process)
+namespace emul {
+struct Violations {
+  std::atomic<unsigned long long> count{0};
+  char first[224] = {0};  // "wrapper(a, b, c) at file:line" of the first one
+};
+static inline Violations &violations() {
+  static Violations v;
+  return v;
+}
+static inline void violate(const char *wrapper, uint32_t a, uint32_t b, uint32_t c, const char *file, int line) {
+  Violations &v = violations();
+  if (v.count.fetch_add(1) == 0)
+    snprintf(v.first, sizeof v.first, "%s(0x%x, 0x%x, 0x%x) at %s:%d", wrapper, (unsigned)a, (unsigned)b, (unsigned)c, file, line);
+}
+// puts back an earlier state (count 0, "": a reset)
+static inline void restore_violations(unsigned long long count, const char *first) {
+  Violations &v = violations();
+  v.count = count;
+  snprintf(v.first, sizeof v.first, "%s", first);
+}
+}  // namespace emul
+// the caller's file and line, for the record of the first violation
+#define ICAMD_EMUL_SITE const char *file_ = __builtin_FILE(), int line_ = __builtin_LINE()
+#define ICAMD_EMUL_DOMAIN(ok, name, a, b, c) do { if (!(ok)) emul::violate(name, (uint32_t)(a), (uint32_t)(b), (uint32_t)(c), file_, line_); } while (0)
 
 ICAMD_DEV uint32_t umulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
 ICAMD_DEV uint32_t udot4(uint32_t a, uint32_t b, uint32_t c) {
   for (int i = 0; i < 4; ++i) c += ((a >> (8 * i)) & 0xff) * ((b >> (8 * i)) & 0xff);
   return c;
 }
-ICAMD_DEV uint32_t sad_u32(uint32_t a, uint32_t b, uint32_t c) { return (a > b ? a - b : b - a) + c; }
 ICAMD_DEV uint32_t sad_u16x2(uint32_t a, uint32_t b, uint32_t c) {
   const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
   return (al > bl ? al - bl : bl - al) + (ah > bh ? ah - bh : bh - ah) + c;
+}
+// (v_sad_u16, as the device form: high halves that are not zero add their own difference)
+ICAMD_DEV uint32_t sad_u32(uint32_t a, uint32_t b, uint32_t c, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(a < 65536u && b < 65536u, "sad_u32", a, b, c);
+  return sad_u16x2(a, b, c);
 }
 ICAMD_DEV uint32_t sad_u8(uint32_t a, uint32_t b, uint32_t c) {
   for (int i = 0; i < 4; ++i) {
@@ -87,7 +124,8 @@ ICAMD_DEV uint32_t sad_u8(uint32_t a, uint32_t b, uint32_t c) {
   return c;
 }
 ICAMD_DEV uint32_t sad_hi_u8(uint32_t a, uint32_t b, uint32_t c) { return (sad_u8(a, b, 0u) << 16) + c; }
-ICAMD_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) {
+ICAMD_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(sh < 32u, "alignbit", hi, lo, sh);
   return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31));
 }
 ICAMD_DEV uint32_t avg_u8(uint32_t a, uint32_t b) {
@@ -95,21 +133,42 @@ ICAMD_DEV uint32_t avg_u8(uint32_t a, uint32_t b) {
   for (int i = 0; i < 4; ++i) r |= ((((a >> (8 * i)) & 0xff) + ((b >> (8 * i)) & 0xff)) >> 1) << (8 * i);
   return r;
 }
-ICAMD_DEV uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
+// (selectors 8..11: the sign bit of byte 1, 3, 5, 7 replicated; 12: 0x00; 13..255: 0xff)
+ICAMD_DEV uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel, ICAMD_EMUL_SITE) {
   uint64_t v = ((uint64_t)hi << 32) | lo;
   uint32_t r = 0;
+  bool ok = true;
   for (int i = 0; i < 4; ++i) {
-    uint32_t s = (sel >> (8 * i)) & 0xff;
-    uint32_t b = s <= 7 ? (uint32_t)((v >> (8 * s)) & 0xff) : (s == 0x0c ? 0u : 0xffu);
+    uint32_t s = (sel >> (8 * i)) & 0xff, b;
+    if (s <= 7) b = (uint32_t)((v >> (8 * s)) & 0xff);
+    else if (s <= 11) b = ((v >> (16 * (s - 8) + 15)) & 1) ? 0xffu : 0u;
+    else b = s == 0x0c ? 0u : 0xffu;
+    ok = ok && (s <= 7 || s == 0x0c);
     r |= b << (8 * i);
   }
+  ICAMD_EMUL_DOMAIN(ok, "perm", hi, lo, sel);
   return r;
 }
-ICAMD_DEV uint32_t bfe(uint32_t v, uint32_t off, uint32_t w) { return (v >> off) & ((1u << w) - 1u); }
-ICAMD_DEV uint32_t bit_mask(uint32_t v, uint32_t bit) { return (v >> bit) & 1u ? 0xffffffffu : 0u; }
-ICAMD_DEV int32_t imad24(int32_t a, int32_t b, int32_t c) { return a * b + c; }
-// (the low 24 bits of each operand, as v_mad_u32_u24 takes them: an operand out of range shows in the host tier too)
-ICAMD_DEV uint32_t umad24(uint32_t a, uint32_t b, uint32_t c) { return (a & 0xffffffu) * (b & 0xffffffu) + c; }
+// (v_bfe_u32 / v_bfe_i32 read five bits of the offset and five of the width: a width of 32 is a width of 0)
+ICAMD_DEV uint32_t bfe(uint32_t v, uint32_t off, uint32_t w, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(off < 32u && w < 32u, "bfe", v, off, w);
+  return (v >> (off & 31u)) & ((1u << (w & 31u)) - 1u);
+}
+ICAMD_DEV uint32_t bit_mask(uint32_t v, uint32_t bit, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(bit < 32u, "bit_mask", v, bit, 0u);
+  return (v >> (bit & 31u)) & 1u ? 0xffffffffu : 0u;
+}
+// (the low 24 bits of each operand, sign-extended, as v_mad_i32_i24 takes them; the low 32 bits of the sum)
+ICAMD_DEV int32_t imad24(int32_t a, int32_t b, int32_t c, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(a > -(1 << 23) && a < (1 << 23) && b > -(1 << 23) && b < (1 << 23), "imad24", a, b, c);
+  const int64_t a24 = (int32_t)((uint32_t)a << 8) >> 8, b24 = (int32_t)((uint32_t)b << 8) >> 8;
+  return (int32_t)((uint32_t)(uint64_t)(a24 * b24) + (uint32_t)c);
+}
+// (the low 24 bits of each operand, as v_mad_u32_u24 takes them)
+ICAMD_DEV uint32_t umad24(uint32_t a, uint32_t b, uint32_t c, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(a < (1u << 24) && b < (1u << 24), "umad24", a, b, c);
+  return (a & 0xffffffu) * (b & 0xffffffu) + c;
+}
 ICAMD_DEV uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 ICAMD_DEV uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 ICAMD_DEV int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
@@ -132,18 +191,21 @@ ICAMD_DEV uint32_t sad_u8(uint32_t a, uint32_t b, uint32_t c) { return __builtin
 ICAMD_DEV uint32_t sad_hi_u8(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_sad_hi_u8(a, b, c); }  // (sad << 16) + c
 // v_lerp_u8 with a zero rounding operand: per byte (a + b) >> 1 -- four floor-averages in one instruction
 ICAMD_DEV uint32_t avg_u8(uint32_t a, uint32_t b) { return __builtin_amdgcn_lerp(a, b, 0u); }
-// v_alignbit_b32: low 32 bits of ({hi,lo} >> sh)
+// v_alignbit_b32: low 32 bits of ({hi,lo} >> sh).  PRECONDITION sh < 32 (the instruction reads sh & 31).
 ICAMD_DEV uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
 // v_perm_b32: byte i of the result = byte sel.b[i] of the 8-byte value {hi,lo}
-// (selector 0..3 -> lo bytes, 4..7 -> hi bytes, 0x0c -> 0x00).
+// (selector 0..3 -> lo bytes, 4..7 -> hi bytes, 0x0c -> 0x00).  PRECONDITION every selector byte is 0..7 or 0x0c
+// (8..11 replicate the sign bit of byte 1, 3, 5, 7; 13..255 give 0xff: nothing here relies on either).
 ICAMD_DEV uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+// v_bfe_u32: (v >> off) & (2^w - 1).  PRECONDITION off < 32 and w < 32 (the instruction reads off & 31 and w & 31: a width
+// of 32 extracts nothing).
 ICAMD_DEV uint32_t bfe(uint32_t v, uint32_t off, uint32_t w) { return __builtin_amdgcn_ubfe(v, off, w); }
-// v_bfe_i32 of a one-bit field: all ones iff bit `bit` of v is set
+// v_bfe_i32 of a one-bit field: all ones iff bit `bit` of v is set.  PRECONDITION bit < 32 (read as bit & 31).
 ICAMD_DEV uint32_t bit_mask(uint32_t v, uint32_t bit) { return (uint32_t)__builtin_amdgcn_sbfe((int32_t)v, bit, 1u); }
 // v_mad_i32_i24: a * b + c.  PRECONDITION |a|, |b| < 2^23 (the compiler cannot prove it and would emit
 // v_mul_lo_u32 + v_add_u32 for the plain expression).
 ICAMD_DEV int32_t imad24(int32_t a, int32_t b, int32_t c) { return __mul24(a, b) + c; }
-// v_mad_u32_u24: the same for unsigned operands below 2^24 (v_mul_lo_u32, what the plain product compiles to when the
+// v_mad_u32_u24: the same for unsigned operands.  PRECONDITION a, b < 2^24 (v_mul_lo_u32, what the plain product compiles to when the
 // range is not provable, issues at a quarter of the rate)
 ICAMD_DEV uint32_t umad24(uint32_t a, uint32_t b, uint32_t c) { return __umul24(a, b) + c; }
 ICAMD_DEV uint32_t umin(uint32_t a, uint32_t b) { return min(a, b); }
@@ -185,7 +247,14 @@ ICAMD_DEV uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { return umin(umin(
 ICAMD_DEV uint32_t umax3(uint32_t a, uint32_t b, uint32_t c) { return umax(umax(a, b), c); }
 ICAMD_DEV int32_t imax3(int32_t a, int32_t b, int32_t c) { return imax(imax(a, b), c); }
 
+#if defined(ICAMD_HOST_EMULATION)
+ICAMD_DEV uint32_t fastdiv(uint32_t n, const FastDiv &f, ICAMD_EMUL_SITE) {
+  ICAMD_EMUL_DOMAIN(n < (1u << 31) && f.shift < 32u, "fastdiv", n, f.mul, f.shift);  // (d <= 2^31 iff shift <= 31)
+  return (umulhi32(n, f.mul) + n) >> (f.shift & 31u);
+}
+#else
 ICAMD_DEV uint32_t fastdiv(uint32_t n, const FastDiv &f) { return (umulhi32(n, f.mul) + n) >> f.shift; }
+#endif
 
 // Unaligned-tolerant vector loads (gfx950 global memory runs in unaligned-access
 // mode; the backend emits one global_load_dwordx3/x4 for these).

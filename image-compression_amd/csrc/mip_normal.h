@@ -38,31 +38,39 @@ ICAMD_DEV uint32_t normal_div_settle(uint32_t n, uint32_t d, uint32_t q) {
 // the square root (below 2^15) is off by less than 2^-8 and the quotient (below 2^19) by less than 2^-2 before truncation:
 // the truncated guess is the floor or its neighbour.  BIAS (host emulation only) replaces the guess by the exact floor + BIAS,
 // clamped at 0: the tests run every case with the guess forced one off in either direction.
+// (the raw truncated guesses on their own, so that tests/device_probe measures the expressions the filter runs)
+#if defined(ICAMD_HOST_EMULATION)
+ICAMD_DEV uint32_t normal_isqrt_guess(uint32_t n) { return (uint32_t)sqrtf((float)n); }
+ICAMD_DEV uint32_t normal_div_guess(uint32_t n, uint32_t d) { return (uint32_t)((float)n * (1.0f / (float)d)); }
+#else
+ICAMD_DEV uint32_t normal_isqrt_guess(uint32_t n) { return (uint32_t)__builtin_amdgcn_sqrtf((float)n); }
+ICAMD_DEV uint32_t normal_div_guess(uint32_t n, uint32_t d) { return (uint32_t)((float)n * __builtin_amdgcn_rcpf((float)d)); }
+#endif
 template <int BIAS>
 ICAMD_DEV uint32_t normal_isqrt(uint32_t n) {
 #if defined(ICAMD_HOST_EMULATION)
+  if (n >= 1u << 30) emul::violate("normal_isqrt", n, 0u, 0u, __FILE__, __LINE__);
   if (BIAS != 0) {
     const int32_t s = (int32_t)sqrt((double)n) + BIAS;
     return normal_isqrt_settle(n, (uint32_t)(s < 0 ? 0 : s));
   }
-  return normal_isqrt_settle(n, (uint32_t)sqrtf((float)n));
 #else
   static_assert(BIAS == 0, "the biased guess is for the host emulation");
-  return normal_isqrt_settle(n, (uint32_t)__builtin_amdgcn_sqrtf((float)n));
 #endif
+  return normal_isqrt_settle(n, normal_isqrt_guess(n));
 }
 template <int BIAS>
 ICAMD_DEV uint32_t normal_div(uint32_t n, uint32_t d) {
 #if defined(ICAMD_HOST_EMULATION)
+  if (!((n < 1u << 23 && d >= 16u && d < 1u << 15) || (n == 0u && d >= 1u))) emul::violate("normal_div", n, d, 0u, __FILE__, __LINE__);
   if (BIAS != 0) {
     const int32_t q = (int32_t)(n / d) + BIAS;
     return normal_div_settle(n, d, (uint32_t)(q < 0 ? 0 : q));
   }
-  return normal_div_settle(n, d, (uint32_t)((float)n * (1.0f / (float)d)));
 #else
   static_assert(BIAS == 0, "the biased guess is for the host emulation");
-  return normal_div_settle(n, d, (uint32_t)((float)n * __builtin_amdgcn_rcpf((float)d)));
 #endif
+  return normal_div_settle(n, d, normal_div_guess(n, d));
 }
 
 // z of one texel: the nearest integer to sqrt(max(0, 255^2 - x^2 - y^2)), x = 2r - 255, y = 2g - 255.

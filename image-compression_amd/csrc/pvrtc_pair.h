@@ -83,11 +83,7 @@ ICAMD_DEV uint32_t pvrtc_block_modulation(const uint32_t rows[4][2], uint32_t ri
     for (int h = 0; h < 2; ++h) {
       const uint32_t r = rows[y][h];
       // pixels best served by an intermediate value (1 or 2): low bit xor high bit of each byte
-#if defined(ICAMD_HOST_EMULATION)
-      inter += (uint32_t)__builtin_popcount((r ^ (r >> 1)) & 0x01010101u);
-#else
-      inter += (uint32_t)__popc((r ^ (r >> 1)) & 0x01010101u);
-#endif
+      inter += popcount_u32((r ^ (r >> 1)) & 0x01010101u);
       // "horizontal_count" in the source sums |m - m(x, y+1)|, "vertical_count" |m - m(x+1, y)|
       // (the names are swapped there, pvrtc.cc:426-429; kept as the reference computes them).
       const uint32_t down = y < 3 ? rows[y + 1][h] : below[h];

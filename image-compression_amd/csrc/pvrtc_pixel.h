@@ -221,14 +221,16 @@ static_assert(blend53_is_nested_average(), "(5a+3b)/8 != avg(a, avg(b, avg(a,b))
 // B_rb, B_ga) -- the reference's truncated 8-bit channels (pvrtc.cc:228-236, sum / 32) are therefore exactly the
 // HIGH BYTES of the four 16-bit lanes, and one v_perm_b32 per colour packs them as R,G,B,A.  The two intermediate
 // colours (5A+3B)/8 and (3A+5B)/8 (pvrtc.cc:111-135) are nested byte averages (v_lerp_u8, all four channels per
-// instruction), the four L1 distances are v_sad_u8.  The value (0..3) is ADDED into `acc` at the byte whose unit
-// is `unit` (1, 1<<8, ...).  Same decisions as best_modulation().
+// instruction), the four L1 distances are v_sad_u8.  The value (0..3) lands in `acc` at the byte whose unit is
+// `unit` (1, 1<<8, ...), which is zero on entry: the plain form adds it there, the SDWA form writes the byte (with unit 1 the
+// whole dword) -- the same thing inside the precondition below.  Same decisions as best_modulation().
 #if !defined(ICAMD_HOST_EMULATION) && !defined(ICAMD_PVRTC_NO_SCAN_SDWA)  // kept: tests/test_isa_guards.py builds the plain form
 // The early-exit scan  s1 + (s1 && s2) + (s1 && s2 && s3)  as nested selects  e1 ? (e2 ? (e3 ? 3 : 2) : 1) : 0  on VCC, the
 // last select writing byte J of `acc` in place (SDWA dst_sel, the other bytes preserved): 3 v_cmp + 3 v_cndmask and no scalar
 // instruction, where the plain expression compiles to 3 v_cmp + 2 s_and_b64 + 2 v_cndmask + v_addc + v_lshl_add (r05: -2 %
 // on the one-pass kernel, profiles/r05_ab_pvrtc_onepass.log; -DICAMD_PVRTC_NO_SCAN_SDWA builds the plain form).  The byte of
-// `acc` that `unit` addresses must be zero on entry.
+// `acc` that `unit` addresses must be zero on entry.  PRECONDITION unit is 1, 2^8, 2^16 or 2^24; the byte of `acc` it addresses
+// is zero, and with unit 1 the whole of `acc` is zero (only there do this form and the plain one agree).
 ICAMD_DEV uint32_t scan_into_byte(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t unit, uint32_t acc) {
   uint32_t x;
   const uint32_t three = 3u, zero = 0u;
@@ -246,6 +248,18 @@ ICAMD_DEV uint32_t scan_into_byte(uint32_t d0, uint32_t d1, uint32_t d2, uint32_
 #undef ICAMD_SCAN_TAIL
 #undef ICAMD_SCAN_OPS
   return acc;
+}
+#elif defined(ICAMD_HOST_EMULATION)
+// (the SDWA form, which is what the kernels run: the value REPLACES the byte `unit` addresses, and unit 1 replaces the whole
+// dword; a unit that is none of the four counts as the last, as in the chain of comparisons above -- that case is NOT probed on
+// the device, tests/device_probe fixes the unit per op as every caller does)
+ICAMD_DEV uint32_t scan_into_byte(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t unit, uint32_t acc, ICAMD_EMUL_SITE) {
+  const bool s1 = d1 < d0, s2 = s1 && d2 < d1, s3 = s2 && d3 < d2;  // stop at the first non-improving step
+  const uint32_t x = (uint32_t)s1 + (uint32_t)s2 + (uint32_t)s3;
+  const uint32_t byte = unit == 1u ? 0u : unit == 1u << 8 ? 1u : unit == 1u << 16 ? 2u : 3u;
+  ICAMD_EMUL_DOMAIN((unit == 1u ? acc == 0u : ((acc >> (8u * byte)) & 0xffu) == 0u) && unit == 1u << (8u * byte), "scan_into_byte",
+                    unit, acc, x);
+  return byte == 0u ? x : (acc & ~(0xffu << (8u * byte))) | x << (8u * byte);
 }
 #else
 ICAMD_DEV uint32_t scan_into_byte(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t unit, uint32_t acc) {

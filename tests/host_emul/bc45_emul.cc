@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "bc45_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

@@ -14,6 +14,7 @@
 #include "pvrtc_block.h"
 #include "decode_block.h"
 #include "blockops_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

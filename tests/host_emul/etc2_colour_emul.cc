@@ -11,6 +11,7 @@
 #include "etc1_block.h"
 #include "etc2_block.h"
 #include "etc2_colour_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

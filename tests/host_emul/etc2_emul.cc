@@ -9,6 +9,7 @@
 
 #include "etc1_block.h"
 #include "etc2_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "metric_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

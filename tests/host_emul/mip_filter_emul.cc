@@ -5,6 +5,7 @@
 #error "build with -DICAMD_HOST_EMULATION"
 #endif
 #include "mip_filter.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

@@ -6,6 +6,7 @@
 #error "build with -DICAMD_HOST_EMULATION"
 #endif
 #include "mip_normal.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "transcode5_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "blockops_block.h"
+#include "emul_violations.h"
 
 using namespace icamd;
 

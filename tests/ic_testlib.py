@@ -89,6 +89,16 @@ def ref():
     return _ref
 
 
+def assert_no_emul_violations(L, what):
+    """Teardown of every host-emulation fixture: no wrapper twin saw an operand outside its stated domain
+    (tests/host_emul/emul_violations.h)."""
+    L.icamd_emul_violations.restype = ctypes.c_ulonglong
+    L.icamd_emul_violations.argtypes = [ctypes.c_char_p, sz]
+    first = ctypes.create_string_buffer(256)
+    n = L.icamd_emul_violations(first, len(first))
+    assert n == 0, "%s: %d operand(s) outside a wrapper's stated domain, first: %s" % (what, n, first.value.decode())
+
+
 # ------------------------------------------------------------------ wrappers
 
 

@@ -15,6 +15,7 @@
 #include "ic_oracle.h"
 
 extern "C" {
+unsigned long long icamd_emul_violations(char *first, size_t n);
 int emul_encode(int codec, int strategy, int comps, int swap, uint32_t h, uint32_t w, uint32_t gh, uint32_t gw,
                 uint32_t stride, const uint8_t *src, uint8_t *out);
 int emul_decode(int codec, int swap, uint32_t h, uint32_t w, uint32_t pad, const uint8_t *blocks, uint8_t *out);
@@ -153,6 +154,9 @@ int main() {
       CHECK(emul_decode(ICO_PVRTC2, 0, n, n, 0, a.data(), pb.data()) == 1, "emul_decode pvrtc");
       CHECK(pa == pb, "pvrtc decode mismatch %u", n);
     }
+  char first[256] = "";
+  const unsigned long long violations = icamd_emul_violations(first, sizeof first);
+  CHECK(violations == 0, "%llu operand(s) outside a wrapper's domain, first %s", violations, first);
   if (failures) {
     fprintf(stderr, "%d check(s) failed\n", failures);
     return 1;

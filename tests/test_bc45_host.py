@@ -37,7 +37,8 @@ def emul(tmp_path_factory):
     L.bc45_emul_decode.argtypes = [T.ci, T.u32, T.u32, T.u32, T.vp, T.vp]
     L.bc45_emul_block_both.restype = None
     L.bc45_emul_block_both.argtypes = [T.vp, T.ci, T.vp, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_bc45_host")
 
 
 def emul_encode(L, codec, flat, h, w, comps, swap=0, gh=None, gw=None, stride=None, packed_only=0):

@@ -60,7 +60,8 @@ def emul(tmp_path_factory):
     L.etc2c_emul_planar_pack.argtypes = [T.u32, T.vp, T.vp, T.vp]
     L.etc2c_emul_decode_rgba8.restype = ctypes.c_int
     L.etc2c_emul_decode_rgba8.argtypes = [T.ci, T.u32, T.u32, T.u32, T.vp, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_etc2_colour_host")
 
 
 def emul_decode_words(L, words):

@@ -43,7 +43,8 @@ def emul(tmp_path_factory):
     L.etc2_emul_alpha_block.argtypes = [T.vp, T.vp, T.vp]
     L.etc2_emul_modifier.restype = ctypes.c_int
     L.etc2_emul_modifier.argtypes = [T.ci, T.ci]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_etc2_host")
 
 
 def emul_encode(L, flat, h, w, strategy, gh=None, gw=None, stride=None):

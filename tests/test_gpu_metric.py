@@ -11,6 +11,7 @@ import pytest
 import bc45_oracle as B
 import ic_testlib as T
 import metric_oracle as M
+import wrapper_cases as W
 
 pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("image-compression_amd")
@@ -32,6 +33,8 @@ def _to_dev(buf, dev):
 def _measure(codec, src, blocks, h, w, comps, dev, **kw):
     """(sse [n, 4], max_abs [n, 4]) as numpy int64; src / blocks: bytes-like or device tensors."""
     import torch
+    launch = (max(kw.get("grid_height") or h, h), max(kw.get("grid_width") or w, w), kw.get("n_images", 1))
+    assert launch in W.METRIC_GRIDS, "list %r in wrapper_cases.METRIC_GRIDS: fastdiv is probed at this file's divisors" % (launch,)
     s = src if hasattr(src, "is_cuda") else _to_dev(src, dev)
     b = blocks if hasattr(blocks, "is_cuda") else _to_dev(blocks, dev)
     got = pkg.measure_error_device(codec, s, b, h, w, comps, **kw)
@@ -256,3 +259,35 @@ def test_cxx_member_equals_the_c_abi(tmp_path):
     out = r.stdout.decode()
     assert r.returncode == 0, out + r.stderr.decode()
     assert out.count("OK ") == 7 and "BAD" not in out, out
+
+
+def _extreme_pair(codec, comps, swap, h, w):
+    """(source of zeros, the oracle's blocks for an all-255 image of the same shape, the definition's record)."""
+    src = np.zeros((h, w, comps), np.uint8)
+    white = np.full((h, w, comps), 255, np.uint8)
+    blocks = T.oracle_encode(codec, white, h, w, 4) if codec in (M.PVRTC2, M.PVRTC4) else _encode(codec, white, h, w, comps, swap)
+    want = M.measure(codec, src, blocks, h, w, comps, swap)
+    for k, _, _ in M.channel_pairs(codec, comps, swap):  # a condition on the input alone: every difference is at the top
+        assert want[1][k] >= 247, (codec, comps, swap, k, want[1])
+    return src, blocks, want
+
+
+def _extreme_batch(dev, codec, comps, swap, h, w, n):
+    src, blocks, want = _extreme_pair(codec, comps, swap, h, w)
+    got = _measure(codec, src.tobytes() * n, bytes(blocks) * n, h, w, comps, dev, swap_rb=bool(swap), n_images=n)
+    for i in range(n):
+        _check(got, want, i, what=("extremes", codec, comps, swap, h, w, n, i))
+
+
+def test_partial_sums_at_the_top_of_their_range(dev):
+    """metric_block.h budgets 256 * 4 * 32 * 65025 < 2^32 for a workgroup's 32-bit partial sums: every pixel of every block of a
+    full workgroup differs by (nearly) 255 -- 128 x 128 is 1024 blocks -- and the same extremes through the per-wave flush of a
+    workgroup that spans 37 small images."""
+    for codec, comps, swap in M.BLOCK_LAYOUTS:
+        _extreme_batch(dev, codec, comps, swap, 128, 128, 1)
+        _extreme_batch(dev, codec, comps, swap, 8, 8, 37)
+
+
+def test_pvrtc_partial_sums_at_the_top_of_their_range(dev):
+    for codec, comps, swap in M.PVRTC_LAYOUTS:
+        _extreme_batch(dev, codec, comps, swap, 256, 256, 1)

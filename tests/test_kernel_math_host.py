@@ -26,7 +26,8 @@ def emul():
     L = ctypes.CDLL(so)
     L.emul_encode.restype = ctypes.c_int
     L.emul_encode.argtypes = [T.ci, T.ci, T.ci, T.ci, T.u32, T.u32, T.u32, T.u32, T.u32, T.vp, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_kernel_math_host")
 
 
 def emul_encode(L, codec, src, h, w, comps, swap=0, strategy=2, gh=None, gw=None, stride=None):

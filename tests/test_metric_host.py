@@ -35,7 +35,8 @@ def emul(tmp_path_factory):
     L = ctypes.CDLL(so)
     L.metric_emul_measure.restype = ctypes.c_int
     L.metric_emul_measure.argtypes = [T.ci, T.ci, T.ci, T.ci, T.u32, T.u32, T.u32, T.u32, T.u32, T.vp, T.vp, T.vp, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_metric_host")
 
 
 def emul_measure(L, codec, flat, blocks, h, w, comps, swap=0, gh=None, gw=None, stride=None, gather=0):

@@ -45,7 +45,8 @@ def emul(tmp_path_factory):
     L.mip_filter_emul_quotient.argtypes = [T.vp, T.vp, T.u32, T.vp]
     L.mip_filter_emul_quads.restype = ctypes.c_int
     L.mip_filter_emul_quads.argtypes = [T.ci, T.ci, T.vp, T.u32, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_mip_filters_host")
 
 
 # ---- the oracle

@@ -48,7 +48,8 @@ def emul(tmp_path_factory):
     L.mip_normal_emul_code.argtypes = [T.ci, T.vp, T.vp, T.u32, T.vp]
     L.mip_normal_emul_quads.restype = ctypes.c_int
     L.mip_normal_emul_quads.argtypes = [T.ci, T.ci, T.ci, T.vp, T.u32, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_mip_normal_host")
 
 
 # ---- the oracle

@@ -41,7 +41,8 @@ def emul(tmp_path_factory):
         getattr(L, name).argtypes = [T.sz, T.vp, T.vp]
     L.transcode5_emul_colour.restype = None
     L.transcode5_emul_colour.argtypes = [T.ci, T.sz, T.vp, T.vp]
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_transcode5_host")
 
 
 def emul_transcode(L, blocks):

@@ -42,7 +42,8 @@ def wave():
         getattr(L, name).argtypes = args
     L.wemul_error.restype = ctypes.c_char_p
     L.so_path = so
-    return L
+    yield L
+    T.assert_no_emul_violations(L, "test_wave_votes_host")
 
 
 def _check(L, ok, what):
