@@ -44,6 +44,11 @@ ETC2_RGBA8 = 16
 # encoder's word or the least-squares planar word, whichever is strictly closer.  17 is unassigned and rejected.
 # encode_device / decode_device / measure_error_device / containers only
 ETC2_RGB8 = 18
+# EXTENSION (include/ic_amd.h ICAMD_EAC_R11): EAC R11 (one channel, 8 bytes per block) and EAC RG11 (two channels, 16 bytes per
+# block), the ETC2 family's BC4 / BC5; every word is what ETC2 RGBA8's alpha search writes for the channel, the
+# decoder is the 11-bit one.  Source channels as for BC4 / BC5.  encode_device / decode_device / measure_error_device /
+# containers only
+EAC_R11, EAC_RG11 = 19, 20
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -144,8 +149,8 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
                   src_image_stride_bytes=None, out=None, stream=None):
     """Launch the encode kernel on `src` (a torch.uint8 CUDA tensor, any shape, contiguous bytes).
     Returns the output tensor [n_images, encoded_size] (device).  No synchronisation.
-    BC4 reads R from 1..4-byte pixels, BC5 reads R and G from 2..4-byte pixels: R = byte 0 (byte 2 with swap_rb, which needs
-    3 or 4 bytes per pixel), G = byte 1."""
+    BC4 and EAC_R11 read R from 1..4-byte pixels, BC5 and EAC_RG11 read R and G from 2..4-byte pixels: R = byte 0 (byte 2 with
+    swap_rb, which needs 3 or 4 bytes per pixel), G = byte 1."""
     _assert_u8_cuda(src)
     gh = height if grid_height is None else max(grid_height, height)
     gw = width if grid_width is None else max(grid_width, width)
@@ -212,7 +217,8 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     _assert_u8_cuda(blocks)
-    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, BC4: 1, BC5: 2}.get(codec, 3)  # BC4 -> R8, BC5 -> RG8
+    # BC4 and EAC_R11 -> R8, BC5 and EAC_RG11 -> RG8
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

@@ -219,16 +219,20 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr,
 }
 
 // Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 4,
-// BC4 1..4, BC5 2..4.
+// BC4 and EAC R11 1..4, BC5 and EAC RG11 2..4.
 bool codec_accepts_components(int codec, int comps) {
   switch (codec) {
     case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: return comps == 3 || comps == 4;
     case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: return comps == 4;
-    case ICAMD_BC4: return comps >= 1 && comps <= 4;
-    case ICAMD_BC5: return comps >= 2 && comps <= 4;
+    case ICAMD_BC4: case ICAMD_EAC_R11: return comps >= 1 && comps <= 4;
+    case ICAMD_BC5: case ICAMD_EAC_RG11: return comps >= 2 && comps <= 4;
   }
   return false;
 }
+// The one- and two-channel codecs (R, or R and G, of 1..4-byte pixels; R8 / RG8 rows out): BC4 / BC5 and EAC R11 / RG11.
+bool plane_codec(int codec) { return codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
+bool two_plane_codec(int codec) { return codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11; }
+bool eac11_codec(int codec) { return codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
 
 // The sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650): a square power of two of at least 8 x 8 (for a square
 // power of two, width % 8 == 0 && height % 4 == 0 is width >= 8).  The reference sizes its output with the uint32 product
@@ -317,13 +321,16 @@ icamd::GridParams grid_params(const void *d_src, void *d_dst, uint32_t height, u
   return P;
 }
 
-// EXTENSION (include/ic_amd.h ICAMD_BC4): BC4 from 1..4-byte sources, BC5 from 2..4-byte ones; R = byte 0 (byte 2 when swap_rb
-// and the source has 3 or 4 bytes), G = byte 1.  The argument checks come before any device work.
-int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_height,
+// EXTENSION (include/ic_amd.h ICAMD_BC4, ICAMD_EAC_R11): BC4 / EAC R11 from 1..4-byte sources, BC5 / EAC RG11 from 2..4-byte ones;
+// R = byte 0 (byte 2 when swap_rb and the source has 3 or 4 bytes), G = byte 1.  The argument checks come before any device work.
+int plane_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_height,
                             uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, hipStream_t stream) {
   if (!codec_accepts_components(codec, src_components))
-    return fail(ICAMD_ERR_ARG, codec == ICAMD_BC5 ? "BC5 needs 2, 3 or 4 source components" : "BC4 needs 1 to 4 source components");
+    return fail(ICAMD_ERR_ARG, codec == ICAMD_BC5 ? "BC5 needs 2, 3 or 4 source components"
+                               : codec == ICAMD_BC4 ? "BC4 needs 1 to 4 source components"
+                               : codec == ICAMD_EAC_RG11 ? "EAC RG11 needs 2, 3 or 4 source components"
+                                                         : "EAC R11 needs 1 to 4 source components");
   if (swap_rb && src_components < 3) return fail(ICAMD_ERR_ARG, "swap_rb needs a 3- or 4-component source");
   if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components)
     return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
@@ -332,7 +339,10 @@ int bc45_encode_device_impl(int codec, int src_components, int swap_rb, uint32_t
   if (rc != ICAMD_OK) return rc;
   const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
                                           src_image_stride_bytes, dst_image_stride_bytes, swap_rb, 0);
-  ICAMD_HIP(icamd::launch_bc45_encode(codec, src_components, P, stream), codec == ICAMD_BC5 ? "launch bc5" : "launch bc4");
+  if (eac11_codec(codec))
+    ICAMD_HIP(icamd::launch_eac11_encode(codec, src_components, P, stream), "launch eac r11 / rg11");
+  else
+    ICAMD_HIP(icamd::launch_bc45_encode(codec, src_components, P, stream), codec == ICAMD_BC5 ? "launch bc5" : "launch bc4");
   return ICAMD_OK;
 }
 
@@ -478,6 +488,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_PVRTC2: return icamd::pvrtc2_kernel_name();
     case ICAMD_PVRTC4: return icamd::pvrtc4_kernel_name();
     case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
+    case ICAMD_EAC_R11: case ICAMD_EAC_RG11: return icamd::eac11_kernel_name(codec, src_components);
   }
   return "";
 }
@@ -512,9 +523,9 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
                         const void *d_src, void *d_dst, void *hip_stream) try {
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (codec == ICAMD_BC4 || codec == ICAMD_BC5)
-    return bc45_encode_device_impl(codec, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
-                                   n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, stream);
+  if (plane_codec(codec))
+    return plane_encode_device_impl(codec, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
+                                    n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, stream);
   if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
   // EXTENSION (include/ic_amd.h ICAMD_ETC2_RGBA8): the alpha half needs the fourth byte; checked before any device work
   if (codec == ICAMD_ETC2_RGBA8 && src_components != 4) return fail(ICAMD_ERR_ARG, "ETC2 RGBA8 needs a 4-component source");
@@ -758,19 +769,19 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                         const void *d_blocks, void *d_pixels, void *hip_stream) try {
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
-  const bool bc45 = codec == ICAMD_BC4 || codec == ICAMD_BC5;
+  const bool plane = plane_codec(codec);  // (BC4 / BC5 and EAC R11 / RG11: R8 / RG8 rows)
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 &&
-      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && !bc45)
+      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && !plane)
     return ICAMD_FALSE;
-  if (bc45 && swap_rb) return fail(ICAMD_ERR_ARG, "BC4 / BC5 decode: swap_rb must be 0");
+  if (plane && swap_rb) return fail(ICAMD_ERR_ARG, eac11_codec(codec) ? "EAC R11 / RG11 decode: swap_rb must be 0" : "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
   uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
-  if (bc45) {
-    // EXTENSION (include/ic_amd.h ICAMD_BC4): R8 / RG8 rows; 64-bit addressing and chunked grids, so no banding is needed
+  if (plane) {
+    // EXTENSION (include/ic_amd.h ICAMD_BC4, ICAMD_EAC_R11): R8 / RG8 rows; 64-bit addressing and chunked grids, so no banding is needed
     icamd::Bc45DecodeParams P;
     P.blocks = blocks;
     P.pixels = pixels;
@@ -780,9 +791,12 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     P.width = width;
     P.block_rows = num_blocks4(height);
     P.block_cols = num_blocks4(width);
-    P.row_stride = width * (codec == ICAMD_BC5 ? 2u : 1u) + padding_bytes_per_row;
+    P.row_stride = width * (two_plane_codec(codec) ? 2u : 1u) + padding_bytes_per_row;
     P.log2_tile_cols = P.tile_row0 = 0;
-    ICAMD_HIP(icamd::launch_bc45_decode(codec, n_images, P, stream), "launch bc4 / bc5 decode");
+    if (eac11_codec(codec))
+      ICAMD_HIP(icamd::launch_eac11_decode(codec, n_images, P, stream), "launch eac r11 / rg11 decode");
+    else
+      ICAMD_HIP(icamd::launch_bc45_decode(codec, n_images, P, stream), "launch bc4 / bc5 decode");
     return ICAMD_OK;
   }
   const bool pvrtc = codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4;
@@ -1444,8 +1458,7 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
                           const uint8_t *const *level_data, const size_t *level_sizes, uint8_t *out, size_t out_size) try {
   using namespace icamd;
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
-  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && codec != ICAMD_BC4 && codec != ICAMD_BC5 && codec != ICAMD_ETC2_RGBA8 &&
-                             codec != ICAMD_ETC2_RGB8))
+  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);
@@ -1487,7 +1500,7 @@ static int encode_mips(int codec, int etc_strategy, int src_components, int swap
   if (filter == ICAMD_MIP_FILTER_NORMAL && codec != ICAMD_BC5) return mip_check_filter(codec, src_components, filter);
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
-  if (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8)
+  if (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || eac11_codec(codec))  // (EAC R11 / RG11: of the ETC2 family)
     return fail(ICAMD_ERR_ARG, "ETC2 has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;

@@ -162,6 +162,11 @@ struct Bc45DecodeParams {
 hipError_t launch_bc45_encode(int codec, int comps, const GridParams &P, hipStream_t stream);
 hipError_t launch_bc45_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
 const char *bc45_kernel_name(int codec, int comps);
+// EAC R11 / RG11 (extension, eac11_kernels.hip).  Encode: GridParams as for ETC1 (etc_strategy is not read), comps = 1..4 (R11) /
+// 2..4 (RG11).  Decode: Bc45DecodeParams and the lane groups of the BC4 / BC5 decoders, R8 / RG8 rows.
+hipError_t launch_eac11_encode(int codec, int comps, const GridParams &P, hipStream_t stream);
+hipError_t launch_eac11_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
+const char *eac11_kernel_name(int codec, int comps);  // "" where launch_eac11_encode has no kernel
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

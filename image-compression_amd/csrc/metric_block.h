@@ -7,7 +7,7 @@
 //  * pixels as R,G,B,A dwords (DXT1, DXT5, ETC1, PVRTC): |s - d| on 16-bit lanes, two channels per register -- (R, B) and
 //    (G, A) -- whose running maximum is one packed instruction each; the four pixels' differences of one channel are then
 //    four BYTES of a dword, and their sum of squares is one v_dot4_u32_u8 of that dword with itself;
-//  * one-channel rows, byte x = pixel x (BC4, BC5 -- the form decode_bc4_rows produces): sum d^2 = sum a^2 + sum b^2 -
+//  * one-channel rows, byte x = pixel x (BC4, BC5, EAC R11 / RG11 -- the form decode_bc4_rows and decode_eac11 produce): sum d^2 = sum a^2 + sum b^2 -
 //    2 sum a b, three v_dot4_u32_u8 per four values, and the maximum on the same 16-bit lanes.
 // Range: a squared byte difference is at most 65 025; a lane adds at most 4 blocks x 32 pixels of them, a workgroup 256 lanes:
 // 256 * 4 * 32 * 65 025 < 2^32.
@@ -15,6 +15,7 @@
 #define ICAMD_METRIC_BLOCK_H_
 
 #include "bc45_block.h"  // blockops_block.h (decode_block_rows), decode_block.h, dxt_block.h (packed 16-bit helpers)
+#include "eac11_block.h"  // decode_eac11
 #include "etc2_block.h"  // decode_etc2_rgba8, decode_etc2_colour
 #include "ic_device.h"
 
@@ -172,8 +173,9 @@ ICAMD_DEV void metric_gather_channel(const uint8_t *img, uint32_t h, uint32_t wd
 }
 
 // BC4 (w[0..1]) / BC5 (w[0..3]) block against channel R (and G) of the COMPS-byte source: R = byte 0, or byte 2 with swap
-// (3 or 4 components); G = byte 1.  PRECONDITION row < h, col < wd.
-template <int COMPS, bool BC5>
+// (3 or 4 components); G = byte 1.  EAC: the words are EAC R11 / RG11 words (decode_eac11) instead, same channels and rules.
+// PRECONDITION row < h, col < wd.
+template <int COMPS, bool BC5, bool EAC = false>
 ICAMD_DEV void metric_bc45_block(const uint32_t *w, bool swap, const uint8_t *img, uint32_t h, uint32_t wd, uint32_t stride,
                                  uint32_t row, uint32_t col, bool wide_ok, MetricAcc &a) {
   uint32_t sr[4], sg[4] = { 0, 0, 0, 0 }, dr[4], dg[4] = { 0, 0, 0, 0 };
@@ -204,8 +206,13 @@ ICAMD_DEV void metric_bc45_block(const uint32_t *w, bool swap, const uint8_t *im
     metric_gather_channel<COMPS>(img, h, wd, stride, row, col, rch, sr);
     if (BC5) metric_gather_channel<COMPS>(img, h, wd, stride, row, col, 1u, sg);
   }
-  decode_bc4_rows(w[0], w[1], dr);
-  if (BC5) decode_bc4_rows(w[2], w[3], dg);
+  if (EAC) {
+    decode_eac11(w[0], w[1], dr);
+    if (BC5) decode_eac11(w[2], w[3], dg);
+  } else {
+    decode_bc4_rows(w[0], w[1], dr);
+    if (BC5) decode_bc4_rows(w[2], w[3], dg);
+  }
   const uint32_t cols = umin(wd - col, 4u), rows = umin(h - row, 4u);
   const uint32_t m = cols >= 4u ? 0xffffffffu : (1u << (8u * cols)) - 1u;
   ICAMD_UNROLL

@@ -120,7 +120,34 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device,
         * icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions (KTX 0x9274, PKM 2.0 type 1,
         * PVR 22; no DDS) only: no Compressor + format pair selects it, and the mip entry points answer ICAMD_ERR_ARG. */
-       ICAMD_ETC2_RGB8 = 18 };
+       ICAMD_ETC2_RGB8 = 18,
+       /* EXTENSION: EAC R11 (COMPRESSED_R11_EAC, one channel, 8 bytes per 4 x 4 block) and EAC RG11 (COMPRESSED_RG11_EAC, two
+        * channels, 16 bytes per block: the word of R, then the word of G), in the raster block order of ETC1.  Unsigned only.
+        * They are to the ETC2 family what BC4 / BC5 are to DXT.  A word has the layout of the ETC2 RGBA8 alpha word: byte 0 =
+        * base, byte 1 = multiplier << 4 | table, then sixteen 3-bit indices, big-endian, texel i = 4 x + y in bits
+        * 47 - 3 i .. 45 - 3 i.
+        *   Decode (Khronos EAC, 11-bit): v11 = clamp(8 base + 4 + M[table][index] * (multiplier == 0 ? 1 : 8 multiplier), 0,
+        *       2047) with the modifier table of ICAMD_ETC2_RGBA8.  icamd_decode_device writes R8 (R11) or RG8 (RG11) rows of
+        *       width * 1 / width * 2 + padding bytes, as the BC4 / BC5 decoders do, and needs swap_rb = 0 (else ICAMD_ERR_ARG).
+        *       The byte written is v11 >> 3, the top byte of the specification's 16-bit expansion v11 << 5 | v11 >> 6.  For a
+        *       multiplier of 1 or more that is clamp(base + M multiplier, 0, 255), exactly the alpha decoder's byte (8 x + 4
+        *       clamped to 0..2047 and shifted is x clamped to 0..255).  For multiplier 0 it is not: the word
+        *       80 0d 7e 49 24 92 49 24 (base 128, multiplier 0, table 13, indices 3, 7, 4, 4, ...) gives v11 = 1018, 1037, 1028,
+        *       ... and the bytes 127, 129, 128, ..., where the alpha decoder gives 128 everywhere.  Base 255, multiplier 0,
+        *       table 0, index 7 clamps to 2047 -> 255; base 0, multiplier 0, table 0, index 3 clamps to 0.
+        *   Encode, a definition, PARITY PINNED through ICAMD_ETC2_RGBA8's alpha half: R11 of channel c of an image is bytes 0..7
+        *       of every block that icamd_encode_device(ICAMD_ETC2_RGBA8, ...) writes for the RGBA image whose alpha is channel c
+        *       -- the 144-candidate search stated there, the same clamp-to-edge replication and padded-grid fetch (no BC4-style
+        *       one-pixel rule), smallest (sse, table, multiplier, base), smallest index at each texel's minimum; multiplier 0 is
+        *       never written.  RG11 = R11(R) followed by R11(G).
+        * Source channels read by icamd_encode_device follow the ICAMD_BC4 rules: R = byte 0 (byte 2 when swap_rb and
+        * src_components >= 3), G = byte 1; R11 accepts src_components 1..4, RG11 2..4, swap_rb only with 3 or 4 (otherwise
+        * ICAMD_ERR_ARG); etc_strategy is ignored.  icamd_measure_error_device compares k = 0 (R11) or k = 0, 1 (RG11) against the
+        * decoder's byte.  Reachable through icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device,
+        * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
+        * (KTX 0x9270 / 0x9272, PKM 2.0 types 5 / 6, PVR 25 / 26; no DDS) only: no Compressor + format pair selects them, the mip
+        * entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0. */
+       ICAMD_EAC_R11 = 19, ICAMD_EAC_RG11 = 20 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -231,7 +258,8 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
  * src_image_stride_bytes) 16-byte aligned, d_dst (and dst_image_stride_bytes) 8-byte aligned, else ICAMD_ERR_ARG.
  * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT.
  * ETC2 RGBA8 (extension, see ICAMD_ETC2_RGBA8): src_components must be 4; otherwise as ETC1.
- * ETC2 RGB8 (extension, see ICAMD_ETC2_RGB8): src_components 3 or 4; as ETC1. */
+ * ETC2 RGB8 (extension, see ICAMD_ETC2_RGB8): src_components 3 or 4; as ETC1.
+ * EAC R11 / RG11 (extension, see ICAMD_EAC_R11): channels and argument rules as BC4 / BC5; grids, strides and batches as ETC1. */
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
                         uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
                         uint32_t row_stride_bytes, uint32_t n_images,
@@ -250,7 +278,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
  * punch-through weights 0, 4, 4, 8 with alpha 0 for value 2).  ICAMD_BC4 / ICAMD_BC5 (extension, see ICAMD_BC4) write
  * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG.  ICAMD_ETC2_RGBA8 (extension)
  * writes width*4 bytes per row plus the padding, ICAMD_ETC2_RGB8 (extension) width*3 like ICAMD_ETC1 (and like it stores the
- * channels in their stored order whatever swap_rb); both decode all five ETC2 colour modes. */
+ * channels in their stored order whatever swap_rb); both decode all five ETC2 colour modes.  ICAMD_EAC_R11 / ICAMD_EAC_RG11
+ * (extension) write R8 / RG8 rows under the BC4 / BC5 rules. */
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t padding_bytes_per_row, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
@@ -564,6 +593,7 @@ const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
  *     ETC2 RGBA8            bytes 0..3                        src_components 4
  *     BC4                   k = 0 is R                        src_components 1..4  (R, G located by the rules at ICAMD_BC4:
  *     BC5                   k = 0, 1 are R, G                 src_components 2..4   R = byte 0, or byte 2 with swap_rb)
+ *     EAC R11 / RG11        as BC4 / BC5                      src_components 1..4 / 2..4
  * Everything is integer arithmetic: the result is exact and the same from run to run.  PSNR over N pixels and C channels is
  * 10 log10(255^2 N C / sum of sse).
  * Arguments: source rules as icamd_encode_device, codec by codec (swap_rb only with 3 or 4 components; PVRTC ignores it, as
