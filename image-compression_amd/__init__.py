@@ -291,6 +291,54 @@ def transcode_dxt5_to_etc2_rgba8_device(t, stream=None):
     return t if _check(st, "icamd_transcode_dxt5_to_etc2_rgba8_device") else None
 
 
+def _transcode_host(symbol, blocks):
+    b = _host_u8(blocks, copy=True)
+    st = getattr(lib(), symbol)(b.ctypes.data, b.size)
+    return b.tobytes() if _check(st, symbol) else None
+
+
+def _transcode_device(symbol, t, stream):
+    _assert_u8_cuda(t)
+    st = getattr(lib(), symbol)(_ptr(t), t.numel(), _stream_handle(stream))
+    return t if _check(st, symbol) else None
+
+
+def transcode_dxt1_to_etc2_rgb8_host(blocks):
+    """icamd_transcode_dxt1_to_etc2_rgb8 (extension): DXT1 blocks (bytes-like) -> ETC2 RGB8 blocks of the same size; bytes past
+    the last whole 8-byte block come back unchanged."""
+    return _transcode_host("icamd_transcode_dxt1_to_etc2_rgb8", blocks)
+
+
+def transcode_dxt1_to_etc2_rgb8_device(t, stream=None):
+    """icamd_transcode_dxt1_to_etc2_rgb8_device (extension): the DXT1 blocks in `t` (a contiguous torch.uint8 CUDA tensor whose
+    storage is 8-byte aligned) become ETC2 RGB8 blocks IN PLACE; returns `t`.  No synchronisation."""
+    return _transcode_device("icamd_transcode_dxt1_to_etc2_rgb8_device", t, stream)
+
+
+def transcode_bc4_to_eac_r11_host(blocks):
+    """icamd_transcode_bc4_to_eac_r11 (extension): BC4 blocks (bytes-like) -> EAC R11 blocks of the same size; bytes past the
+    last whole 8-byte block come back unchanged."""
+    return _transcode_host("icamd_transcode_bc4_to_eac_r11", blocks)
+
+
+def transcode_bc4_to_eac_r11_device(t, stream=None):
+    """icamd_transcode_bc4_to_eac_r11_device (extension): the BC4 blocks in `t` (8-byte aligned) become EAC R11 blocks IN PLACE;
+    returns `t`.  No synchronisation."""
+    return _transcode_device("icamd_transcode_bc4_to_eac_r11_device", t, stream)
+
+
+def transcode_bc5_to_eac_rg11_host(blocks):
+    """icamd_transcode_bc5_to_eac_rg11 (extension): BC5 blocks (bytes-like) -> EAC RG11 blocks of the same size; bytes past the
+    last whole 16-byte block come back unchanged."""
+    return _transcode_host("icamd_transcode_bc5_to_eac_rg11", blocks)
+
+
+def transcode_bc5_to_eac_rg11_device(t, stream=None):
+    """icamd_transcode_bc5_to_eac_rg11_device (extension): the BC5 blocks in `t` (16-byte aligned) become EAC RG11 blocks IN
+    PLACE; returns `t`.  No synchronisation."""
+    return _transcode_device("icamd_transcode_bc5_to_eac_rg11_device", t, stream)
+
+
 def pvrtc_encode_region_device(src, size, first_block, n_blocks, *, out=None, stream=None):
     """icamd_pvrtc2_encode_region_device: blocks [first_block, first_block + n_blocks) of the Z-order output of the
     size x size RGBA8 image `src` (torch.uint8 CUDA tensor).  Returns the [8 * n_blocks] uint8 device tensor, or None

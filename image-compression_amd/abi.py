@@ -44,6 +44,12 @@ PROTOTYPES = (
     ("icamd_transcode_dxt1_to_etc1", i, [p, z]),
     ("icamd_transcode_dxt5_to_etc2_rgba8_device", i, [p, z, p]),
     ("icamd_transcode_dxt5_to_etc2_rgba8", i, [p, z]),
+    ("icamd_transcode_dxt1_to_etc2_rgb8_device", i, [p, z, p]),
+    ("icamd_transcode_dxt1_to_etc2_rgb8", i, [p, z]),
+    ("icamd_transcode_bc4_to_eac_r11_device", i, [p, z, p]),
+    ("icamd_transcode_bc4_to_eac_r11", i, [p, z]),
+    ("icamd_transcode_bc5_to_eac_rg11_device", i, [p, z, p]),
+    ("icamd_transcode_bc5_to_eac_rg11", i, [p, z]),
     ("icamd_compress_batch", i, [i, i, i, u, u, u, u, p, p, z, p, i, p]),
     ("icamd_encode_batch_sharded_device", i, [i, i, i, i, u, u, u, u, p, p, p, i, i, p, z, p]),
     ("icamd_rccl_available", i, []),

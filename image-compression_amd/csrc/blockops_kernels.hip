@@ -1,9 +1,10 @@
-// blockops_kernels.hip -- Pad / Downsample / DXT1->ETC1 and DXT5->ETC2 RGBA8 transcode kernels: one output
-// block per lane, coalesced 8/16-byte block loads and stores.  See blockops_block.h for the per-block math and
+// blockops_kernels.hip -- Pad / Downsample / DXT1->ETC1, DXT5->ETC2 RGBA8, DXT1->ETC2 RGB8, BC4->EAC R11 and BC5->EAC RG11
+// transcode kernels: one output block per lane, coalesced 8/16-byte block loads and stores.  See blockops_block.h for the per-block math and
 // blockops_plan.h for which kernel a call gets, with which grid: the launchers at the end of this file run what the plan says.
 #include <cstdlib>
 #include "blockops_block.h"
 #include "transcode5_block.h"
+#include "transcode_family_block.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
@@ -296,6 +297,34 @@ extern "C" __global__ void __launch_bounds__(kSearchLanes) icamd_transcode_dxt5_
   blocks[k] = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// DXT1 -> ETC2 RGB8, BC4 -> EAC R11, BC5 -> EAC RG11 in place (EXTENSIONS; transcode_family_block.h): one block
+// per lane, one 8- or 16-byte load and one store of the same size.  The DXT1 kernel has no search and keeps the four-wave
+// workgroups of the DXT1 -> ETC1 kernel; the two EAC kernels are the palette search of the DXT5 kernel (twice, back to back,
+// for BC5) and take its one-wave workgroups for the same reason.
+extern "C" __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_transcode_dxt1_to_etc2_rgb8_kernel(uint2 *blocks, uint32_t n) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k >= n) return;
+  const uint2 b = blocks[k];
+  const Out8 o = transcode_dxt1_block_to_etc2_rgb8(b.x, b.y);
+  blocks[k] = make_uint2(o.lo, o.hi);
+}
+extern "C" __global__ void __launch_bounds__(kSearchLanes) icamd_transcode_bc4_to_eac_r11_kernel(uint2 *blocks, uint32_t n) {
+  const uint32_t k = blockIdx.x * kSearchLanes + threadIdx.x;
+  if (k >= n) return;
+  const uint2 b = blocks[k];
+  const Out8 o = transcode_bc4_block_to_eac_r11(b.x, b.y);
+  blocks[k] = make_uint2(o.lo, o.hi);
+}
+extern "C" __global__ void __launch_bounds__(kSearchLanes) icamd_transcode_bc5_to_eac_rg11_kernel(uint4 *blocks, uint32_t n) {
+  const uint32_t k = blockIdx.x * kSearchLanes + threadIdx.x;
+  if (k >= n) return;
+  const uint4 b = blocks[k];
+  const uint32_t w[4] = { b.x, b.y, b.z, b.w };
+  uint32_t o[4];
+  transcode_bc5_block_to_eac_rg11(w, o);
+  blocks[k] = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 // ICAMD_PAD_BORDER_QUAD=0: one lane per pad block, the r04 form; read once.  Kept: the GPU tests run both forms through it.
 static bool pad_border_quad() {
   static const bool on = [] { const char *e = getenv("ICAMD_PAD_BORDER_QUAD"); return !(e && e[0] == '0'); }();
@@ -380,6 +409,28 @@ hipError_t launch_transcode_dxt5_to_etc2_rgba8(void *blocks, uint64_t n_blocks, 
     err = hipGetLastError();
   });
   return err;
+}
+
+// The launches blockops_plan.h cuts a buffer of n_blocks into (transcode_launch), each with its kernel's lanes per workgroup
+template <typename Block>
+static hipError_t launch_transcode_family(void (*kernel)(Block *, uint32_t), uint32_t lanes, void *blocks, uint64_t n_blocks,
+                                          hipStream_t stream) {
+  for (uint64_t i = 0; i < transcode_launches(n_blocks); ++i) {
+    const TranscodeLaunch l = transcode_launch(n_blocks, (uint32_t)sizeof(Block), lanes, i);
+    hipLaunchKernelGGL(kernel, dim3(l.grid_x), dim3(l.lanes), 0, stream, static_cast<Block *>(blocks) + l.first_block, l.blocks);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+hipError_t launch_transcode_dxt1_to_etc2_rgb8(void *blocks, uint64_t n_blocks, hipStream_t stream) {
+  return launch_transcode_family<uint2>(icamd_transcode_dxt1_to_etc2_rgb8_kernel, kThreadsPerWorkgroup, blocks, n_blocks, stream);
+}
+hipError_t launch_transcode_bc4_to_eac_r11(void *blocks, uint64_t n_blocks, hipStream_t stream) {
+  return launch_transcode_family<uint2>(icamd_transcode_bc4_to_eac_r11_kernel, kSearchLanes, blocks, n_blocks, stream);
+}
+hipError_t launch_transcode_bc5_to_eac_rg11(void *blocks, uint64_t n_blocks, hipStream_t stream) {
+  return launch_transcode_family<uint4>(icamd_transcode_bc5_to_eac_rg11_kernel, kSearchLanes, blocks, n_blocks, stream);
 }
 
 // ---- CreateSolidImage / CopySubimage on device-resident block grids (helper.h:522-592) ----

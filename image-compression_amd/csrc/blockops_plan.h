@@ -192,6 +192,22 @@ inline void for_chunks(uint64_t total, uint64_t limit, Launch launch) {
   for (uint64_t first = 0; first < total; first += limit) launch(first, total - first < limit ? total - first : limit);
 }
 
+// The in-place transcodes of the ETC2 family (DXT1 -> ETC2 RGB8, BC4 -> EAC R11, BC5 -> EAC RG11; transcode_family_block.h): a
+// buffer of n_bytes holds n_bytes / block_bytes whole blocks, the rest is left alone; a launch takes at most kTranscodeFamilyChunk
+// blocks, which its kernel indexes with 32 bits, one block per lane in workgroups of `lanes`.  Launch i of transcode_launches().
+constexpr uint64_t kTranscodeFamilyChunk = 1ull << 30;
+struct TranscodeLaunch {
+  uint64_t first_block, byte_offset;  // where the launch starts in the buffer
+  uint32_t blocks, grid_x, lanes;
+};
+inline uint64_t transcode_blocks(uint64_t n_bytes, uint32_t block_bytes) { return n_bytes / block_bytes; }
+inline uint64_t transcode_launches(uint64_t n_blocks) { return (n_blocks + kTranscodeFamilyChunk - 1) / kTranscodeFamilyChunk; }
+inline TranscodeLaunch transcode_launch(uint64_t n_blocks, uint32_t block_bytes, uint32_t lanes, uint64_t i) {
+  const uint64_t first = i * kTranscodeFamilyChunk, left = n_blocks - first;
+  const uint32_t blocks = (uint32_t)(left < kTranscodeFamilyChunk ? left : kTranscodeFamilyChunk);
+  return { first, first * block_bytes, blocks, (blocks + lanes - 1) / lanes, lanes };
+}
+
 // CopySubimage: grid = (column chunks of a block row, rows, images), rows and images in chunks of kGridLimitYZ
 inline uint32_t copy_subimage_grid_x(uint32_t cols) { return (cols + kBlockOpLanes - 1) / kBlockOpLanes; }
 // CreateSolid, one image: a grid-stride loop of at most kFillWorkgroups workgroups

@@ -1054,6 +1054,32 @@ int icamd_transcode_dxt5_to_etc2_rgba8_device(void *d_blocks, size_t n_bytes, vo
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 
+// EXTENSIONS (include/ic_amd.h): DXT1 -> ETC2 RGB8, BC4 -> EAC R11 (8-byte blocks), BC5 -> EAC RG11 (16-byte blocks) in place
+using TranscodeLauncher = hipError_t (*)(void *, uint64_t, hipStream_t);
+static int transcode_family_device(TranscodeLauncher launch, const char *what, size_t block, void *d_blocks, size_t n_bytes,
+                                   void *hip_stream) {
+  if (!d_blocks) return ICAMD_FALSE;
+  if (reinterpret_cast<uintptr_t>(d_blocks) % block)
+    return fail(ICAMD_ERR_ARG, block == 16 ? "block pointer must be 16-byte aligned" : "block pointer must be 8-byte aligned");
+  if (n_bytes < block) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  ICAMD_HIP(launch(d_blocks, n_bytes / block, static_cast<hipStream_t>(hip_stream)), what);
+  return ICAMD_OK;
+}
+int icamd_transcode_dxt1_to_etc2_rgb8_device(void *d_blocks, size_t n_bytes, void *hip_stream) try {
+  return transcode_family_device(icamd::launch_transcode_dxt1_to_etc2_rgb8, "launch transcode dxt1 -> etc2 rgb8", 8, d_blocks,
+                                 n_bytes, hip_stream);
+} ICAMD_ABI_CATCH
+int icamd_transcode_bc4_to_eac_r11_device(void *d_blocks, size_t n_bytes, void *hip_stream) try {
+  return transcode_family_device(icamd::launch_transcode_bc4_to_eac_r11, "launch transcode bc4 -> eac r11", 8, d_blocks, n_bytes,
+                                 hip_stream);
+} ICAMD_ABI_CATCH
+int icamd_transcode_bc5_to_eac_rg11_device(void *d_blocks, size_t n_bytes, void *hip_stream) try {
+  return transcode_family_device(icamd::launch_transcode_bc5_to_eac_rg11, "launch transcode bc5 -> eac rg11", 16, d_blocks,
+                                 n_bytes, hip_stream);
+} ICAMD_ABI_CATCH
+
 int icamd_pad(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, const uint8_t *blocks,
               uint32_t ph, uint32_t pw, uint8_t *out, size_t out_size) try {
   int codec;
@@ -1092,6 +1118,25 @@ int icamd_transcode_dxt5_to_etc2_rgba8(uint8_t *blocks, size_t n_bytes) try {
   return staged_blockop(tls_staging(), blocks, n_bytes, blocks, whole, whole, true, [&](void *din, void *, hipStream_t s) {
     return icamd_transcode_dxt5_to_etc2_rgba8_device(din, n_bytes, s);
   });
+} ICAMD_ABI_CATCH
+
+// the host forms of the ETC2-family transcodes: staged through the device like the two above
+using TranscodeDeviceFn = int (*)(void *, size_t, void *);
+static int transcode_family_host(TranscodeDeviceFn device_form, size_t block, uint8_t *blocks, size_t n_bytes) {
+  if (!blocks) return ICAMD_FALSE;
+  if (n_bytes < block) return ICAMD_OK;
+  const size_t whole = n_bytes - n_bytes % block;
+  return staged_blockop(tls_staging(), blocks, n_bytes, blocks, whole, whole, true,
+                        [&](void *din, void *, hipStream_t s) { return device_form(din, n_bytes, s); });
+}
+int icamd_transcode_dxt1_to_etc2_rgb8(uint8_t *blocks, size_t n_bytes) try {
+  return transcode_family_host(icamd_transcode_dxt1_to_etc2_rgb8_device, 8, blocks, n_bytes);
+} ICAMD_ABI_CATCH
+int icamd_transcode_bc4_to_eac_r11(uint8_t *blocks, size_t n_bytes) try {
+  return transcode_family_host(icamd_transcode_bc4_to_eac_r11_device, 8, blocks, n_bytes);
+} ICAMD_ABI_CATCH
+int icamd_transcode_bc5_to_eac_rg11(uint8_t *blocks, size_t n_bytes) try {
+  return transcode_family_host(icamd_transcode_bc5_to_eac_rg11_device, 16, blocks, n_bytes);
 } ICAMD_ABI_CATCH
 
 int icamd_compress_batch(int compressor, int etc_strategy, int format, uint32_t height, uint32_t width,

@@ -225,6 +225,9 @@ hipError_t launch_pad(BlockOpCall call, hipStream_t stream);
 hipError_t launch_downsample(BlockOpCall call, hipStream_t stream);
 hipError_t launch_transcode_dxt1_to_etc1(void *blocks, uint64_t n_blocks, hipStream_t stream);  // 8-byte blocks, in place
 hipError_t launch_transcode_dxt5_to_etc2_rgba8(void *blocks, uint64_t n_blocks, hipStream_t stream);  // 16-byte blocks, in place
+hipError_t launch_transcode_dxt1_to_etc2_rgb8(void *blocks, uint64_t n_blocks, hipStream_t stream);   // 8-byte blocks, in place
+hipError_t launch_transcode_bc4_to_eac_r11(void *blocks, uint64_t n_blocks, hipStream_t stream);      // 8-byte blocks, in place
+hipError_t launch_transcode_bc5_to_eac_rg11(void *blocks, uint64_t n_blocks, hipStream_t stream);     // 16-byte blocks, in place
 // CreateSolidImage: `words` (block_bytes / 4 of them) replicated n_blocks times.  CopySubimage: rows x cols blocks
 // starting at block (r0, c0) of a grid src_cols blocks wide.
 hipError_t launch_fill_blocks(void *dst, uint64_t n_blocks, int block_bytes, const uint32_t words[4], hipStream_t stream);

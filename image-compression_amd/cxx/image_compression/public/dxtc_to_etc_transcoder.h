@@ -15,6 +15,13 @@ void TranscodeDxt1ToEtc1(CompressedImage *image);
 // icamd_transcode_dxt5_to_etc2_rgba8 in ic_amd.h.  Data only: the metadata, format name included, is left untouched.
 void TranscodeDxt5ToEtc2Rgba8(CompressedImage *image);
 
+// EXTENSIONS: the other three textures of a desktop asset set, in place and data only like the one above.  DXT1 blocks become the
+// ETC2 RGB8 blocks (ETC1-compatible or planar, kHeuristic) of the pixels they decode to, BC4 blocks the EAC R11 blocks and BC5
+// blocks the EAC RG11 blocks of theirs; see icamd_transcode_dxt1_to_etc2_rgb8 / _bc4_to_eac_r11 / _bc5_to_eac_rg11 in ic_amd.h.
+void TranscodeDxt1ToEtc2Rgb8(CompressedImage *image);
+void TranscodeBc4ToEacR11(CompressedImage *image);
+void TranscodeBc5ToEacRg11(CompressedImage *image);
+
 }  // namespace image_codec_compression
 
 #endif  // IMAGE_COMPRESSION_PUBLIC_DXTC_TO_ETC_TRANSCODER

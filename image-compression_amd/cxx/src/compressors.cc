@@ -460,4 +460,17 @@ void TranscodeDxt5ToEtc2Rgba8(CompressedImage *image) {  // EXTENSION: in place,
                "icamd_transcode_dxt5_to_etc2_rgba8");
 }
 
+void TranscodeDxt1ToEtc2Rgb8(CompressedImage *image) {  // EXTENSION: in place, data only
+  ReportStatus(icamd_transcode_dxt1_to_etc2_rgb8(image->GetMutableData(), image->GetDataSize()),
+               "icamd_transcode_dxt1_to_etc2_rgb8");
+}
+
+void TranscodeBc4ToEacR11(CompressedImage *image) {  // EXTENSION: in place, data only
+  ReportStatus(icamd_transcode_bc4_to_eac_r11(image->GetMutableData(), image->GetDataSize()), "icamd_transcode_bc4_to_eac_r11");
+}
+
+void TranscodeBc5ToEacRg11(CompressedImage *image) {  // EXTENSION: in place, data only
+  ReportStatus(icamd_transcode_bc5_to_eac_rg11(image->GetMutableData(), image->GetDataSize()), "icamd_transcode_bc5_to_eac_rg11");
+}
+
 }  // namespace image_codec_compression

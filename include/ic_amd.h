@@ -302,7 +302,8 @@ int icamd_pvrtc2_decompress(uint32_t size, const uint8_t *blocks, size_t blocks_
  * Compressor::Pad (compressor.h:104-106; helper.h:393-477; pad functors dxtc.cc:594-696, etc.cc:645-698) for the
  * case that really pads: the source grid covers (compressed_height, compressed_width) pixels, the result
  * (padded_height, padded_width); out_size must be the result's data size.  Device pointers of the block-domain
- * operations (pad, downsample: 4-byte; DXT1 -> ETC1 transcode: 8-byte; DXT5 -> ETC2 RGBA8 transcode: 16-byte) must be aligned,
+ * operations (pad, downsample: 4-byte; DXT1 -> ETC1 transcode: 8-byte; DXT5 -> ETC2 RGBA8 transcode: 16-byte; the ETC2-family
+ * transcodes: their block size) must be aligned,
  * else ICAMD_ERR_ARG; the decoders accept
  * any pointer.  Returns ICAMD_FALSE for PVRTC and when a
  * padded dimension has fewer blocks than the source (the reference either just duplicates the image, which the caller
@@ -389,6 +390,33 @@ int icamd_transcode_dxt1_to_etc1(uint8_t *blocks, size_t n_bytes);
  * stream-ordered, does not synchronise and can be captured into a graph. */
 int icamd_transcode_dxt5_to_etc2_rgba8_device(void *d_blocks, size_t n_bytes, void *hip_stream);
 int icamd_transcode_dxt5_to_etc2_rgba8(uint8_t *blocks, size_t n_bytes);
+
+/* EXTENSIONS: the rest of a DXT / BC asset set to the ETC2 family in place, in the compressed domain.  Block
+ * sizes do not change: DXT1 and ETC2 RGB8 keep a block in 8 bytes, BC4 and EAC R11 in 8, BC5 and EAC RG11 in 16.
+ * DXT1 -> ETC2 RGB8 (ICAMD_ETC2_RGB8).  DEFINITION: every whole 8-byte block B of the buffer is replaced by exactly the 8 bytes that
+ *   icamd_encode_device(ICAMD_ETC2_RGB8, ICAMD_ETC_HEURISTIC, 3 components, swap_rb = 0, ...)
+ * writes for the 4 x 4 RGB888 image that icamd_decode_device(ICAMD_DXT1, swap_rb = 0) produces from B: with E the eight bytes
+ * icamd_transcode_dxt1_to_etc1 writes for B and P the least-squares planar word of the sixteen decoded texels (the fit, the
+ * quantisation and the ignored bits of ICAMD_ETC2_RGB8), the result is P where its squared error over 16 texels x 3 channels is
+ * strictly smaller than E's, else E byte for byte.  The three-colour mode (c0 <= c1, index 3 black) decodes as the DXT1 decoder
+ * decodes it.
+ * BC4 -> EAC R11 (ICAMD_EAC_R11).  DEFINITION: every whole 8-byte block becomes the 8 bytes
+ *   icamd_encode_device(ICAMD_EAC_R11, 1 component, ...)
+ * writes for the 4 x 4 R8 image icamd_decode_device(ICAMD_BC4) produces from it -- the palette search of the DXT5 transcoder
+ * above: lo and hi are the extremes of the palette entries some texel uses, the smallest (sse, table, multiplier, base) wins,
+ * every texel takes the smallest index at its minimum, multiplier 0 is never written.
+ * BC5 -> EAC RG11 (ICAMD_EAC_RG11).  DEFINITION: every whole 16-byte block becomes the BC4 -> EAC R11 result of its bytes 0..7
+ * followed by that of its bytes 8..15.
+ * No pixel is materialised.  With `block` = 8, 8, 16: NULL -> ICAMD_FALSE; a device pointer that is not block-aligned ->
+ * ICAMD_ERR_ARG; n_bytes < block -> ICAMD_OK, nothing touched; otherwise n_bytes / block blocks are transcoded and the trailing
+ * n_bytes % block bytes are left as they were.  The device forms are stream-ordered, do not synchronise, allocate nothing and can
+ * be captured on a single stream; the host forms stage through the device (no CPU fall-back: ICAMD_ERR_NO_DEVICE without one). */
+int icamd_transcode_dxt1_to_etc2_rgb8_device(void *d_blocks, size_t n_bytes, void *hip_stream);
+int icamd_transcode_dxt1_to_etc2_rgb8(uint8_t *blocks, size_t n_bytes);
+int icamd_transcode_bc4_to_eac_r11_device(void *d_blocks, size_t n_bytes, void *hip_stream);
+int icamd_transcode_bc4_to_eac_r11(uint8_t *blocks, size_t n_bytes);
+int icamd_transcode_bc5_to_eac_rg11_device(void *d_blocks, size_t n_bytes, void *hip_stream);
+int icamd_transcode_bc5_to_eac_rg11(uint8_t *blocks, size_t n_bytes);
 
 /* ---- multi-GPU from one process: a batch of independent images, host buffers ----
  * Image i is compressed exactly like icamd_compress(compressor, ..., buffers[i], outs[i], out_size) on device
