@@ -49,6 +49,11 @@ ETC2_RGB8 = 18
 # decoder is the 11-bit one.  Source channels as for BC4 / BC5.  encode_device / decode_device / measure_error_device /
 # containers only
 EAC_R11, EAC_RG11 = 19, 20
+# EXTENSION (include/ic_amd.h ICAMD_ETC2_RGB8A1): ETC2 RGB8 with punch-through alpha, 8 bytes per block, from RGBA8 sources: a texel
+# is transparent iff its alpha is < 128; opaque blocks as ETC2 RGB8 (without the individual mode), blocks with transparency by the
+# masked differential search.  Decodes to RGBA8 with alpha 0 or 255.  encode_device / decode_device /
+# measure_error_device / containers only
+ETC2_RGB8A1 = 21
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -218,7 +223,7 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     _assert_u8_cuda(blocks)
     # BC4 and EAC_R11 -> R8, BC5 and EAC_RG11 -> RG8
-    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, ETC2_RGB8A1: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

@@ -17,29 +17,12 @@
 
 namespace icamd {
 
-// locate_tile<false> for lane `tid` of the workgroup
-__device__ __forceinline__ TileCoord etc2_rgb8_tile(const GridParams &P, uint32_t tid) {
-  TileCoord t;
-  const uint32_t cols = 1u << P.log2_tile_cols, rows = 256u >> P.log2_tile_cols;
-  t.lx = tid & (cols - 1u);
-  t.ly = tid >> P.log2_tile_cols;
-  t.bcol0 = blockIdx.x * cols;
-  t.brow0 = (blockIdx.y + P.tile_row0) * rows;
-  t.bcol = t.bcol0 + t.lx;
-  t.brow = t.brow0 + t.ly;
-  t.img = blockIdx.z;
-  t.full = t.bcol0 + cols <= P.block_cols && t.brow0 + rows <= P.block_rows;
-  t.interior = (t.bcol0 + cols) * 4u <= P.width && (t.brow0 + rows) * 4u <= P.height;
-  t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
-  return t;
-}
-
 template <int COMPS, int STRATEGY>
 __device__ __forceinline__ void etc2_rgb8_encode_one(const GridParams &P) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: a scalar register
   Out8 c;
   {
-    const TileCoord t = etc2_rgb8_tile(P, threadIdx.x);
+    const TileCoord t = locate_tile_lane(P, threadIdx.x);
     if (!t.valid) return;
     uint32_t px[16];
     load_tile_block<COMPS>(P, t, px);
@@ -56,7 +39,7 @@ __device__ __forceinline__ void etc2_rgb8_encode_one(const GridParams &P) {
   // kSmallerError kernel spills 8 bytes at 128 VGPRs.
   asm volatile("" ::: "memory");
   const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  const TileCoord t = etc2_rgb8_tile(P, lane + 64u * wave);
+  const TileCoord t = locate_tile_lane(P, lane + 64u * wave);
   if (!t.valid) return;  // (the same lanes as above; the store below is bounded by THIS coordinate)
   uint32_t px[16];
   load_tile_block<COMPS>(P, t, px);

@@ -218,12 +218,13 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr,
   return false;
 }
 
-// Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 4,
+// Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 /
+// ETC2 RGB8A1 4,
 // BC4 and EAC R11 1..4, BC5 and EAC RG11 2..4.
 bool codec_accepts_components(int codec, int comps) {
   switch (codec) {
     case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: return comps == 3 || comps == 4;
-    case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: return comps == 4;
+    case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: case ICAMD_ETC2_RGB8A1: return comps == 4;
     case ICAMD_BC4: case ICAMD_EAC_R11: return comps >= 1 && comps <= 4;
     case ICAMD_BC5: case ICAMD_EAC_RG11: return comps >= 2 && comps <= 4;
   }
@@ -485,6 +486,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_ETC1: return icamd::etc1_kernel_name(src_components);
     case ICAMD_ETC2_RGBA8: return icamd::etc2_kernel_name(src_components);
     case ICAMD_ETC2_RGB8: return icamd::etc2_rgb8_kernel_name(src_components);
+    case ICAMD_ETC2_RGB8A1: return icamd::etc2_a1_kernel_name(src_components);
     case ICAMD_PVRTC2: return icamd::pvrtc2_kernel_name();
     case ICAMD_PVRTC4: return icamd::pvrtc4_kernel_name();
     case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
@@ -529,6 +531,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
   if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
   // EXTENSION (include/ic_amd.h ICAMD_ETC2_RGBA8): the alpha half needs the fourth byte; checked before any device work
   if (codec == ICAMD_ETC2_RGBA8 && src_components != 4) return fail(ICAMD_ERR_ARG, "ETC2 RGBA8 needs a 4-component source");
+  if (codec == ICAMD_ETC2_RGB8A1 && src_components != 4) return fail(ICAMD_ERR_ARG, "ETC2 RGB8A1 needs a 4-component source");
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
@@ -536,7 +539,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return pvrtc_encode_device_impl(codec, src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
                                     dst_image_stride_bytes, d_src, d_dst, stream, false);
-  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8)
+  if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
+      codec != ICAMD_ETC2_RGB8A1)
     return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!codec_accepts_components(codec, src_components)) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
   if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
@@ -549,6 +553,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     ICAMD_HIP(icamd::launch_etc2(P, stream), "launch etc2");
   else if (codec == ICAMD_ETC2_RGB8)
     ICAMD_HIP(icamd::launch_etc2_rgb8(src_components, P, stream), "launch etc2 rgb8");
+  else if (codec == ICAMD_ETC2_RGB8A1)
+    ICAMD_HIP(icamd::launch_etc2_a1(P, stream), "launch etc2 rgb8a1");
   else
     ICAMD_HIP(icamd::launch_dxt(codec, src_components, P, stream), "launch dxt");
   return ICAMD_OK;
@@ -760,6 +766,8 @@ static int decode_launch(int codec, int swap_rb, uint32_t height, uint32_t width
     ICAMD_HIP(icamd::launch_etc2_decode(P, stream), "launch etc2 decode");
   else if (codec == ICAMD_ETC2_RGB8)
     ICAMD_HIP(icamd::launch_etc2_rgb8_decode(P, stream), "launch etc2 rgb8 decode");
+  else if (codec == ICAMD_ETC2_RGB8A1)
+    ICAMD_HIP(icamd::launch_etc2_a1_decode(P, stream), "launch etc2 rgb8a1 decode");
   else
     ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
   return ICAMD_OK;
@@ -771,7 +779,7 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
   const bool plane = plane_codec(codec);  // (BC4 / BC5 and EAC R11 / RG11: R8 / RG8 rows)
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 &&
-      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && !plane)
+      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1 && !plane)
     return ICAMD_FALSE;
   if (plane && swap_rb) return fail(ICAMD_ERR_ARG, eac11_codec(codec) ? "EAC R11 / RG11 decode: swap_rb must be 0" : "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
@@ -807,7 +815,8 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     swap_rb = 0;
   }
   const uint32_t block_bytes = icamd::codec_block_bytes(codec);
-  const uint32_t row_stride = width * (codec == ICAMD_DXT5 || codec == ICAMD_ETC2_RGBA8 || pvrtc ? 4u : 3u) + padding_bytes_per_row;
+  const bool rgba_rows = codec == ICAMD_DXT5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8A1 || pvrtc;
+  const uint32_t row_stride = width * (rgba_rows ? 4u : 3u) + padding_bytes_per_row;
   const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
   const uint64_t kMaxBlocks = (1ull << 31) - 1;
   if (pvrtc && bpi > kMaxBlocks) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
@@ -1503,7 +1512,8 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
                           const uint8_t *const *level_data, const size_t *level_sizes, uint8_t *out, size_t out_size) try {
   using namespace icamd;
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
-  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8))
+  if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
+                             codec != ICAMD_ETC2_RGB8A1))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);
@@ -1545,7 +1555,7 @@ static int encode_mips(int codec, int etc_strategy, int src_components, int swap
   if (filter == ICAMD_MIP_FILTER_NORMAL && codec != ICAMD_BC5) return mip_check_filter(codec, src_components, filter);
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4)
     return fail(ICAMD_ERR_ARG, "PVRTC has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
-  if (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || eac11_codec(codec))  // (EAC R11 / RG11: of the ETC2 family)
+  if (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_ETC2_RGB8A1 || eac11_codec(codec))  // (EAC R11 / RG11: of the ETC2 family)
     return fail(ICAMD_ERR_ARG, "ETC2 has no fused mip chain: icamd_mip_pyramid_device, then icamd_encode_device per level");
   if (!mip_codec(codec)) return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;

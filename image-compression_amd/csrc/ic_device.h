@@ -347,6 +347,23 @@ template <bool WIDE, uint32_t WIDE_ROWS = 1>
 __device__ __forceinline__ TileCoord locate_tile(const GridParams &P) {
   return locate_tile<WIDE, WIDE_ROWS>(P, blockIdx.x);
 }
+// locate_tile<false> for lane `tid` of the workgroup: for kernels that derive the coordinate a second time from the hardware's
+// lane index instead of holding it in registers (etc2_rgb8_kernels.hip, etc2_a1_kernels.hip).
+__device__ __forceinline__ TileCoord locate_tile_lane(const GridParams &P, uint32_t tid) {
+  TileCoord t;
+  const uint32_t cols = 1u << P.log2_tile_cols, rows = 256u >> P.log2_tile_cols;
+  t.lx = tid & (cols - 1u);
+  t.ly = tid >> P.log2_tile_cols;
+  t.bcol0 = blockIdx.x * cols;
+  t.brow0 = (blockIdx.y + P.tile_row0) * rows;
+  t.bcol = t.bcol0 + t.lx;
+  t.brow = t.brow0 + t.ly;
+  t.img = blockIdx.z;
+  t.full = t.bcol0 + cols <= P.block_cols && t.brow0 + rows <= P.block_rows;
+  t.interior = (t.bcol0 + cols) * 4u <= P.width && (t.brow0 + rows) * 4u <= P.height;
+  t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
+  return t;
+}
 // The block's first source byte = uniform 64-bit base + 32-bit lane offset (<= 4 * 256 rows of stride).
 struct TileSrc {
   const uint8_t *base;  // workgroup-uniform

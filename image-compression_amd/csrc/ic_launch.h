@@ -91,6 +91,9 @@ const char *etc2_kernel_name(int comps);  // "" unless comps == 4
 // ETC2 RGB8 (extension, etc2_rgb8_kernels.hip): comps 3 or 4; P.etc_strategy picks the ETC1 candidate's kernel as for ETC1
 hipError_t launch_etc2_rgb8(int comps, const GridParams &P, hipStream_t stream);
 const char *etc2_rgb8_kernel_name(int comps);  // "" unless comps is 3 or 4
+// ETC2 RGB8A1 (extension, etc2_a1_kernels.hip): RGBA8 sources only; P.etc_strategy as for ETC1
+hipError_t launch_etc2_a1(const GridParams &P, hipStream_t stream);
+const char *etc2_a1_kernel_name(int comps);  // "" unless comps == 4
 
 // PVRTC1 2bpp: square power-of-two RGBA8 images, n_images of them.
 struct PvrtcParams {
@@ -132,6 +135,7 @@ struct DecodeParams {
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
 hipError_t launch_etc2_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGBA8 -> RGBA8 rows (etc2_kernels.hip)
 hipError_t launch_etc2_rgb8_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGB8 -> RGB888 rows (etc2_rgb8_kernels.hip)
+hipError_t launch_etc2_a1_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGB8A1 -> RGBA8 rows (etc2_a1_kernels.hip)
 
 // Quality metric (metric_kernels.hip): n_images block grids against their source pixels, one launch of fewer than 2^31
 // blocks.  block_rows x block_cols are the blocks that cover the IMAGE (blocks of a padded grid beyond it are never visited);

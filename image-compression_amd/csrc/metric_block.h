@@ -16,6 +16,7 @@
 
 #include "bc45_block.h"  // blockops_block.h (decode_block_rows), decode_block.h, dxt_block.h (packed 16-bit helpers)
 #include "eac11_block.h"  // decode_eac11
+#include "etc2_a1_block.h"  // decode_etc2_a1
 #include "etc2_block.h"  // decode_etc2_rgba8, decode_etc2_colour
 #include "ic_device.h"
 
@@ -155,6 +156,25 @@ ICAMD_DEV void metric_etc2_rgb8_block(const uint32_t *w, const uint8_t *img, uin
   }
   ICAMD_UNROLL
   for (int y = 0; y < 4; ++y) metric_row4<3>(&S[4 * y], &D[4 * y], a);
+}
+
+// ETC2 RGB8A1 block `w` (EXTENSION: one punch-through colour word in any mode, either opaque bit) against the RGBA8 source pixels,
+// four channels, with the decoder's own math (decode_etc2_a1, swap included: a transparent texel is (0, 0, 0, 0)); a pixel
+// outside the image compares with itself.  PRECONDITION row < h, col < wd.
+ICAMD_DEV void metric_etc2_a1_block(const uint32_t *w, bool swap, const uint8_t *img, uint32_t h, uint32_t wd, uint32_t stride,
+                                    uint32_t row, uint32_t col, bool wide_ok, MetricAcc &a) {
+  uint32_t S[16], D[16];
+  load_block<4>(img, h, wd, stride, row, col, S, wide_ok);
+  decode_etc2_a1(w[0], w[1], swap, D);
+  if (row + 4 > h || col + 4 > wd) {
+    ICAMD_UNROLL
+    for (int y = 0; y < 4; ++y)
+      ICAMD_UNROLL
+      for (int x = 0; x < 4; ++x)
+        if (row + (uint32_t)y >= h || col + (uint32_t)x >= wd) S[4 * y + x] = D[4 * y + x];
+  }
+  ICAMD_UNROLL
+  for (int y = 0; y < 4; ++y) metric_row4<4>(&S[4 * y], &D[4 * y], a);
 }
 
 // Channel `ch` of the COMPS-byte pixels of the block at (row, col), clamped to the image: r[y] byte x = pixel (x, y).

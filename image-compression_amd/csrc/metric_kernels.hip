@@ -123,6 +123,8 @@ __device__ __forceinline__ void metric_block_codec(const MetricParams &P, uint32
       metric_etc2_block(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u, wide_ok, acc);
     else if constexpr (CODEC == ICAMD_ETC2_RGB8)
       metric_etc2_rgb8_block<COMPS>(w, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u, wide_ok, acc);
+    else if constexpr (CODEC == ICAMD_ETC2_RGB8A1)
+      metric_etc2_a1_block(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u, wide_ok, acc);
     else if constexpr (CODEC == ICAMD_BC4 || CODEC == ICAMD_BC5)
       metric_bc45_block<COMPS, CODEC == ICAMD_BC5>(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u,
                                                    wide_ok, acc);
@@ -217,6 +219,7 @@ ICAMD_METRIC_KERNEL(icamd_metric_etc1_rgba8_kernel, ICAMD_ETC1, 4)
 ICAMD_METRIC_KERNEL(icamd_metric_etc2_rgba8_kernel, ICAMD_ETC2_RGBA8, 4)
 ICAMD_METRIC_KERNEL(icamd_metric_etc2_rgb8_rgb888_kernel, ICAMD_ETC2_RGB8, 3)
 ICAMD_METRIC_KERNEL(icamd_metric_etc2_rgb8_rgba8_kernel, ICAMD_ETC2_RGB8, 4)
+ICAMD_METRIC_KERNEL(icamd_metric_etc2_rgb8a1_kernel, ICAMD_ETC2_RGB8A1, 4)
 ICAMD_METRIC_KERNEL(icamd_metric_bc4_r8_kernel, ICAMD_BC4, 1)
 ICAMD_METRIC_KERNEL(icamd_metric_bc4_rg8_kernel, ICAMD_BC4, 2)
 ICAMD_METRIC_KERNEL(icamd_metric_bc4_rgb888_kernel, ICAMD_BC4, 3)
@@ -266,6 +269,7 @@ const MetricKernel kMetricKernels[] = {
   ICAMD_METRIC_ENTRY(ICAMD_ETC2_RGBA8, 4, icamd_metric_etc2_rgba8_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_ETC2_RGB8, 3, icamd_metric_etc2_rgb8_rgb888_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_ETC2_RGB8, 4, icamd_metric_etc2_rgb8_rgba8_kernel),
+  ICAMD_METRIC_ENTRY(ICAMD_ETC2_RGB8A1, 4, icamd_metric_etc2_rgb8a1_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_BC4, 1, icamd_metric_bc4_r8_kernel), ICAMD_METRIC_ENTRY(ICAMD_BC4, 2, icamd_metric_bc4_rg8_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_BC4, 3, icamd_metric_bc4_rgb888_kernel), ICAMD_METRIC_ENTRY(ICAMD_BC4, 4, icamd_metric_bc4_rgba8_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_BC5, 2, icamd_metric_bc5_rg8_kernel), ICAMD_METRIC_ENTRY(ICAMD_BC5, 3, icamd_metric_bc5_rgb888_kernel),

@@ -147,7 +147,57 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
         * (KTX 0x9270 / 0x9272, PKM 2.0 types 5 / 6, PVR 25 / 26; no DDS) only: no Compressor + format pair selects them, the mip
         * entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0. */
-       ICAMD_EAC_R11 = 19, ICAMD_EAC_RG11 = 20 };
+       ICAMD_EAC_R11 = 19, ICAMD_EAC_RG11 = 20,
+       /* EXTENSION: ETC2 RGB8 with punch-through alpha (COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2), 8 bytes per 4 x 4 block in the
+        * raster block order of ETC1.  PARITY UNPINNED (the reference has no such format) except where stated.
+        *   The word is big-endian; hi = bits 63..32, lo = bits 31..0.  The field positions are those of ICAMD_ETC2_RGB8
+        *       (csrc/etc2_colour_block.h), with bit 33 the OPAQUE bit Op instead of the diff bit.
+        *   Mode.  There is no individual mode.  For byte c (R, G, B = bytes 0, 1, 2) s_c = 5-bit base + sign-extended 3-bit
+        *       delta, whatever Op: s_R outside 0..31 selects T, else s_G outside H, else s_B outside planar, else differential.
+        *   Differential.  Bases, flip (bit 32), the two 3-bit table fields and the texel index k = bit(p) | bit(p + 16) << 1 of
+        *       lo, p = 4 x + y, as in ETC1.  Op = 1: texel = clamp(base + {+a, +b, -a, -b}[k]), alpha 255 -- exactly an ETC1
+        *       differential word.  Op = 0: the modifiers are {0, +b, -, -b}; k = 2 is a transparent texel, R = G = B = A = 0; every
+        *       other texel has alpha 255.  a, b = 2, 5, 9, 13, 18, 24, 33, 47 and 8, 17, 29, 42, 60, 80, 106, 183 by table.
+        *   T and H.  The paint colours of ICAMD_ETC2_RGB8; with Op = 0, k = 2 gives (0, 0, 0, 0) instead of paint 2.  The last bit
+        *       of the H distance index is derived as there.
+        *   Planar.  As ICAMD_ETC2_RGB8; alpha is 255 for every texel, whatever Op.
+        *   Known answers: 00 00 00 00 ff ff 00 00 decodes to sixteen (0, 0, 0, 0).  1c 00 00 f4 ff 00 f0 f0 is T with Op = 0,
+        *       C1 = (204, 0, 0), C2 = (0, 0, 255), d = 11: column x = 0 is (204, 0, 0, 255), x = 1 (11, 11, 255, 255), x = 2
+        *       (0, 0, 0, 0), x = 3 (0, 0, 244, 255); with byte 3 = f6 (Op = 1) column 2 is (0, 0, 255, 255).
+        *       60 90 c8 00 ff 00 00 00 gives (99, 148, 206, 255) in columns 0 and 1 and (0, 0, 0, 0) in columns 2 and 3.
+        *   Encode, a definition and not a heuristic.  src_components == 4 only (else ICAMD_ERR_ARG).  The sixteen
+        *       texels are the ones ICAMD_ETC2_RGBA8 is handed for the block (same edge replication and padded-grid fetch, bytes
+        *       0..2 as they lie in memory whatever swap_rb).  A texel is TRANSPARENT iff its byte 3 is < 128.
+        *       1. All 16 transparent: the word is 00 00 00 00 ff ff 00 00.
+        *       2. None transparent: E = the 8 bytes icamd_encode_device(ICAMD_ETC1, etc_strategy, ...) writes for the block
+        *          (PARITY PINNED through ETC1); C = E if E is differential (bit 33 set), else C = D(texels, no mask, Op = 1,
+        *          partition = E's flip bit); the block is the least-squares planar word of ICAMD_ETC2_RGB8 where its summed squared
+        *          error is STRICTLY smaller than C's, else C.  So wherever E is differential the block is byte for byte what
+        *          ICAMD_ETC2_RGB8 writes.
+        *       3. 1..15 transparent: the word is D(texels, mask, Op = 0, partitions by strategy): ICAMD_ETC_SPLIT_HORIZONTALLY flip
+        *          1 only, ICAMD_ETC_SPLIT_VERTICALLY flip 0 only, the other two both, the smaller error wins and a tie keeps
+        *          flip 0.  No planar candidate.
+        *       D, the masked differential search, on the ETC1 sub-blocks (flip 0: S0 = columns 0..1, S1 = columns 2..3; flip 1:
+        *       rows).  Per partition -- bases: n = the sub-block's opaque texels, per channel q5 = floor(sum over them / (8 n))
+        *       (n = 8: ETC1's sum >> 6); a sub-block with n = 0 takes the other's q5.  Delta, per channel: d = q5(S1) - q5(S0),
+        *       c = clamp(d, -4, 3), e = d - c, a' = q5(S0) + e / 2 (truncating toward zero), b' = a' + c; the word stores a' and c,
+        *       the decoded bases are v << 3 | v >> 2 (both lie between the two q5, so no channel overflows).  Tables and indices:
+        *       per sub-block and table t = 0..7 every opaque texel takes the allowed index (Op = 1: 0..3; Op = 0: 0, 1, 3) with
+        *       the smallest squared RGB distance to clamp(base + modifier), ties to the smallest index; transparent texels take
+        *       index 2 and add no error; the table is the t with the smallest error, ties to the smallest t (so n = 0: table 0).
+        *       The partition's error is the sum of its two sub-blocks'.
+        *       Example: every texel (100, 150, 200), alpha 255 for x < 2 and 0 for x >= 2: 60 90 c8 00 ff 00 00 00 for strategies
+        *       1, 2, 3 (q5 = 12, 18, 25, every opaque texel index 0 at error 41, the partitions tie at 328), 60 90 c8 01 ff 00 00 00
+        *       for strategy 0.  T and H are decoded, never written; a fully opaque block never gets Op = 0, and no block gets a
+        *       transparent texel it did not have.
+        * icamd_decode_device writes RGBA8 rows (swap_rb as for ICAMD_ETC2_RGBA8) and reads all four modes under both values of Op.
+        * icamd_measure_error_device takes src_components == 4 and compares all four decoded channels against the source, as
+        * ICAMD_ETC2_RGBA8 does -- so colour stored under a transparent texel counts against decoded 0, and a source alpha that is
+        * not 0 / 255 counts against 0 / 255.  Reachable through icamd_encode_device, icamd_encode_batch_sharded_device,
+        * icamd_decode_device, icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the
+        * container functions (KTX 0x9276 with GL_RGBA, PKM 2.0 type 4, PVR 24; no DDS) only: no Compressor + format pair selects
+        * it, the mip entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0. */
+       ICAMD_ETC2_RGB8A1 = 21 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -259,7 +309,8 @@ int icamd_compress_and_pad_device(int compressor, int etc_strategy, int format,
  * BC4 / BC5 (extension, see ICAMD_BC4): channels and argument rules at the codec enumeration; otherwise as DXT.
  * ETC2 RGBA8 (extension, see ICAMD_ETC2_RGBA8): src_components must be 4; otherwise as ETC1.
  * ETC2 RGB8 (extension, see ICAMD_ETC2_RGB8): src_components 3 or 4; as ETC1.
- * EAC R11 / RG11 (extension, see ICAMD_EAC_R11): channels and argument rules as BC4 / BC5; grids, strides and batches as ETC1. */
+ * EAC R11 / RG11 (extension, see ICAMD_EAC_R11): channels and argument rules as BC4 / BC5; grids, strides and batches as ETC1.
+ * ETC2 RGB8A1 (extension, see ICAMD_ETC2_RGB8A1): src_components must be 4; otherwise as ETC1. */
 int icamd_encode_device(int codec, int etc_strategy, int src_components, int swap_rb,
                         uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
                         uint32_t row_stride_bytes, uint32_t n_images,
@@ -279,7 +330,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
  * width*1 / width*2 bytes per row (R8 / RG8) plus the padding; swap_rb must be 0, else ICAMD_ERR_ARG.  ICAMD_ETC2_RGBA8 (extension)
  * writes width*4 bytes per row plus the padding, ICAMD_ETC2_RGB8 (extension) width*3 like ICAMD_ETC1 (and like it stores the
  * channels in their stored order whatever swap_rb); both decode all five ETC2 colour modes.  ICAMD_EAC_R11 / ICAMD_EAC_RG11
- * (extension) write R8 / RG8 rows under the BC4 / BC5 rules. */
+ * (extension) write R8 / RG8 rows under the BC4 / BC5 rules.  ICAMD_ETC2_RGB8A1 (extension) writes width*4 bytes per row plus the
+ * padding, alpha 0 or 255, swap_rb as for ICAMD_ETC2_RGBA8. */
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
                         uint32_t padding_bytes_per_row, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
@@ -487,7 +539,8 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
  * The reference ends at the raw block stream (compressed_image.h:52-66); it has no file-container code, so there is
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
  * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
- * PVRTC2, BC4, BC5, ETC2 RGBA8, ETC2 RGB8), PKM (ETC1 as "PKM 10" type 0, ETC2 RGB8 / RGBA8 as "PKM 20" type 1 / 3; one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
+ * PVRTC2, BC4, BC5, ETC2 RGBA8, ETC2 RGB8, ETC2 RGB8A1), PKM (ETC1 as "PKM 10" type 0, ETC2 RGB8 / RGBA8 / RGB8A1 as "PKM 20" type 1 / 3 / 4;
+ * one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
  * icamd_compress / icamd_downsample return for that size (PVRTC: square power-of-two levels of 8 x 8 and up only). */
 enum { ICAMD_CONTAINER_DDS = 0, ICAMD_CONTAINER_KTX = 1, ICAMD_CONTAINER_PKM = 2, ICAMD_CONTAINER_PVR = 3 };
@@ -619,6 +672,7 @@ const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
  *     DXT1, ETC1, ETC2 RGB8 bytes 0..2 of the source pixel   src_components 3 or 4 (alpha ignored, sse[3] = 0)
  *     DXT5, PVRTC2, PVRTC4  bytes 0..3                        src_components 4
  *     ETC2 RGBA8            bytes 0..3                        src_components 4
+ *     ETC2 RGB8A1           bytes 0..3 (see ICAMD_ETC2_RGB8A1)  src_components 4
  *     BC4                   k = 0 is R                        src_components 1..4  (R, G located by the rules at ICAMD_BC4:
  *     BC5                   k = 0, 1 are R, G                 src_components 2..4   R = byte 0, or byte 2 with swap_rb)
  *     EAC R11 / RG11        as BC4 / BC5                      src_components 1..4 / 2..4
