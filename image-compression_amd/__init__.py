@@ -44,6 +44,9 @@ ETC2_RGBA8 = 16
 # encoder's word or the least-squares planar word, whichever is strictly closer.  17 is unassigned and rejected.
 # encode_device / decode_device / measure_error_device / containers only
 ETC2_RGB8 = 18
+# etc2_modes of encode_device (include/ic_amd.h icamd_encode_etc2_device): DEFAULT = what icamd_encode_device writes; TH = then the
+# T / H pass, which replaces the blocks a T or H word renders strictly closer (ETC2_RGB8 only)
+ETC2_MODES_DEFAULT, ETC2_MODES_TH = 0, 1
 # EXTENSION (include/ic_amd.h ICAMD_EAC_R11): EAC R11 (one channel, 8 bytes per block) and EAC RG11 (two channels, 16 bytes per
 # block), the ETC2 family's BC4 / BC5; every word is what ETC2 RGBA8's alpha search writes for the channel, the
 # decoder is the 11-bit one.  Source channels as for BC4 / BC5.  encode_device / decode_device / measure_error_device /
@@ -111,6 +114,12 @@ def kernel_name(codec, src_components):
     return lib().icamd_kernel_name(codec, src_components).decode()
 
 
+def etc2_kernel_name(codec, src_components, etc2_modes):
+    """icamd_etc2_kernel_name: the kernel of the T / H pass (etc2_modes = ETC2_MODES_TH), "" where there is none; with
+    ETC2_MODES_DEFAULT what kernel_name answers."""
+    return lib().icamd_etc2_kernel_name(codec, src_components, etc2_modes).decode()
+
+
 def _stream_handle(stream=None):
     s = torch.cuda.current_stream() if stream is None else stream
     return ctypes.c_void_p(s.cuda_stream)
@@ -151,9 +160,10 @@ def _compress_out_size(compressor, fmt, height, width, padded, out_size):
 
 def encode_device(codec, src, height, width, src_components, *, swap_rb=False, etc_strategy=ETC_SMALLER_ERROR,
                   grid_height=None, grid_width=None, row_stride_bytes=None, n_images=1,
-                  src_image_stride_bytes=None, out=None, stream=None):
+                  src_image_stride_bytes=None, out=None, stream=None, etc2_modes=0):
     """Launch the encode kernel on `src` (a torch.uint8 CUDA tensor, any shape, contiguous bytes).
     Returns the output tensor [n_images, encoded_size] (device).  No synchronisation.
+    etc2_modes = ETC2_MODES_TH (ETC2_RGB8 only): icamd_encode_etc2_device, the encode followed by the T / H pass.
     BC4 and EAC_R11 read R from 1..4-byte pixels, BC5 and EAC_RG11 read R and G from 2..4-byte pixels: R = byte 0 (byte 2 with
     swap_rb, which needs 3 or 4 bytes per pixel), G = byte 1."""
     _assert_u8_cuda(src)
@@ -164,6 +174,10 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
     per = encoded_size(codec, gh, gw)
     if out is None:
         out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    if etc2_modes != ETC2_MODES_DEFAULT:
+        st = lib().icamd_encode_etc2_device(codec, etc_strategy, etc2_modes, src_components, int(swap_rb), height, width, gh, gw,
+                                            stride, n_images, img_stride, per, _ptr(src), _ptr(out), _stream_handle(stream))
+        return out if _check(st, "icamd_encode_etc2_device") else None
     st = lib().icamd_encode_device(codec, etc_strategy, src_components, int(swap_rb), height, width, gh, gw, stride,
                                    n_images, img_stride, per, _ptr(src), _ptr(out), _stream_handle(stream))
     if not _check(st, "icamd_encode_device"):

@@ -25,6 +25,8 @@ PROTOTYPES = (
     ("icamd_compress_device", i, [i, i, i, u, u, u, p, p, z, p]),
     ("icamd_compress_and_pad_device", i, [i, i, i, u, u, u, u, u, p, p, z, p]),
     ("icamd_encode_device", i, [i, i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_encode_etc2_device", i, [i, i, i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_etc2_kernel_name", s, [i, i, i]),
     ("icamd_decode_device", i, [i, i, u, u, u, u, z, z, p, p, p]),
     ("icamd_decompress", i, [i, i, u, u, u, p, z, p, z]),
     ("icamd_pvrtc2_decompress", i, [u, p, z, p, z]),

@@ -560,6 +560,36 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
 
+// EXTENSION (include/ic_amd.h ICAMD_ETC2_MODES_TH): every argument is checked before any device work; modes 0 IS
+// icamd_encode_device, modes 1 its launch followed on the same stream by the T / H pass over the same grid
+int icamd_encode_etc2_device(int codec, int etc_strategy, int etc2_modes, int src_components, int swap_rb,
+                             uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
+                             uint32_t row_stride_bytes, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (codec != ICAMD_ETC2_RGB8) return fail(ICAMD_ERR_ARG, "icamd_encode_etc2_device encodes ICAMD_ETC2_RGB8 only");
+  if (etc2_modes != ICAMD_ETC2_MODES_DEFAULT && etc2_modes != ICAMD_ETC2_MODES_TH)
+    return fail(ICAMD_ERR_ARG, "etc2_modes must be ICAMD_ETC2_MODES_DEFAULT or ICAMD_ETC2_MODES_TH");
+  if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
+  if (n_images == 0) return ICAMD_OK;  // (before the stride, as in icamd_encode_device)
+  if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  const int rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, grid_height, grid_width,
+                                     row_stride_bytes, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst,
+                                     hip_stream);
+  if (rc != ICAMD_OK || etc2_modes == ICAMD_ETC2_MODES_DEFAULT) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, swap_rb, (uint32_t)etc_strategy);
+  ICAMD_HIP(icamd::launch_etc2_th(src_components, P, static_cast<hipStream_t>(hip_stream)), "launch etc2 t/h");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes) {
+  if (etc2_modes == ICAMD_ETC2_MODES_DEFAULT) return icamd_kernel_name(codec, src_components);
+  if (etc2_modes == ICAMD_ETC2_MODES_TH && codec == ICAMD_ETC2_RGB8) return icamd::etc2_th_kernel_name(src_components);
+  return "";
+}
+
 int icamd_pvrtc2_encode_region_device(uint32_t size, uint32_t first_block, uint32_t n_blocks, const void *d_src,
                                       void *d_dst_region, void *hip_stream) try {
   if (!d_src || !d_dst_region || n_blocks == 0) return ICAMD_FALSE;

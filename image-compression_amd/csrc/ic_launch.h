@@ -91,6 +91,10 @@ const char *etc2_kernel_name(int comps);  // "" unless comps == 4
 // ETC2 RGB8 (extension, etc2_rgb8_kernels.hip): comps 3 or 4; P.etc_strategy picks the ETC1 candidate's kernel as for ETC1
 hipError_t launch_etc2_rgb8(int comps, const GridParams &P, hipStream_t stream);
 const char *etc2_rgb8_kernel_name(int comps);  // "" unless comps is 3 or 4
+// The T / H pass of ETC2 RGB8 (extension, etc2_th_kernels.hip; icamd_encode_etc2_device with ICAMD_ETC2_MODES_TH): runs on the
+// stream AFTER launch_etc2_rgb8 with the same P and replaces the blocks a T or H word renders strictly closer
+hipError_t launch_etc2_th(int comps, const GridParams &P, hipStream_t stream);
+const char *etc2_th_kernel_name(int comps);  // "" unless comps is 3 or 4
 // ETC2 RGB8A1 (extension, etc2_a1_kernels.hip): RGBA8 sources only; P.etc_strategy as for ETC1
 hipError_t launch_etc2_a1(const GridParams &P, hipStream_t stream);
 const char *etc2_a1_kernel_name(int comps);  // "" unless comps == 4

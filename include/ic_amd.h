@@ -114,6 +114,31 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         *       47..45 = 111 and bit 42 = 0 where b + t >= 4, else 000 and 1).
         *       The block is P if its squared error summed over the 16 texels and 3 channels is STRICTLY smaller than E's, else E
         *       byte for byte.  So the summed error never exceeds ETC1's, block by block.  T and H are decoded, never written.
+        *   Encode with T and H, opt-in: icamd_encode_etc2_device(..., ICAMD_ETC2_MODES_TH, ...), a definition and not a heuristic
+        *       (DESIGN.md 3.17).  icamd_encode_device itself writes what is stated above, for every etc_strategy.  With v_p the
+        *       sixteen texels above (index p = 4 x + y), W the 8 bytes icamd_encode_device(ICAMD_ETC2_RGB8, etc_strategy, ...)
+        *       writes for the block and err(W) its squared error summed over the 16 texels and 3 channels:
+        *       Partitions of the texels into clusters A and B, two, tried in this order; one with A or B empty is dropped.
+        *           L (luminance): Y_p = R + 2 G + B; p is in B iff 16 Y_p > Sum Y.
+        *           C (widest channel): c* = the channel with the largest max - min over the block, ties to R before G before
+        *           B; p is in B iff 2 v_p[c*] > max + min of that channel.
+        *       Cluster colours: per cluster (n texels, channel sum S) and channel the 4-bit code q = (30 S + 255 n) / (510 n),
+        *           truncating; the colour is 17 q.  a is A's colour, b is B's.  A partition whose two 12-bit codes are equal is
+        *           dropped.
+        *       Candidates of a partition, in this order, each with the distance index di = 0..7 ascending: T(C1 = a, C2 = b),
+        *           T(C1 = b, C2 = a), H(a, b).  The paint colours are the decoder's (T: C1, clamp(C2 + d), C2, clamp(C2 - d); H:
+        *           clamp(a +- d), clamp(b +- d)); the colours are not refined.  Every texel takes the paint with the smallest
+        *           squared RGB distance, ties to the smallest paint index; the candidate's error is the sum over the texels.
+        *       Choice: the best candidate has the smallest error, ties to the earliest in the order (partition L before C, then
+        *           the candidate order, then di).  The block is the best candidate's word if its error is STRICTLY smaller than
+        *           err(W), else W byte for byte; a block with no surviving partition is W.  So the summed error never exceeds
+        *           icamd_encode_device's, block by block.
+        *       Packing (fields: csrc/etc2_colour_block.h; bit 33 set).  T: di = bits 35-34 : 32; with a = R1 >> 2 and b = R1 & 3,
+        *           bits 63-61 = 111 and bit 58 = 0 where a + b >= 4, else 000 and 1, so byte 0 overflows.  H: bit 34 = di >> 2,
+        *           bit 32 = (di >> 1) & 1, and where (C1 >= C2 as R << 16 | G << 8 | B) != (di & 1) for (C1, C2) = (a, b) the
+        *           colours are stored swapped and every texel's index flipped by k ^= 2; bit 63 = G1 bit 3, so byte 0 does not
+        *           overflow; with a' = (G1 & 1) << 1 | B1 >> 3 and b' = (B1 >> 1) & 3, bits 55-53 = 111 and bit 50 = 0 where
+        *           a' + b' >= 4, else 000 and 1, so byte 1 overflows.
         * icamd_encode_device takes src_components 3 or 4 and honours etc_strategy, grids, strides and batches as for ETC1.
         * icamd_decode_device writes RGB888 rows and, like ICAMD_ETC1, stores the word's channels in their stored order whatever
         * swap_rb.  icamd_measure_error_device compares three channels, sources of 3 or 4 components.  Reachable through
@@ -316,6 +341,26 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
                         uint32_t row_stride_bytes, uint32_t n_images,
                         size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                         const void *d_src, void *d_dst, void *hip_stream);
+
+/* EXTENSION: the ETC2 family's encoder with a choice of colour modes.  codec must be ICAMD_ETC2_RGB8 (ETC2 RGBA8's colour half and
+ * ETC2 RGB8A1 are not covered: ICAMD_ERR_ARG, like every other codec) and etc2_modes one of the two values below, else
+ * ICAMD_ERR_ARG.  Every other argument means what it means to icamd_encode_device and is checked before any device work: a
+ * null pointer or a zero height / width returns ICAMD_FALSE; then a codec, etc2_modes or src_components outside the above
+ * ICAMD_ERR_ARG; then n_images == 0 ICAMD_OK; then a row stride shorter than a row ICAMD_ERR_ARG -- the order of
+ * icamd_encode_device, so an empty batch with a short stride is ICAMD_OK in both.
+ *   ICAMD_ETC2_MODES_DEFAULT  the call IS icamd_encode_device: the same kernels, byte for byte.
+ *   ICAMD_ETC2_MODES_TH       after those kernels, a second launch on the same stream replaces every block for which the T / H
+ *                             search defined at ICAMD_ETC2_RGB8 finds a strictly closer word; all other bytes stay as they are.
+ * icamd_etc2_kernel_name names the kernel of that second launch ("" for combinations that have none); with
+ * ICAMD_ETC2_MODES_DEFAULT it answers what icamd_kernel_name answers. */
+enum { ICAMD_ETC2_MODES_DEFAULT = 0,   /* what icamd_encode_device writes */
+       ICAMD_ETC2_MODES_TH = 1 };      /* + the T and H candidates */
+int icamd_encode_etc2_device(int codec, int etc_strategy, int etc2_modes, int src_components, int swap_rb,
+                             uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
+                             uint32_t row_stride_bytes, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, void *hip_stream);
+const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes);
 
 /* ---- "next" row 8f.1: block decoders on device (Compressor::Decompress, compressor.h:85-86;
  * helper.h:218-262, dxtc.cc:167-267, etc.cc:198-289).  Writes height rows of
