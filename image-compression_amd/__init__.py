@@ -789,6 +789,67 @@ def mip_kernel_name(codec, src_components, mip_filter=0):
     return lib().icamd_mip_kernel_name(codec, src_components, mip_filter).decode()
 
 
+# ---- mip chains of the ETC2 family (EXTENSION, include/ic_amd.h): the pixel pyramid, then every level in one encode launch ----
+def etc2_mip_chain_size(codec, height, width, levels=None):
+    """mip_chain_size for ETC2_RGBA8 / ETC2_RGB8 / ETC2_RGB8A1 / EAC_R11 / EAC_RG11: (bytes of one image's chain, [offset of
+    level l for l in 0..levels]); (0, None) where the codec / size / level count is refused."""
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    offs = (ctypes.c_size_t * (max(levels, 0) + 1))()
+    n = lib().icamd_etc2_mip_chain_size(codec, height, width, levels, offs)
+    return (n, list(offs)) if n else (0, None)
+
+
+def etc2_mip_workspace_size(codec, src_components, height, width, levels=None, n_images=1):
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    return lib().icamd_etc2_mip_workspace_size(codec, src_components, height, width, levels, n_images)
+
+
+def encode_etc2_mips_device(codec, src, height, width, src_components, *, levels=None, swap_rb=False,
+                            etc_strategy=ETC_SMALLER_ERROR, etc2_modes=0, mip_filter=0, n_images=1, row_stride_bytes=None,
+                            src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, workspace=None, stream=None):
+    """Mip-chain encode of the ETC2 family (icamd_encode_etc2_mips_device) of `src` (a torch.uint8 CUDA tensor, contiguous
+    bytes): etc2_modes as encode_etc2_device (ETC2_MODES_TH with ETC2_RGB8 only), mip_filter as encode_mips_device
+    (MIP_FILTER_NORMAL for EAC_RG11 from two-byte pixels).  Returns (flat, views) as encode_mips_device does: flat is
+    [n_images, dst_image_stride] (device), views[l] the blocks of level l.  The workspace is allocated here unless the caller
+    passes one (a uint8 CUDA tensor of at least etc2_mip_workspace_size bytes).  No synchronisation."""
+    _assert_u8_cuda(src)
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    total, offs = etc2_mip_chain_size(codec, height, width, levels)
+    per = total if dst_image_stride_bytes is None else dst_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
+    _check_out(out, n_images, per, "encode_etc2_mips_device")
+    ws_bytes = etc2_mip_workspace_size(codec, src_components, height, width, levels, n_images) if total else 0
+    if workspace is None and ws_bytes:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=src.device)
+    if workspace is not None and not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("encode_etc2_mips_device: workspace must be a contiguous uint8 CUDA tensor")
+    ws_ptr = _ptr(workspace) if workspace is not None else None
+    ws_len = workspace.numel() if workspace is not None else 0
+    st = lib().icamd_encode_etc2_mips_device(codec, etc_strategy, etc2_modes, src_components, int(swap_rb), mip_filter, height,
+                                             width, stride, levels, n_images, img_stride, per, _ptr(src), _ptr(out), ws_ptr,
+                                             ws_len, _stream_handle(stream))
+    if not _check(st, "icamd_encode_etc2_mips_device") or offs is None:
+        return None
+    return out, [out[:, offs[l]:offs[l + 1]] for l in range(levels)]
+
+
+def etc2_mip_kernel_name(codec, src_components, etc_strategy=ETC_SMALLER_ERROR, etc2_modes=0):
+    """Name of the kernel of the chain's encode launch -- with ETC2_MODES_TH of its T / H launch -- ("" if refused)."""
+    return lib().icamd_etc2_mip_kernel_name(codec, src_components, etc_strategy, etc2_modes).decode()
+
+
+def etc2_mip_tune(level_order=1):
+    """Measurement knob: 1 = the largest level's workgroups first in the encode launch (default), 0 = the smallest's.  Time
+    only, never bytes."""
+    _require_ok(lib().icamd_etc2_mip_tune(level_order), "icamd_etc2_mip_tune")
+
+
 # ---- quality metric (icamd_measure_error_device): compressed blocks against their source pixels
 
 ERROR_STATS_BYTES = 48  # sizeof(icamd_error_stats): uint64 sse[4], uint32 max_abs[4]

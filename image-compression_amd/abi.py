@@ -71,6 +71,11 @@ PROTOTYPES = (
     ("icamd_mip_pyramid_filtered_device", i, [i, i, u, u, u, u, u, z, z, p, p, p]),
     ("icamd_compress_mips_filtered", i, [i, i, i, i, u, u, u, u, p, p, z]),
     ("icamd_mip_kernel_name", s, [i, i, i]),
+    ("icamd_etc2_mip_chain_size", z, [i, u, u, u, p]),
+    ("icamd_etc2_mip_workspace_size", z, [i, i, u, u, u, u]),
+    ("icamd_encode_etc2_mips_device", i, [i, i, i, i, i, i, u, u, u, u, u, z, z, p, p, p, z, p]),
+    ("icamd_etc2_mip_kernel_name", s, [i, i, i, i]),
+    ("icamd_etc2_mip_tune", i, [i]),
     ("icamd_measure_error_device", i, [i, i, i, u, u, u, u, u, u, z, z, p, p, p, p]),
     ("icamd_measure_error", i, [i, i, u, u, u, p, p, z, p]),
     ("icamd_metric_kernel_name", s, [i, i]),

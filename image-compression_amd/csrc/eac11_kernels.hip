@@ -10,67 +10,13 @@
 // RG11 runs both searches in ONE lane, R then G (G's sixteen bytes wait in four registers), and stores 16 bytes once: the
 // source is read once, and every vote of a search's wave-uniform exit is taken among lanes that search the same channel.
 // Decode: the lane-group decoder of lane_groups.h (K = 4 / 2 blocks per lane, 16-byte row stores), as BC4 / BC5.
-#include "eac11_block.h"
-#include "metric_block.h"  // metric_gather_channel: the clamp-to-edge gather of one channel
+#include "etc2_encode_bodies.inc"  // eac11_encode_one: the encode body, shared with the chain kernels of etc2_mip_kernels.hip
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "lane_groups.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-struct __attribute__((packed, aligned(1))) EacU1 { uint32_t x; };
-
-// r[y] byte x = R of texel (x, y) of the lane's block, g likewise (RG only): R = byte 0, or byte 2 of a swapped 3- / 4-byte
-// source; G = byte 1.  Texels outside the image replicate its last row / column, also on a padded grid.
-template <int COMPS, bool RG>
-__device__ __forceinline__ void eac11_fetch(const GridParams &P, const TileCoord &t, uint32_t r[4], uint32_t g[4]) {
-  if constexpr (COMPS >= 3) {
-    uint32_t px[16];
-    load_tile_block<COMPS>(P, t, px);
-    const uint32_t lo = P.swap_rb ? 0x0c0c0602u : 0x0c0c0400u, hi = P.swap_rb ? 0x06020c0cu : 0x04000c0cu;
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      r[y] = perm(px[4 * y + 1], px[4 * y], lo) | perm(px[4 * y + 3], px[4 * y + 2], hi);
-      if (RG) g[y] = perm(px[4 * y + 1], px[4 * y], 0x0c0c0501u) | perm(px[4 * y + 3], px[4 * y + 2], 0x05010c0cu);
-    }
-  } else {
-    const uint8_t *img = P.src + (uint64_t)t.img * P.src_image_stride;
-    const uint32_t row = t.brow * 4u, col = t.bcol * 4u;
-    if ((uint64_t)row + 4u <= P.height && (uint64_t)col + 4u <= P.width) {
-      const uint8_t *p = img + (uint64_t)row * P.row_stride + (uint64_t)col * COMPS;
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        const uint8_t *line = p + (uint64_t)y * P.row_stride;
-        if (COMPS == 1) {
-          r[y] = reinterpret_cast<const EacU1 *>(line)->x;
-        } else {
-          const U2 v = load_stream(reinterpret_cast<const U2 *>(line));
-          r[y] = rg_row_r(v.x, v.y);
-          if (RG) g[y] = rg_row_g(v.x, v.y);
-        }
-      }
-    } else {
-      metric_gather_channel<COMPS>(img, P.height, P.width, P.row_stride, row, col, 0u, r);
-      if (RG) metric_gather_channel<COMPS>(img, P.height, P.width, P.row_stride, row, col, 1u, g);
-    }
-  }
-}
-
-template <int COMPS, bool RG>
-__device__ __forceinline__ void eac11_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<false>(P);
-  if (!t.valid) return;
-  uint32_t r[4], g[4] = { 0u, 0u, 0u, 0u };
-  eac11_fetch<COMPS, RG>(P, t, r, g);
-  const Out8 a = encode_eac11_rows(r);
-  if (RG) {
-    const Out8 b = encode_eac11_rows(g);
-    store_stream16(tile_dst<16>(P, t), a.lo, a.hi, b.lo, b.hi);
-  } else {
-    store_stream8(tile_dst<8>(P, t), a.lo, a.hi);
-  }
-}
 
 struct Eac11Rows {
   __device__ __forceinline__ void operator()(uint32_t w0, uint32_t w1, uint32_t rows[4]) const { decode_eac11(w0, w1, rows); }
@@ -79,7 +25,7 @@ struct Eac11Rows {
 extern "C" {
 
 #define ICAMD_EAC11_KERNEL(name, comps, rg) \
-  __global__ void __launch_bounds__(kThreadsPerWorkgroup) name(GridParams P) { eac11_encode_one<comps, rg>(P); }
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) name(GridParams P) { eac11_encode_one<comps, rg>(P, tile_of_launch(P)); }
 ICAMD_EAC11_KERNEL(icamd_eac_r11_r8_kernel, 1, false)
 ICAMD_EAC11_KERNEL(icamd_eac_r11_rg8_kernel, 2, false)
 ICAMD_EAC11_KERNEL(icamd_eac_r11_rgb888_kernel, 3, false)

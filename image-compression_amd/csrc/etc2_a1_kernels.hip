@@ -8,49 +8,12 @@
 // it, then the planar candidate on the opaque lanes.  Every skip is a wave vote in which only the lanes that use the result
 // take part; lanes outside the block grid have left before the first one.  The block leaves as one 8-byte store.
 // Decode: one block per lane, an 8-byte block load and four 16-byte row stores (RGBA8), clipped at the image's edge.
-#include "etc1_block.h"
-#include "etc2_a1_block.h"
+#include "etc2_encode_bodies.inc"  // etc2_a1_encode_one: the encode body, shared with the chain kernels of etc2_mip_kernels.hip
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-template <int STRATEGY>
-__device__ __forceinline__ void etc2_a1_encode_one(const GridParams &P) {
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: a scalar register
-  Out8 c = { 0u, 0u };
-  {
-    const TileCoord t = locate_tile_lane(P, threadIdx.x);
-    if (!t.valid) return;
-    uint32_t px[16];
-    load_tile_block<4>(P, t, px);
-    uint32_t all = px[0];
-    ICAMD_UNROLL
-    for (int p = 1; p < 16; ++p) all &= px[p];
-    const bool opaque = (all >> 31) != 0u;  // every byte 3 >= 128
-    if (!wave_all(!opaque)) {
-      if (opaque) {
-        if (STRATEGY == 3) {
-          c = encode_etc1_block<false>(px, 3u);
-        } else {
-          const uint32_t spread = etc1_block_spread(px);
-          c = etc1_encode_classified<STRATEGY>(px, etc1_constant_block(px, spread), spread >= ICAMD_ETC1_BUSY_SPREAD);
-        }
-      }
-    }
-  }
-  // Phase two holds only the ETC1 word across the search, as the ETC2 RGB8 kernels do: lane and wave index come from the
-  // hardware, the coordinates are derived again and the texels read again.
-  asm volatile("" ::: "memory");
-  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  const TileCoord t = locate_tile_lane(P, lane + 64u * wave);
-  if (!t.valid) return;  // (the same lanes as above; the store below is bounded by THIS coordinate)
-  uint32_t px[16];
-  load_tile_block<4>(P, t, px);
-  const Out8 o = etc2_a1_block<STRATEGY>(px, c);
-  store_stream8(tile_dst<8>(P, t), o.lo, o.hi);
-}
 
 __device__ __forceinline__ void etc2_a1_decode_one(const DecodeParams &P, uint32_t k) {
   const uint32_t img = fastdiv(k, P.div_bpi);
@@ -84,7 +47,7 @@ extern "C" {
 // (amdgpu_waves_per_eu(4): as the ETC1 kernels -- the colour search must fit 128 VGPRs)
 #define ICAMD_ETC2_A1_KERNEL(name, strategy)                                                                           \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) __attribute__((amdgpu_waves_per_eu(4))) name(GridParams P) { \
-    etc2_a1_encode_one<strategy>(P);                                                                                   \
+    etc2_a1_encode_one<strategy>(P, tile_of_launch(P));                                                                                   \
   }
 ICAMD_ETC2_A1_KERNEL(icamd_etc2_rgb8a1_kernel, 2)            // kSmallerError (the reference's default)
 ICAMD_ETC2_A1_KERNEL(icamd_etc2_rgb8a1_split_h_kernel, 0)    // kSplitHorizontally

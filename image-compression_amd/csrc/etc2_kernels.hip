@@ -10,37 +10,12 @@
 // SIMD -- it compiles to 132 VGPRs and no scratch; the alpha search, which is most of the time, needs few registers and no
 // memory, so three waves keep the SIMD issuing.  Both halves leave as one 16-byte store.
 // Decode: one block per lane, a 16-byte block load and four 16-byte row stores (RGBA8), clipped at the image's edge.
-#include "etc1_block.h"
-#include "etc2_block.h"
+#include "etc2_encode_bodies.inc"  // etc2_encode_one: the encode body, shared with the chain kernels of etc2_mip_kernels.hip
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-template <int STRATEGY>
-__device__ __forceinline__ void etc2_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<false>(P);
-  if (!t.valid) return;
-  uint32_t px[16];
-  load_tile_block<4>(P, t, px);
-  uint32_t al[4];  // row y's four alpha bytes, byte x = texel (x, y)
-#pragma unroll
-  for (int y = 0; y < 4; ++y)
-    al[y] = perm(px[4 * y + 1], px[4 * y], 0x0c0c0703u) | perm(px[4 * y + 3], px[4 * y + 2], 0x07030c0cu);
-  Out8 c;
-  if (STRATEGY == 3) {
-    c = encode_etc1_block<false>(px, 3u);
-  } else {
-    const uint32_t spread = etc1_block_spread(px);
-    c = etc1_encode_classified<STRATEGY>(px, etc1_constant_block(px, spread), spread >= ICAMD_ETC1_BUSY_SPREAD);
-  }
-  uint32_t a[16];
-#pragma unroll
-  for (int p = 0; p < 16; ++p) a[p] = bfe(al[p >> 2], 8 * (p & 3), 8);
-  const Out8 e = encode_eac_alpha(a);
-  store_stream16(tile_dst<16>(P, t), e.lo, e.hi, c.lo, c.hi);
-}
 
 __device__ __forceinline__ void etc2_decode_one(const DecodeParams &P, uint32_t k) {
   const uint32_t img = fastdiv(k, P.div_bpi);
@@ -75,7 +50,7 @@ extern "C" {
 // (amdgpu_waves_per_eu(4): as the ETC1 kernels -- the colour search must fit 128 VGPRs; kSmallerError: 3 or 4, see above)
 #define ICAMD_ETC2_KERNEL(name, strategy)                                                                              \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) __attribute__((amdgpu_waves_per_eu(strategy == 2 ? 3 : 4, 4))) name(GridParams P) { \
-    etc2_encode_one<strategy>(P);                                                                                      \
+    etc2_encode_one<strategy>(P, tile_of_launch(P));                                                                                      \
   }
 ICAMD_ETC2_KERNEL(icamd_etc2_rgba8_kernel, 2)            // kSmallerError (the reference's default)
 ICAMD_ETC2_KERNEL(icamd_etc2_rgba8_split_h_kernel, 0)    // kSplitHorizontally

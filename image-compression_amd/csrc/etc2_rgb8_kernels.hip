@@ -9,43 +9,12 @@
 // strategy at four waves per SIMD and without scratch.  Phase two has no wave-uniform decision.
 // The block leaves as one 8-byte store.
 // Decode: one block per lane, an 8-byte block load and four 12-byte row stores (RGB888), clipped at the image's edge.
-#include "etc1_block.h"
-#include "etc2_colour_block.h"
+#include "etc2_encode_bodies.inc"  // etc2_rgb8_encode_one: the encode body, shared with the chain kernels of etc2_mip_kernels.hip
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-template <int COMPS, int STRATEGY>
-__device__ __forceinline__ void etc2_rgb8_encode_one(const GridParams &P) {
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: a scalar register
-  Out8 c;
-  {
-    const TileCoord t = locate_tile_lane(P, threadIdx.x);
-    if (!t.valid) return;
-    uint32_t px[16];
-    load_tile_block<COMPS>(P, t, px);
-    if (STRATEGY == 3) {
-      c = encode_etc1_block<false>(px, 3u);
-    } else {
-      const uint32_t spread = etc1_block_spread(px);
-      c = etc1_encode_classified<STRATEGY>(px, etc1_constant_block(px, spread), spread >= ICAMD_ETC1_BUSY_SPREAD);
-    }
-  }
-  // Phase two holds NO vector register across the search: the lane index comes from the hardware (mbcnt) and the wave's from
-  // a scalar register, the block's coordinates and addresses are derived again from them, and the texels are read again (the
-  // compiler barrier keeps the second read apart from the first).  With as little as the lane index kept alive the RGBA8
-  // kSmallerError kernel spills 8 bytes at 128 VGPRs.
-  asm volatile("" ::: "memory");
-  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  const TileCoord t = locate_tile_lane(P, lane + 64u * wave);
-  if (!t.valid) return;  // (the same lanes as above; the store below is bounded by THIS coordinate)
-  uint32_t px[16];
-  load_tile_block<COMPS>(P, t, px);
-  const Out8 o = etc2_rgb8_choose(px, c);
-  store_stream8(tile_dst<8>(P, t), o.lo, o.hi);
-}
 
 __device__ __forceinline__ void etc2_rgb8_decode_one(const DecodeParams &P, uint32_t k) {
   const uint32_t img = fastdiv(k, P.div_bpi);
@@ -79,7 +48,7 @@ extern "C" {
 // (amdgpu_waves_per_eu(4): as the ETC1 kernels -- the colour search must fit 128 VGPRs)
 #define ICAMD_ETC2_RGB8_KERNEL(name, comps, strategy)                                                                  \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) __attribute__((amdgpu_waves_per_eu(4))) name(GridParams P) { \
-    etc2_rgb8_encode_one<comps, strategy>(P);                                                                          \
+    etc2_rgb8_encode_one<comps, strategy>(P, tile_of_launch(P));                                                                          \
   }
 ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgb888_kernel, 3, 2)            // kSmallerError (the reference's default)
 ICAMD_ETC2_RGB8_KERNEL(icamd_etc2_rgb8_rgba8_kernel, 4, 2)

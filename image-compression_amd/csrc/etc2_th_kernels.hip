@@ -8,30 +8,17 @@
 // is strictly closer -- every other block keeps the first launch's bytes untouched.  The search so stays out of the ETC1 search's
 // 128-VGPR budget, and modes 0 launches exactly what icamd_encode_device launches.  No wave-uniform decision: every shortcut of
 // etc2_th_block.h is a per-lane branch.
-#include "etc2_th_block.h"
+#include "etc2_encode_bodies.inc"  // etc2_th_encode_one: the pass's body, shared with the chain kernels of etc2_mip_kernels.hip
 #include "codec_info.h"
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
 
-template <int COMPS>
-__device__ __forceinline__ void etc2_th_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile_lane(P, threadIdx.x);
-  if (!t.valid) return;  // (the load and the store below are bounded by this coordinate, as in the first launch)
-  uint32_t px[16];
-  load_tile_block<COMPS>(P, t, px);
-  uint8_t *dst = tile_dst<8>(P, t);
-  const U2 v = load_stream(reinterpret_cast<const U2 *>(dst));
-  const Out8 w = { v.x, v.y };
-  Out8 o;
-  if (etc2_th_choose(px, w, &o)) store_stream8(dst, o.lo, o.hi);
-}
-
 extern "C" {
 
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_etc2_th_rgb888_kernel(GridParams P) { etc2_th_encode_one<3>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_etc2_th_rgba8_kernel(GridParams P) { etc2_th_encode_one<4>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_etc2_th_rgb888_kernel(GridParams P) { etc2_th_encode_one<3>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_etc2_th_rgba8_kernel(GridParams P) { etc2_th_encode_one<4>(P, tile_of_launch(P)); }
 
 }  // extern "C"
 

@@ -1638,6 +1638,92 @@ int icamd_encode_mips_filtered_device(int codec, int etc_strategy, int src_compo
                      src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, d_workspace, workspace_bytes, hip_stream);
 } ICAMD_ABI_CATCH
 
+// ---- mip chains of the ETC2 family (EXTENSION): the plan is etc2_mip_plan.h's; here are the argument checks ----
+// the order of the levels inside the encode launch's grid.x (icamd_etc2_mip_tune: time, never bytes)
+static std::atomic<int> g_etc2_mip_order{icamd::kEtc2MipLargestFirst};  // (measured: DESIGN.md 3.18)
+int icamd_etc2_mip_tune(int level_order) try {
+  if (level_order != icamd::kEtc2MipSmallestFirst && level_order != icamd::kEtc2MipLargestFirst)
+    return fail(ICAMD_ERR_ARG, "icamd_etc2_mip_tune: level_order must be 0 (smallest level first) or 1 (largest first, the default)");
+  g_etc2_mip_order.store(level_order);
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+size_t icamd_etc2_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets) {
+  return icamd::etc2_mip_chain_bytes(codec, height, width, levels, level_offsets);
+}
+
+size_t icamd_etc2_mip_workspace_size(int codec, int src_components, uint32_t height, uint32_t width, uint32_t levels,
+                                     uint32_t n_images) {
+  if (!icamd::etc2_mip_codec(codec) || !codec_accepts_components(codec, src_components)) return 0;
+  return icamd::etc2_mip_plan({ codec, src_components, ICAMD_MIP_FILTER_BOX, ICAMD_ETC2_MODES_DEFAULT, height, width, levels, n_images,
+                                0, 0, 0, icamd::kEtc2MipSmallestFirst }).workspace_bytes;
+}
+
+// The filter rules of icamd_encode_etc2_mips_device: the colour filters for the three colour codecs, the normal-map filter for
+// EAC RG11 from RG8 (the one layout the filtered pixel pyramid covers), the box for everything.
+static int etc2_mip_check_filter(int codec, int comps, int filter) {
+  if (filter == ICAMD_MIP_FILTER_BOX) return ICAMD_OK;
+  if (filter == ICAMD_MIP_FILTER_NORMAL)
+    return codec == ICAMD_EAC_RG11 && comps == 2
+               ? ICAMD_OK
+               : fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_NORMAL applies to ICAMD_EAC_RG11 chains from a 2-component (RG) source only");
+  if (filter < 0 || filter > (ICAMD_MIP_FILTER_SRGB | ICAMD_MIP_FILTER_ALPHA_WEIGHTED))
+    return fail(ICAMD_ERR_ARG, "mip filter must be a combination of ICAMD_MIP_FILTER_SRGB and ICAMD_MIP_FILTER_ALPHA_WEIGHTED, "
+                               "or ICAMD_MIP_FILTER_NORMAL alone");
+  if (eac11_codec(codec)) return fail(ICAMD_ERR_ARG, "EAC R11 / RG11 hold data channels: ICAMD_MIP_FILTER_BOX, or NORMAL for RG11 from RG8");
+  if ((filter & ICAMD_MIP_FILTER_ALPHA_WEIGHTED) && comps != 4)
+    return fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_ALPHA_WEIGHTED needs a 4-component source");
+  return ICAMD_OK;
+}
+
+int icamd_encode_etc2_mips_device(int codec, int etc_strategy, int etc2_modes, int src_components, int swap_rb, int filter,
+                                  uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                                  size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src, void *d_dst,
+                                  void *d_workspace, size_t workspace_bytes, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (!icamd::etc2_mip_codec(codec))
+    return fail(ICAMD_ERR_ARG, "icamd_encode_etc2_mips_device encodes ETC2 RGBA8 / RGB8 / RGB8A1 and EAC R11 / RG11 only");
+  if (etc2_modes != ICAMD_ETC2_MODES_DEFAULT && !(etc2_modes == ICAMD_ETC2_MODES_TH && codec == ICAMD_ETC2_RGB8))
+    return fail(ICAMD_ERR_ARG, "etc2_modes must be ICAMD_ETC2_MODES_DEFAULT, or ICAMD_ETC2_MODES_TH with ICAMD_ETC2_RGB8");
+  int rc = mip_check_components(codec, src_components, swap_rb);
+  if (rc != ICAMD_OK) return rc;
+  rc = etc2_mip_check_filter(codec, src_components, filter);
+  if (rc != ICAMD_OK) return rc;
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  const icamd::Etc2MipPlan plan = icamd::etc2_mip_plan({ codec, src_components, filter, etc2_modes, height, width, levels, n_images,
+                                                         row_stride_bytes, src_image_stride_bytes, dst_image_stride_bytes,
+                                                         g_etc2_mip_order.load() });
+  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * (uint32_t)src_components;
+  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < plan.chain_bytes))
+    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
+  if (plan.workspace_bytes && (!d_workspace || workspace_bytes < plan.workspace_bytes))
+    return fail(ICAMD_ERR_ARG, "workspace smaller than icamd_etc2_mip_workspace_size");
+  if (n_images == 0) return ICAMD_OK;
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (plan.form != icamd::kMipLaunch) return fail(ICAMD_ERR_ARG, "ETC2 mip chain: more workgroups than one launch holds");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const icamd::MipBuffers buffers = { static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_workspace), static_cast<uint8_t *>(d_dst) };
+  // the pixel pyramid into the workspace (built unswapped: averaging is per channel), then every level of every image in one
+  // launch (per piece of 65 535 images), then -- ICAMD_ETC2_MODES_TH -- the T / H pass over the same grid
+  for (uint32_t k = 0; k < plan.pyramid.n_passes; ++k)
+    ICAMD_HIP(icamd::launch_mip_pass(icamd::kMipPyramidMode, src_components, filter, plan.pyramid.pass[k], buffers, false, stream),
+              "launch mip pyramid");
+  ICAMD_HIP(icamd::launch_etc2_mip(codec, src_components, (uint32_t)etc_strategy, false, swap_rb != 0, plan, buffers,
+                                   src_image_stride_bytes, dst_image_stride_bytes, stream), "launch etc2 mip chain");
+  if (plan.th)
+    ICAMD_HIP(icamd::launch_etc2_mip(codec, src_components, (uint32_t)etc_strategy, true, swap_rb != 0, plan, buffers,
+                                     src_image_stride_bytes, dst_image_stride_bytes, stream), "launch etc2 mip chain t/h");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_etc2_mip_kernel_name(int codec, int src_components, int etc_strategy, int etc2_modes) {
+  if (etc2_modes != ICAMD_ETC2_MODES_DEFAULT && !(etc2_modes == ICAMD_ETC2_MODES_TH && codec == ICAMD_ETC2_RGB8)) return "";
+  return icamd::etc2_mip_kernel_form(codec, src_components, etc_strategy, etc2_modes == ICAMD_ETC2_MODES_TH);
+}
+
 // icamd_mip_pyramid_device / icamd_mip_pyramid_filtered_device (the former is filter 0)
 static int mip_pyramid(int src_components, int filter, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
                        uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,

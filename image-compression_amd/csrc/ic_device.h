@@ -327,21 +327,28 @@ struct TileCoord {
 // WIDE_ROWS > 1: the workgroup covers WIDE_ROWS block rows and every lane encodes WIDE_ROWS vertically adjacent blocks
 // (the returned coordinate is the first one; the caller steps brow0 / brow).
 // tile_col: the tile column this workgroup takes (blockIdx.x, unless the kernel deals the columns out differently)
+// tile_row, img: the tile row and the image, for kernels whose grid is not (column tiles, row tiles, images) -- the chain kernels
+// of etc2_mip_kernels.hip, which find level, tile and image of a workgroup in a table; every other kernel takes them from
+// blockIdx.y (+ tile_row0) and blockIdx.z through the overloads below
 template <bool WIDE, uint32_t WIDE_ROWS = 1>
-__device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t tile_col) {
+__device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t tile_col, uint32_t tile_row, uint32_t img) {
   TileCoord t;
   const uint32_t cols = WIDE ? 256u : 1u << P.log2_tile_cols, rows = WIDE ? WIDE_ROWS : 256u >> P.log2_tile_cols;
   t.lx = WIDE ? threadIdx.x : threadIdx.x & (cols - 1u);
   t.ly = WIDE ? 0u : threadIdx.x >> P.log2_tile_cols;
   t.bcol0 = tile_col * cols;
-  t.brow0 = (blockIdx.y + P.tile_row0) * rows;
+  t.brow0 = tile_row * rows;
   t.bcol = t.bcol0 + t.lx;
   t.brow = t.brow0 + t.ly;
-  t.img = blockIdx.z;
+  t.img = img;
   t.full = t.bcol0 + cols <= P.block_cols && t.brow0 + rows <= P.block_rows;
   t.interior = (t.bcol0 + cols) * 4u <= P.width && (t.brow0 + rows) * 4u <= P.height;
   t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
   return t;
+}
+template <bool WIDE, uint32_t WIDE_ROWS = 1>
+__device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t tile_col) {
+  return locate_tile<WIDE, WIDE_ROWS>(P, tile_col, blockIdx.y + P.tile_row0, blockIdx.z);
 }
 template <bool WIDE, uint32_t WIDE_ROWS = 1>
 __device__ __forceinline__ TileCoord locate_tile(const GridParams &P) {
@@ -349,20 +356,34 @@ __device__ __forceinline__ TileCoord locate_tile(const GridParams &P) {
 }
 // locate_tile<false> for lane `tid` of the workgroup: for kernels that derive the coordinate a second time from the hardware's
 // lane index instead of holding it in registers (etc2_rgb8_kernels.hip, etc2_a1_kernels.hip).
-__device__ __forceinline__ TileCoord locate_tile_lane(const GridParams &P, uint32_t tid) {
+// (the second form: tile column, tile row and image given, as for locate_tile)
+__device__ __forceinline__ TileCoord locate_tile_lane(const GridParams &P, uint32_t tid, uint32_t tile_col, uint32_t tile_row,
+                                                      uint32_t img) {
   TileCoord t;
   const uint32_t cols = 1u << P.log2_tile_cols, rows = 256u >> P.log2_tile_cols;
   t.lx = tid & (cols - 1u);
   t.ly = tid >> P.log2_tile_cols;
-  t.bcol0 = blockIdx.x * cols;
-  t.brow0 = (blockIdx.y + P.tile_row0) * rows;
+  t.bcol0 = tile_col * cols;
+  t.brow0 = tile_row * rows;
   t.bcol = t.bcol0 + t.lx;
   t.brow = t.brow0 + t.ly;
-  t.img = blockIdx.z;
+  t.img = img;
   t.full = t.bcol0 + cols <= P.block_cols && t.brow0 + rows <= P.block_rows;
   t.interior = (t.bcol0 + cols) * 4u <= P.width && (t.brow0 + rows) * 4u <= P.height;
   t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
   return t;
+}
+__device__ __forceinline__ TileCoord locate_tile_lane(const GridParams &P, uint32_t tid) {
+  return locate_tile_lane(P, tid, blockIdx.x, blockIdx.y + P.tile_row0, blockIdx.z);
+}
+// The tile a workgroup encodes.  The encode bodies of the ETC2 family (etc2_encode_bodies.inc) take it as an argument: the
+// per-level kernels pass tile_of_launch (the grid of launch_tiled), the chain kernels what their level table says.
+struct TileAt {
+  uint32_t col, row, img;
+};
+__device__ __forceinline__ TileAt tile_of_launch(const GridParams &P) {
+  const TileAt at = { blockIdx.x, blockIdx.y + P.tile_row0, blockIdx.z };
+  return at;
 }
 // The block's first source byte = uniform 64-bit base + 32-bit lane offset (<= 4 * 256 rows of stride).
 struct TileSrc {

@@ -1,8 +1,9 @@
 // ic_launch.h -- host-side launch entry points of the kernel translation units
 // (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip, blockops_kernels.hip); called by ic_capi.hip.
 // Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC), blockops_plan.h (Pad, Downsample and
-// the chunks of CopySubimage, CreateSolid and the transcode) and mip_plan.h (the passes, grids and kernels of the mip chains);
-// the launchers here run what a plan says.
+// the chunks of CopySubimage, CreateSolid and the transcode), mip_plan.h (the passes, grids and kernels of the mip chains) and
+// etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape); the
+// launchers here run what a plan says.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -11,6 +12,7 @@
 #include <atomic>
 
 #include "blockops_plan.h"
+#include "etc2_mip_plan.h"
 #include "ic_device.h"
 #include "mip_plan.h"
 
@@ -36,13 +38,8 @@ inline uint32_t device_compute_units(int dev) {
   return (uint32_t)cus;
 }
 
-// Tile shape for a block grid `block_cols` wide (GridParams::log2_tile_cols): the smallest power of two that covers
-// a block row, at most 256.
-inline uint32_t tile_log2_cols(uint32_t block_cols) {
-  uint32_t l = 0;
-  while (l < 8 && (1u << l) < block_cols) ++l;
-  return l;
-}
+// (the tile shape for a block grid, GridParams::log2_tile_cols and force_gather: tile_log2_cols and encode_tile_shape of
+// etc2_mip_plan.h, where the chain plan applies the same rule to every level)
 // Launches `kernel` over every tile of every image; images go into grid.z in chunks of at most 65 535, tile rows into
 // grid.y in chunks of at most 65 535 (GridParams::tile_row0), so any uint32 geometry the reference accepts runs.
 // max_log2_cols < 8 asks for squarer tiles (e.g. 4: 16 x 16 blocks, a wave = 16 x 4 blocks = 64 x 16 pixels):
@@ -53,14 +50,9 @@ template <typename Kernel>
 hipError_t launch_tiled(Kernel wide_kernel, Kernel narrow_kernel, GridParams P, hipStream_t stream,
                         uint32_t max_log2_cols = 8, uint32_t wide_rows = 1, bool wave_workgroups = false, uint32_t lanes_per_block = 1) {
   if (P.n_images == 0 || P.block_rows == 0 || P.block_cols == 0) return hipSuccess;
-  P.log2_tile_cols = tile_log2_cols(P.block_cols);
-  if (P.log2_tile_cols > max_log2_cols) P.log2_tile_cols = max_log2_cols;
-  // A lane addresses its block with a 32-bit offset from the tile's (64-bit, uniform) origin: up to 4 * 256 - 1 rows
-  // of stride in a 1 x 256 tile.  Rows of 4 MiB and more (or grids of 2^20 block columns and more, for the output
-  // offset) get 256 x 1 tiles, where the offset is at most three rows; rows of more than a third of 4 GiB take the
-  // 64-bit clamp-to-edge gather for every block.
-  if ((uint64_t)P.row_stride * 1024u >= (1ull << 32) || (uint64_t)P.block_cols * 4096u >= (1ull << 32)) P.log2_tile_cols = 8;
-  P.force_gather = (uint64_t)P.row_stride * 3u + 8192u >= (1ull << 32) ? 1u : 0u;
+  const TileShape shape = encode_tile_shape(P.block_cols, P.row_stride, max_log2_cols);
+  P.log2_tile_cols = shape.log2_tile_cols;
+  P.force_gather = shape.force_gather;
   const uint32_t cols = 1u << P.log2_tile_cols, rows = P.log2_tile_cols == 8 ? wide_rows : 256u >> P.log2_tile_cols;
   const uint32_t gx = (uint32_t)(((uint64_t)P.block_cols + cols - 1) / cols);
   const uint32_t gy = (uint32_t)(((uint64_t)P.block_rows + rows - 1) / rows);
@@ -200,6 +192,12 @@ struct MipBuffers {  // what MipBase names: the caller's source, workspace and o
 hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
                            hipStream_t stream);
 const char *mip_kernel_name(int mode, int comps, int filter);  // "" where launch_mip_pass has no kernel
+// Mip chains of the ETC2 family (extension, etc2_mip_kernels.hip): the encode launch of a plan of etc2_mip_plan.h -- every level
+// of every image in one launch per piece of grid.y -- or (th) the T / H pass over the same grid, after it on the stream.  The
+// pixel pyramid is in the workspace by then (launch_mip_pass on the same stream).  hipErrorInvalidValue where the list has no
+// kernel.
+hipError_t launch_etc2_mip(int codec, int comps, uint32_t etc_strategy, bool th, bool swap_rb, const Etc2MipPlan &plan,
+                           const MipBuffers &buffers, uint64_t src_image_stride, uint64_t dst_image_stride, hipStream_t stream);
 
 // Compressed-domain operations on block grids.  BlockOpParams is what a kernel receives: launch_blockop
 // (blockops_kernels.hip) fills it, per launch, from the caller's BlockOpCall and the plan of blockops_plan.h.

@@ -88,7 +88,8 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device, icamd_encoded_size,
         * icamd_kernel_name, icamd_metric_kernel_name and the container functions only: no Compressor + format pair selects it
         * (icamd_supports_format and the host-buffer entry points keep the reference's semantics, so icamd_measure_error does
-        * not reach it), and the mip entry points answer ICAMD_ERR_ARG as they do for PVRTC. */
+        * not reach it), and the mip entry points answer ICAMD_ERR_ARG as they do for PVRTC.  Mip chains: reachable through
+        * icamd_encode_etc2_mips_device, icamd_etc2_mip_chain_size, icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
        ICAMD_ETC2_RGBA8 = 16,
        /* Value 17 is unassigned and rejected by every entry point. */
        /* EXTENSION: ETC2 RGB8 (COMPRESSED_RGB8_ETC2), 8 bytes per 4 x 4 block in the raster block order of ETC1: one ETC2
@@ -144,7 +145,9 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * swap_rb.  icamd_measure_error_device compares three channels, sources of 3 or 4 components.  Reachable through
         * icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device,
         * icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions (KTX 0x9274, PKM 2.0 type 1,
-        * PVR 22; no DDS) only: no Compressor + format pair selects it, and the mip entry points answer ICAMD_ERR_ARG. */
+        * PVR 22; no DDS) only: no Compressor + format pair selects it, and the mip entry points answer ICAMD_ERR_ARG.  Mip chains
+        * (with T and H too): reachable through icamd_encode_etc2_mips_device, icamd_etc2_mip_chain_size,
+        * icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
        ICAMD_ETC2_RGB8 = 18,
        /* EXTENSION: EAC R11 (COMPRESSED_R11_EAC, one channel, 8 bytes per 4 x 4 block) and EAC RG11 (COMPRESSED_RG11_EAC, two
         * channels, 16 bytes per block: the word of R, then the word of G), in the raster block order of ETC1.  Unsigned only.
@@ -171,7 +174,8 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * decoder's byte.  Reachable through icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device,
         * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
         * (KTX 0x9270 / 0x9272, PKM 2.0 types 5 / 6, PVR 25 / 26; no DDS) only: no Compressor + format pair selects them, the mip
-        * entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0. */
+        * entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0.  Mip chains: reachable through
+        * icamd_encode_etc2_mips_device, icamd_etc2_mip_chain_size, icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
        ICAMD_EAC_R11 = 19, ICAMD_EAC_RG11 = 20,
        /* EXTENSION: ETC2 RGB8 with punch-through alpha (COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2), 8 bytes per 4 x 4 block in the
         * raster block order of ETC1.  PARITY UNPINNED (the reference has no such format) except where stated.
@@ -221,7 +225,8 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * not 0 / 255 counts against 0 / 255.  Reachable through icamd_encode_device, icamd_encode_batch_sharded_device,
         * icamd_decode_device, icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the
         * container functions (KTX 0x9276 with GL_RGBA, PKM 2.0 type 4, PVR 24; no DDS) only: no Compressor + format pair selects
-        * it, the mip entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0. */
+        * it, the mip entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0.  Mip chains: reachable through
+        * icamd_encode_etc2_mips_device, icamd_etc2_mip_chain_size, icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
        ICAMD_ETC2_RGB8A1 = 21 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
@@ -703,6 +708,52 @@ int icamd_compress_mips_filtered(int compressor, int etc_strategy, int format, i
  * pixel pyramid's, which is also what ETC1 chains launch before the ETC1 kernels. */
 enum { ICAMD_MIP_PYRAMID = -1 };
 const char *icamd_mip_kernel_name(int codec, int src_components, int filter);
+
+/* ---- mip chains of the ETC2 family (EXTENSION: ICAMD_ETC2_RGBA8, ICAMD_ETC2_RGB8, ICAMD_ETC2_RGB8A1, ICAMD_EAC_R11, ICAMD_EAC_RG11) ----
+ * The mip entry points above keep refusing these codecs (ICAMD_ERR_ARG, sizes 0); these are their chains.  Geometry, cascade,
+ * level sizes and packing are those of icamd_encode_mips_device (the mip-chain section).  P_l is what icamd_mip_pyramid_device
+ * writes for the source -- for filter != 0 icamd_mip_pyramid_filtered_device.  Averaging is per channel, so swap_rb commutes: the
+ * pyramid is built unswapped and each level is encoded with swap_rb, as the ETC1 chain does.  Level l of an image is exactly the
+ * bytes icamd_encode_etc2_device(codec, etc_strategy, etc2_modes, src_components, swap_rb, h_l, w_l, h_l, w_l,
+ * w_l * src_components, 1, ...) writes for P_l; where etc2_modes is ICAMD_ETC2_MODES_DEFAULT that is icamd_encode_device (which is
+ * what encodes the four codecs icamd_encode_etc2_device does not take).  ICAMD_ETC2_MODES_TH is accepted only with
+ * ICAMD_ETC2_RGB8, as in that entry point.  Levels sit back to back at the icamd_etc2_mip_chain_size offsets, largest first: the
+ * level views go straight into icamd_container_write.
+ * What runs: the pixel-pyramid kernels into the workspace, then ONE encode launch over every level of every
+ * image (per 65 535 images) -- its workgroups find their level in a table in the kernel argument and run the per-level kernels'
+ * code on it -- then, with ICAMD_ETC2_MODES_TH, one launch of the T / H pass over the same grid.  1 + L launches become 2 (3 for
+ * chains of more than 7 levels of an image larger than 128 x 128, whose pyramid takes two passes), 1 + 2 L become 3 (4).
+ * Source rules are each codec's icamd_encode_device rules: src_components 4 for RGBA8 and RGB8A1, 3 or 4 for RGB8, 1..4 for R11,
+ * 2..4 for RG11; swap_rb only with 3 or 4.  Filters (ICAMD_MIP_FILTER_*): 0 for all five; SRGB for RGB8, RGBA8 and RGB8A1;
+ * ALPHA_WEIGHTED and SRGB | ALPHA_WEIGHTED for those three with src_components == 4; NORMAL for ICAMD_EAC_RG11 with
+ * src_components == 2 only; everything else (R11 / RG11 with 1..3, NORMAL elsewhere, 5..7) is ICAMD_ERR_ARG.
+ * Workspace: the whole pixel pyramid of every image (levels 1 .. levels-1, src_components bytes per pixel, about a third of the
+ * source), 0 for levels == 1; it does not depend on the filter.
+ * Statuses, in this order, all before a device is touched: ICAMD_FALSE for null pointers or an empty image; ICAMD_ERR_ARG for a
+ * codec outside the five (ETC1 included), modes, components, swap_rb or a filter outside the rules; ICAMD_ERR_ARG for levels of 0
+ * or more than L_max, a row stride smaller than a row, (n_images > 1) image strides smaller than an image / a chain, or a
+ * workspace smaller than icamd_etc2_mip_workspace_size; ICAMD_OK for n_images == 0.  Then ICAMD_ERR_NO_DEVICE without a GPU.  No
+ * allocation, no synchronisation: it can be captured on one stream. */
+/* Bytes of one image's chain; fills level_offsets[0 .. levels] when non-NULL.  0 for every other codec, an empty image or
+ * levels outside 1 .. L_max. */
+size_t icamd_etc2_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets);
+/* 0 also for arguments the encode refuses (codec, components, levels). */
+size_t icamd_etc2_mip_workspace_size(int codec, int src_components, uint32_t height, uint32_t width, uint32_t levels,
+                                     uint32_t n_images);
+int icamd_encode_etc2_mips_device(int codec, int etc_strategy, int etc2_modes, int src_components, int swap_rb, int filter,
+                                  uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                                  uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                  const void *d_src, void *d_dst, void *d_workspace, size_t workspace_bytes,
+                                  void *hip_stream);
+/* Name of the __global__ kernel of the encode launch; with ICAMD_ETC2_MODES_TH (ICAMD_ETC2_RGB8 only) of the T / H launch,
+ * whatever the strategy.  An etc_strategy outside 0..3 is ICAMD_ETC_SMALLER_ERROR, as in the encoders; R11 / RG11 ignore it.
+ * "" for combinations the encode refuses. */
+const char *icamd_etc2_mip_kernel_name(int codec, int src_components, int etc_strategy, int etc2_modes);
+/* Measurement knob (scripts/bench_etc2_mips.py): the order of the levels inside the encode launch's grid.x, 1 = largest level
+ * first (the default), 0 = smallest first (the poorly filled workgroups of the small levels are dispatched first and run under
+ * level 0's; measured within 2.3 % of the default, slower on large textures and faster on some batches of small ones, DESIGN.md
+ * 3.18).  Process-wide; time only, never bytes.  ICAMD_ERR_ARG for any other value. */
+int icamd_etc2_mip_tune(int level_order);
 
 /* ---- quality metric (EXTENSION: the reference has no such function): the error of compressed blocks against source pixels ----
  * For image i, let D be the pixels that icamd_decode_device(codec, swap_rb, ...) yields for the blocks at
