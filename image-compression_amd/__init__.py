@@ -47,6 +47,9 @@ ETC2_RGB8 = 18
 # etc2_modes of encode_device (include/ic_amd.h icamd_encode_etc2_device): DEFAULT = what icamd_encode_device writes; TH = then the
 # T / H pass, which replaces the blocks a T or H word renders strictly closer (ETC2_RGB8 only)
 ETC2_MODES_DEFAULT, ETC2_MODES_TH = 0, 1
+# colour_modes of encode_etc2_colour_device (include/ic_amd.h icamd_encode_etc2_colour_device; ETC2_RGBA8, ETC2_RGB8 and
+# ETC2_RGB8A1): DEFAULT = what icamd_encode_device writes; PLANAR = + the planar word; PLANAR_TH = + T and H words
+ETC2_COLOUR_DEFAULT, ETC2_COLOUR_PLANAR, ETC2_COLOUR_PLANAR_TH = 0, 1, 2
 # EXTENSION (include/ic_amd.h ICAMD_EAC_R11): EAC R11 (one channel, 8 bytes per block) and EAC RG11 (two channels, 16 bytes per
 # block), the ETC2 family's BC4 / BC5; every word is what ETC2 RGBA8's alpha search writes for the channel, the
 # decoder is the 11-bit one.  Source channels as for BC4 / BC5.  encode_device / decode_device / measure_error_device /
@@ -183,6 +186,31 @@ def encode_device(codec, src, height, width, src_components, *, swap_rb=False, e
     if not _check(st, "icamd_encode_device"):
         return None
     return out
+
+
+def encode_etc2_colour_device(codec, src, height, width, src_components, *, colour_modes=ETC2_COLOUR_DEFAULT, swap_rb=False,
+                              etc_strategy=ETC_SMALLER_ERROR, grid_height=None, grid_width=None, row_stride_bytes=None,
+                              n_images=1, src_image_stride_bytes=None, out=None, stream=None):
+    """icamd_encode_etc2_colour_device: encode_device for ETC2_RGBA8, ETC2_RGB8 or ETC2_RGB8A1 with a choice of colour words --
+    ETC2_COLOUR_DEFAULT (encode_device itself), ETC2_COLOUR_PLANAR, ETC2_COLOUR_PLANAR_TH.  Returns the output tensor
+    [n_images, encoded_size] (device).  No synchronisation."""
+    _assert_u8_cuda(src)
+    gh = height if grid_height is None else max(grid_height, height)
+    gw = width if grid_width is None else max(grid_width, width)
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    per = encoded_size(codec, gh, gw)
+    if out is None:
+        out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    st = lib().icamd_encode_etc2_colour_device(codec, etc_strategy, colour_modes, src_components, int(swap_rb), height, width, gh,
+                                               gw, stride, n_images, img_stride, per, _ptr(src), _ptr(out),
+                                               _stream_handle(stream))
+    return out if _check(st, "icamd_encode_etc2_colour_device") else None
+
+
+def etc2_colour_kernel_name(codec, src_components, colour_modes):
+    """icamd_etc2_colour_kernel_name: the kernel of the colour-mode pass, or of what the call forwards to; "" if refused."""
+    return lib().icamd_etc2_colour_kernel_name(codec, src_components, colour_modes).decode()
 
 
 def compress_device(compressor, fmt, src, height, width, *, padding_bytes_per_row=0,

@@ -1,10 +1,11 @@
 // etc2_encode_bodies.inc -- what one workgroup of an ETC2-family encode kernel does with its tile: ETC2 RGBA8, ETC2 RGB8 (and its
-// T / H pass), ETC2 RGB8A1, EAC R11 / RG11.  Kernel text for gfx950, included by the kernel translation units only -- not a header
+// T / H pass), ETC2 RGB8A1 (and the colour-mode passes of the two), EAC R11 / RG11.  Kernel text for gfx950, included by the kernel translation units only -- not a header
 // of block math: it has no host emulation (the block routines these call live in the *_block.h headers, which have one, and the
 // workgroup -> tile -> block walk is emulated in tests/host_emul/etc2_mip_emul.cc).
 //
 // Every body takes the launch's GridParams and the tile as a TileAt (ic_device.h) and has two callers:
-//   the per-level kernels (etc2_kernels.hip, etc2_rgb8_kernels.hip, etc2_th_kernels.hip, etc2_a1_kernels.hip, eac11_kernels.hip),
+//   the per-level kernels (etc2_kernels.hip, etc2_rgb8_kernels.hip, etc2_th_kernels.hip, etc2_a1_kernels.hip,
+//     etc2_colour_modes_kernels.hip, eac11_kernels.hip),
 //     whose grid is launch_tiled's: tile_of_launch(P);
 //   the chain kernels (etc2_mip_kernels.hip), one launch over every level of a mip chain: P is the level's view and the tile
 //     comes from the level table.
@@ -18,6 +19,7 @@
 #include "etc2_colour_block.h"
 #include "etc2_a1_block.h"
 #include "etc2_th_block.h"
+#include "etc2_a1_th_block.h"
 #include "eac11_block.h"
 #include "metric_block.h"  // metric_gather_channel: the clamp-to-edge gather of one channel
 
@@ -91,6 +93,35 @@ __device__ __forceinline__ void etc2_th_encode_one(const GridParams &P, const Ti
   const Out8 w = { v.x, v.y };
   Out8 o;
   if (etc2_th_choose(px, w, &o)) store_stream8(dst, o.lo, o.hi);
+}
+
+// ---- the colour-mode passes of ETC2 RGBA8 and ETC2 RGB8A1 (etc2_colour_modes_kernels.hip) ----
+// ETC2 RGBA8: the lane's colour word (bytes 8..15 of its block, an ETC1 word) becomes ICAMD_ETC2_RGB8's planar choice and, with TH,
+// its T / H choice; 8 bytes are stored only where the word changed, the alpha word never.
+template <bool TH>
+__device__ __forceinline__ void etc2_rgba8_colour_one(const GridParams &P, const TileAt &at) {
+  const TileCoord t = locate_tile_lane(P, threadIdx.x, at.col, at.row, at.img);
+  if (!t.valid) return;  // (the load and the store below are bounded by this coordinate, as in the first launch)
+  uint32_t px[16];
+  load_tile_block<4>(P, t, px);
+  uint8_t *dst = tile_dst<16>(P, t) + 8;
+  const U2 v = load_stream(reinterpret_cast<const U2 *>(dst));
+  const Out8 e = { v.x, v.y };
+  const Out8 o = etc2_rgba8_colour_choose<TH>(px, e);
+  if (o.lo != e.lo || o.hi != e.hi) store_stream8(dst, o.lo, o.hi);
+}
+
+// ETC2 RGB8A1: the T / H choice of the lane's block by its class (etc2_a1_th_block.h); stored only where the word changed.
+__device__ __forceinline__ void etc2_a1_th_one(const GridParams &P, const TileAt &at) {
+  const TileCoord t = locate_tile_lane(P, threadIdx.x, at.col, at.row, at.img);
+  if (!t.valid) return;
+  uint32_t px[16];
+  load_tile_block<4>(P, t, px);
+  uint8_t *dst = tile_dst<8>(P, t);
+  const U2 v = load_stream(reinterpret_cast<const U2 *>(dst));
+  const Out8 w = { v.x, v.y };
+  Out8 o;
+  if (etc2_a1_th_choose(px, w, &o)) store_stream8(dst, o.lo, o.hi);
 }
 
 // ---- ETC2 RGB8A1 (etc2_a1_kernels.hip) ----

@@ -590,6 +590,61 @@ const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes
   return "";
 }
 
+// EXTENSION (include/ic_amd.h ICAMD_ETC2_COLOUR_PLANAR_TH): planar, T and H colour words for all three ETC2 colour codecs.
+// true for the three codecs with a component count they take
+static bool etc2_colour_accepts(int codec, int src_components) {
+  if (codec == ICAMD_ETC2_RGB8) return src_components == 3 || src_components == 4;
+  return (codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8A1) && src_components == 4;
+}
+// true where the pair has a pass of etc2_colour_modes_kernels.hip (the others forward to an existing entry point)
+static bool etc2_colour_has_pass(int codec, int colour_modes) {
+  return (codec == ICAMD_ETC2_RGBA8 && colour_modes != ICAMD_ETC2_COLOUR_DEFAULT) ||
+         (codec == ICAMD_ETC2_RGB8A1 && colour_modes == ICAMD_ETC2_COLOUR_PLANAR_TH);
+}
+
+// Every argument is checked before any device work, in the order of icamd_encode_etc2_device; then the codec's own encode
+// and, where the pair has one, the colour-mode pass on the same stream over the same grid
+int icamd_encode_etc2_colour_device(int codec, int etc_strategy, int colour_modes, int src_components, int swap_rb,
+                                    uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
+                                    uint32_t row_stride_bytes, uint32_t n_images,
+                                    size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                    const void *d_src, void *d_dst, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1)
+    return fail(ICAMD_ERR_ARG, "icamd_encode_etc2_colour_device encodes ICAMD_ETC2_RGBA8, ICAMD_ETC2_RGB8 and ICAMD_ETC2_RGB8A1 only");
+  if (colour_modes != ICAMD_ETC2_COLOUR_DEFAULT && colour_modes != ICAMD_ETC2_COLOUR_PLANAR &&
+      colour_modes != ICAMD_ETC2_COLOUR_PLANAR_TH)
+    return fail(ICAMD_ERR_ARG, "colour_modes must be ICAMD_ETC2_COLOUR_DEFAULT, _PLANAR or _PLANAR_TH");
+  if (!etc2_colour_accepts(codec, src_components))
+    return fail(ICAMD_ERR_ARG, "src_components must be 4 (ICAMD_ETC2_RGB8: 3 or 4)");
+  if (n_images == 0) return ICAMD_OK;  // (before the stride, as in icamd_encode_device)
+  if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (codec == ICAMD_ETC2_RGB8 && colour_modes == ICAMD_ETC2_COLOUR_PLANAR_TH)
+    return icamd_encode_etc2_device(codec, etc_strategy, ICAMD_ETC2_MODES_TH, src_components, swap_rb, height, width, grid_height,
+                                    grid_width, row_stride_bytes, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src,
+                                    d_dst, hip_stream);
+  const int rc = icamd_encode_device(codec, etc_strategy, src_components, swap_rb, height, width, grid_height, grid_width,
+                                     row_stride_bytes, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst,
+                                     hip_stream);
+  if (rc != ICAMD_OK || !etc2_colour_has_pass(codec, colour_modes)) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, swap_rb, (uint32_t)etc_strategy);
+  ICAMD_HIP(icamd::launch_etc2_colour_modes(codec, colour_modes, P, static_cast<hipStream_t>(hip_stream)),
+            "launch etc2 colour modes");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_etc2_colour_kernel_name(int codec, int src_components, int colour_modes) {
+  if (colour_modes == ICAMD_ETC2_COLOUR_DEFAULT) return icamd_kernel_name(codec, src_components);
+  if ((colour_modes != ICAMD_ETC2_COLOUR_PLANAR && colour_modes != ICAMD_ETC2_COLOUR_PLANAR_TH) ||
+      !etc2_colour_accepts(codec, src_components))
+    return "";
+  if (etc2_colour_has_pass(codec, colour_modes)) return icamd::etc2_colour_modes_kernel_name(codec, colour_modes);
+  if (codec == ICAMD_ETC2_RGB8 && colour_modes == ICAMD_ETC2_COLOUR_PLANAR_TH)
+    return icamd_etc2_kernel_name(codec, src_components, ICAMD_ETC2_MODES_TH);
+  return icamd_kernel_name(codec, src_components);  // PLANAR of ICAMD_ETC2_RGB8 and ICAMD_ETC2_RGB8A1 is icamd_encode_device
+}
+
 int icamd_pvrtc2_encode_region_device(uint32_t size, uint32_t first_block, uint32_t n_blocks, const void *d_src,
                                       void *d_dst_region, void *hip_stream) try {
   if (!d_src || !d_dst_region || n_blocks == 0) return ICAMD_FALSE;

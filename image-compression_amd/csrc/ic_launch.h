@@ -90,6 +90,11 @@ const char *etc2_th_kernel_name(int comps);  // "" unless comps is 3 or 4
 // ETC2 RGB8A1 (extension, etc2_a1_kernels.hip): RGBA8 sources only; P.etc_strategy as for ETC1
 hipError_t launch_etc2_a1(const GridParams &P, hipStream_t stream);
 const char *etc2_a1_kernel_name(int comps);  // "" unless comps == 4
+// The colour-mode passes of ETC2 RGBA8 and ETC2 RGB8A1 (extension, etc2_colour_modes_kernels.hip; icamd_encode_etc2_colour_device):
+// run on the stream AFTER launch_etc2 / launch_etc2_a1 with the same P.  codec ICAMD_ETC2_RGBA8 with colour_modes
+// ICAMD_ETC2_COLOUR_PLANAR or _PLANAR_TH, or ICAMD_ETC2_RGB8A1 with _PLANAR_TH; the name is "" for every other pair
+hipError_t launch_etc2_colour_modes(int codec, int colour_modes, const GridParams &P, hipStream_t stream);
+const char *etc2_colour_modes_kernel_name(int codec, int colour_modes);
 
 // PVRTC1 2bpp: square power-of-two RGBA8 images, n_images of them.
 struct PvrtcParams {

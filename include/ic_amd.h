@@ -84,6 +84,10 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * as for ETC1.  icamd_decode_device writes RGBA8 rows (swap_rb: stored R goes to the third byte, as for DXT5) and decodes
         * colour words in all five modes (individual, differential, T, H, planar: see ICAMD_ETC2_RGB8 below); the encoder
         * itself writes the two ETC1-compatible ones only.
+        *   Colour half with planar, T and H words, opt-in: icamd_encode_etc2_colour_device(ICAMD_ETC2_RGBA8, ...,
+        *       ICAMD_ETC2_COLOUR_PLANAR / _PLANAR_TH, ...) keeps bytes 0..7 and writes into bytes 8..15 what ICAMD_ETC2_RGB8 writes
+        *       for the block of the same RGBA8 source (icamd_encode_device, or icamd_encode_etc2_device with ICAMD_ETC2_MODES_TH);
+        *       stated in full at that function.  icamd_encode_device itself writes what is stated above.
         * icamd_measure_error_device compares all four channels.  Reachable through icamd_encode_device,
         * icamd_encode_batch_sharded_device, icamd_decode_device, icamd_measure_error_device, icamd_encoded_size,
         * icamd_kernel_name, icamd_metric_kernel_name and the container functions only: no Compressor + format pair selects it
@@ -219,6 +223,10 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         *       1, 2, 3 (q5 = 12, 18, 25, every opaque texel index 0 at error 41, the partitions tie at 328), 60 90 c8 01 ff 00 00 00
         *       for strategy 0.  T and H are decoded, never written; a fully opaque block never gets Op = 0, and no block gets a
         *       transparent texel it did not have.
+        *   Encode with T and H, opt-in: icamd_encode_etc2_colour_device(ICAMD_ETC2_RGB8A1, ..., ICAMD_ETC2_COLOUR_PLANAR_TH, ...)
+        *       replaces the word W above where a T or H word is STRICTLY closer over the block's opaque texels: the search of
+        *       ICAMD_ETC2_RGB8 on fully opaque blocks, a masked search with paints {0, 1, 3} on blocks with 1..15 transparent
+        *       texels (a definition, stated in full at that function; csrc/etc2_a1_th_block.h); all-transparent blocks stay.
         * icamd_decode_device writes RGBA8 rows (swap_rb as for ICAMD_ETC2_RGBA8) and reads all four modes under both values of Op.
         * icamd_measure_error_device takes src_components == 4 and compares all four decoded channels against the source, as
         * ICAMD_ETC2_RGBA8 does -- so colour stored under a transparent texel counts against decoded 0, and a source alpha that is
@@ -348,7 +356,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
                         const void *d_src, void *d_dst, void *hip_stream);
 
 /* EXTENSION: the ETC2 family's encoder with a choice of colour modes.  codec must be ICAMD_ETC2_RGB8 (ETC2 RGBA8's colour half and
- * ETC2 RGB8A1 are not covered: ICAMD_ERR_ARG, like every other codec) and etc2_modes one of the two values below, else
+ * ETC2 RGB8A1 are covered by icamd_encode_etc2_colour_device below; here they are ICAMD_ERR_ARG, like every other codec) and etc2_modes one of the two values below, else
  * ICAMD_ERR_ARG.  Every other argument means what it means to icamd_encode_device and is checked before any device work: a
  * null pointer or a zero height / width returns ICAMD_FALSE; then a codec, etc2_modes or src_components outside the above
  * ICAMD_ERR_ARG; then n_images == 0 ICAMD_OK; then a row stride shorter than a row ICAMD_ERR_ARG -- the order of
@@ -366,6 +374,62 @@ int icamd_encode_etc2_device(int codec, int etc_strategy, int etc2_modes, int sr
                              size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
                              const void *d_src, void *d_dst, void *hip_stream);
 const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes);
+
+/* EXTENSION: planar, T and H colour words for all three ETC2 colour codecs.  codec is ICAMD_ETC2_RGBA8,
+ * ICAMD_ETC2_RGB8 or ICAMD_ETC2_RGB8A1; src_components 4 for ICAMD_ETC2_RGBA8 and ICAMD_ETC2_RGB8A1, 3 or 4 for ICAMD_ETC2_RGB8;
+ * colour_modes one of the three values below.  Every other argument means what it means to icamd_encode_device.  Every argument
+ * is checked before any device work, in the order of icamd_encode_etc2_device: a null pointer or a zero height / width returns
+ * ICAMD_FALSE; then a codec, colour_modes or src_components outside the above ICAMD_ERR_ARG; then n_images == 0 ICAMD_OK; then a
+ * row stride shorter than a row ICAMD_ERR_ARG.  icamd_encode_device, icamd_encode_etc2_device and icamd_encode_etc2_mips_device
+ * write and refuse what they did before.  The output is defined through those entry points:
+ *   ICAMD_ETC2_COLOUR_DEFAULT, any codec: the call IS icamd_encode_device -- the same kernels, the same bytes.
+ *   ICAMD_ETC2_RGB8: PLANAR is icamd_encode_device; PLANAR_TH is icamd_encode_etc2_device(..., ICAMD_ETC2_MODES_TH, ...).
+ *   ICAMD_ETC2_RGBA8: bytes 0..7 of every block (the EAC alpha word) are what icamd_encode_device(ICAMD_ETC2_RGBA8,
+ *       etc_strategy, ...) writes.  PLANAR: bytes 8..15 are the 8 bytes icamd_encode_device(ICAMD_ETC2_RGB8, etc_strategy, 4,
+ *       swap_rb, the same geometry) writes for that block of the same source; PLANAR_TH: the 8 bytes
+ *       icamd_encode_etc2_device(ICAMD_ETC2_RGB8, etc_strategy, ICAMD_ETC2_MODES_TH, 4, ...) writes.  Alpha never enters the colour
+ *       choice.
+ *   ICAMD_ETC2_RGB8A1: PLANAR is icamd_encode_device (that encoder already takes the planar word on opaque blocks).  PLANAR_TH,
+ *       with W the word icamd_encode_device(ICAMD_ETC2_RGB8A1, etc_strategy, ...) writes, by the block's class at
+ *       ICAMD_ETC2_RGB8A1:
+ *       1. All 16 texels transparent: W.
+ *       2. None transparent: the T / H search of ICAMD_ETC2_RGB8 verbatim with this W in place of its W -- the winner's word
+ *          (bit 33 set, so Op = 1) if its error is STRICTLY smaller than err(W), else W.
+ *       3. 1..15 transparent: the masked T / H search, a definition and not a heuristic.  O = the opaque texels (byte 3 >= 128),
+ *          n = |O|.
+ *          Partitions of O into clusters A and B, tried in this order; one with A or B empty is dropped.
+ *              L: Y_p = R + 2 G + B; p is in B iff n Y_p > Sum over O of Y.
+ *              C: c* = the channel with the largest max - min over O, ties to R before G before B; p is in B iff
+ *              2 v_p[c*] > max + min over O.
+ *          Cluster colours: the rule of ICAMD_ETC2_RGB8 over the cluster's m texels, q = (30 S + 255 m) / (510 m) truncating,
+ *              colour 17 q.  A partition whose two 12-bit codes are equal is dropped.
+ *          Candidates of a partition, in this order, each with di = 0..7 ascending; the paints are the decoder's under Op = 0,
+ *              where index 2 is the transparent texel.  T(C1 = a, C2 = b): {0: C1, 1: clamp(C2 + d), 3: clamp(C2 - d)};
+ *              T(C1 = b, C2 = a): the same with the roles exchanged; H(a, b): the stored order is forced by di's lowest bit --
+ *              (C1, C2) = (a, b) where (a >= b as R << 16 | G << 8 | B) == (di & 1), else (b, a) -- and the paints are
+ *              {0: clamp(C1 + d), 1: clamp(C1 - d), 3: clamp(C2 - d)}; no index is flipped.
+ *          Every opaque texel takes the allowed index (0, 1 or 3) with the smallest squared RGB distance, ties to the smallest
+ *              index; transparent texels take index 2 and add no error.  The best candidate has the smallest error, ties to the
+ *              earliest (L before C, then the candidate order, then di).  err(W) is W's squared RGB error over O only, W read
+ *              by the ICAMD_ETC2_RGB8A1 decoder.  The block is the best candidate's word if its error is STRICTLY smaller than
+ *              err(W), else W byte for byte -- also where no partition survives (always so for n = 1).
+ *          Packing: that of the T / H words of ICAMD_ETC2_RGB8 with bit 33 clear.
+ *       So no block gains or loses a transparent texel, and the summed error over the opaque texels never exceeds
+ *       icamd_encode_device's, block by block.
+ * Where new words are written (ICAMD_ETC2_RGBA8 PLANAR / PLANAR_TH, ICAMD_ETC2_RGB8A1 PLANAR_TH) a second launch on the same
+ * stream follows the codec's own kernels and stores 8 bytes only where a block's colour word changes; all other bytes stay as the
+ * first launch left them.  icamd_etc2_colour_kernel_name names the kernel of that launch; for the forwarding pairs it answers
+ * what the entry point forwarded to answers (ICAMD_ETC2_COLOUR_DEFAULT: icamd_kernel_name), and "" for a refused combination.
+ * Mip chains, the sharded batch entry, the transcodes and the C++ classes do not reach these modes. */
+enum { ICAMD_ETC2_COLOUR_DEFAULT = 0,      /* what icamd_encode_device writes */
+       ICAMD_ETC2_COLOUR_PLANAR = 1,       /* + the planar word */
+       ICAMD_ETC2_COLOUR_PLANAR_TH = 2 };  /* + the T and H words */
+int icamd_encode_etc2_colour_device(int codec, int etc_strategy, int colour_modes, int src_components, int swap_rb,
+                                    uint32_t height, uint32_t width, uint32_t grid_height, uint32_t grid_width,
+                                    uint32_t row_stride_bytes, uint32_t n_images,
+                                    size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                    const void *d_src, void *d_dst, void *hip_stream);
+const char *icamd_etc2_colour_kernel_name(int codec, int src_components, int colour_modes);
 
 /* ---- "next" row 8f.1: block decoders on device (Compressor::Decompress, compressor.h:85-86;
  * helper.h:218-262, dxtc.cc:167-267, etc.cc:198-289).  Writes height rows of
