@@ -60,6 +60,9 @@ EAC_R11, EAC_RG11 = 19, 20
 # masked differential search.  Decodes to RGBA8 with alpha 0 or 255.  encode_device / decode_device /
 # measure_error_device / containers only
 ETC2_RGB8A1 = 21
+# EXTENSION (include/ic_amd.h ICAMD_EAC_SIGNED_R11): signed EAC R11 / RG11, 8 / 16 bytes per block, int16 samples in and out.
+# encode_eac11_16_device / decode_eac11_16_device / measure_error_eac11_16_device / containers only (22 and 23 are unassigned)
+EAC_SIGNED_R11, EAC_SIGNED_RG11 = 24, 25
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -936,3 +939,91 @@ def psnr_from_stats(sse, n_pixels, n_channels):
     import math
     total = float(sse.sum()) if hasattr(sse, "sum") else float(sum(sse))
     return math.inf if total == 0 else 10.0 * math.log10(255.0 ** 2 * n_pixels * n_channels / total)
+
+
+# ---- 16-bit and signed EAC R11 / RG11 (include/ic_amd.h icamd_encode_eac11_16_device)
+# codec: EAC_R11 / EAC_RG11 (uint16 samples) or EAC_SIGNED_R11 / EAC_SIGNED_RG11 (int16 samples).  Pixel tensors may be
+# torch.uint16 / torch.int16 (one element per sample) or torch.uint8 (the same memory as little-endian bytes); blocks are
+# torch.uint8.  Strides and paddings are always in BYTES.
+
+def _eac11_16_signed(codec):
+    return codec in (EAC_SIGNED_R11, EAC_SIGNED_RG11)
+
+
+def _assert_samples_cuda(t):
+    assert t.is_cuda and t.is_contiguous() and t.dtype in (torch.uint8, torch.uint16, torch.int16)
+
+
+def eac11_16_kernel_name(codec, src_channels, metric=False):
+    """icamd_eac11_16_kernel_name, or with metric=True icamd_eac11_16_metric_kernel_name; "" for a refused combination."""
+    fn = lib().icamd_eac11_16_metric_kernel_name if metric else lib().icamd_eac11_16_kernel_name
+    return fn(codec, src_channels).decode()
+
+
+def encode_eac11_16_device(codec, src, height, width, src_channels, *, grid_height=None, grid_width=None, row_stride_bytes=None,
+                           n_images=1, src_image_stride_bytes=None, out=None, stream=None):
+    """icamd_encode_eac11_16_device on `src`: a contiguous CUDA tensor of torch.uint16 (unsigned codecs) / torch.int16 (signed)
+    samples, src_channels per pixel, or the same bytes as torch.uint8.  Returns the torch.uint8 blocks [n_images, encoded_size]
+    (device), or None where the call answers false.  No synchronisation."""
+    _assert_samples_cuda(src)
+    gh = height if grid_height is None else max(grid_height, height)
+    gw = width if grid_width is None else max(grid_width, width)
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    per = encoded_size(codec, gh, gw)
+    if out is None:
+        out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, per, "encode_eac11_16_device")
+    st = lib().icamd_encode_eac11_16_device(codec, src_channels, height, width, gh, gw, stride, n_images, img_stride, per,
+                                            _ptr(src), _ptr(out), _stream_handle(stream))
+    return out if _check(st, "icamd_encode_eac11_16_device") else None
+
+
+def decode_eac11_16_device(codec, blocks, height, width, *, padding_bytes_per_row=0, n_images=1, stream=None):
+    """icamd_decode_eac11_16_device: torch.uint8 blocks -> a [n_images, height * (width * channels + padding_bytes_per_row / 2)]
+    tensor of torch.uint16 (unsigned codecs) or torch.int16 (signed) samples, channels = 1 (R11) or 2 (RG11, R then G); the
+    padding samples are zero.  None where the call answers false.  No synchronisation."""
+    _assert_u8_cuda(blocks)
+    chans = 2 if codec in (EAC_RG11, EAC_SIGNED_RG11) else 1
+    per_out = height * (width * chans * 2 + padding_bytes_per_row)
+    out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)
+    st = lib().icamd_decode_eac11_16_device(codec, height, width, padding_bytes_per_row, n_images, encoded_size(codec, height, width),
+                                            per_out, _ptr(blocks), _ptr(out), _stream_handle(stream))
+    if not _check(st, "icamd_decode_eac11_16_device"):
+        return None
+    return out.view(torch.int16 if _eac11_16_signed(codec) else torch.uint16)
+
+
+def measure_error_eac11_16_device(codec, src, blocks, height, width, src_channels, *, grid_height=None, grid_width=None,
+                                  row_stride_bytes=None, n_images=1, src_image_stride_bytes=None, blocks_image_stride_bytes=None,
+                                  out=None, stream=None):
+    """icamd_measure_error_eac11_16_device: `blocks` (torch.uint8, as encode_eac11_16_device writes them for the grid) against
+    the samples `src` (as encode_eac11_16_device reads them).  Returns ([n, 4] int64 sums of squared 16-bit differences, [n, 4]
+    int32 largest absolute differences; entries 0 = R, 1 = G) as device tensors, or None where the call answers false.  `out`: a
+    caller-owned [n_images, 48] uint8 device tensor for the raw records.  No synchronisation."""
+    _assert_samples_cuda(src)
+    _assert_u8_cuda(blocks)
+    gh = height if grid_height is None else grid_height
+    gw = width if grid_width is None else grid_width
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    blk_stride = encoded_size(codec, max(gh, height), max(gw, width)) if blocks_image_stride_bytes is None \
+        else blocks_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, ERROR_STATS_BYTES), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, ERROR_STATS_BYTES, "measure_error_eac11_16_device")
+    st = lib().icamd_measure_error_eac11_16_device(codec, src_channels, height, width, gh, gw, stride, n_images, img_stride,
+                                                   blk_stride, _ptr(src), _ptr(blocks), _ptr(out), _stream_handle(stream))
+    if not _check(st, "icamd_measure_error_eac11_16_device"):
+        return None
+    return _split_stats(out)
+
+
+def psnr16_from_stats(sse, n_pixels, n_channels, signed=False):
+    """10 log10(peak^2 N C / SSE) of 16-bit samples, peak 65535 (unsigned) or 32767 (signed); inf for a perfect match."""
+    import math
+    total = float(sse.sum()) if hasattr(sse, "sum") else float(sum(sse))
+    peak = 32767.0 if signed else 65535.0
+    return math.inf if total == 0 else 10.0 * math.log10(peak ** 2 * n_pixels * n_channels / total)

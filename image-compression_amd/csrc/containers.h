@@ -11,12 +11,14 @@
 //             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03, COMPRESSED_RED_RGTC1 0x8DBB with base format
 //             GL_RED, COMPRESSED_RG_RGTC2 0x8DBD with base format GL_RG, COMPRESSED_RGBA8_ETC2_EAC 0x9278 with GL_RGBA,
 //             COMPRESSED_R11_EAC 0x9270 with GL_RED, COMPRESSED_RG11_EAC 0x9272 with GL_RG,
+//             COMPRESSED_SIGNED_R11_EAC 0x9271 with GL_RED, COMPRESSED_SIGNED_RG11_EAC 0x9273 with GL_RG,
 //             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA);
 //   * PKM  -- 16-byte big-endian header, exactly one level: "PKM 10" with type 0 for ETC1, "PKM 20" with type 3
 //             (ETC2_RGBA_NO_MIPMAPS) for ETC2 RGBA8, type 4 (ETC2_RGBA1_NO_MIPMAPS) for ETC2 RGB8A1, type 5 / 6 (ETC2_R /
-//             ETC2_RG _NO_MIPMAPS) for EAC R11 / RG11;
+//             ETC2_RG _NO_MIPMAPS) for EAC R11 / RG11, type 7 / 8 (ETC2_R_SIGNED / ETC2_RG_SIGNED _NO_MIPMAPS) for the signed two;
 //   * PVR  -- PVR v3: 52-byte little-endian header (pixel format 1 = PVRTC 2bpp RGBA, 6 = ETC1, 7 = DXT1, 11 = DXT5,
-//             12 = BC4, 13 = BC5, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11),
+//             12 = BC4, 13 = BC5, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11; signed EAC R11 / RG11 are
+//             formats 25 / 26 with the channel-type field 1, signed byte normalised, where every other codec has 0),
 //             no metadata, levels follow largest first.  PVRTC data is stored in the Z-order the encoder already
 //             produces (pvrtc_compressor.cc:551-580).
 // Mip level l of an h x w texture is max(1, h >> l) x max(1, w >> l) pixels; its block stream is what
@@ -61,10 +63,12 @@ inline bool container_supports(int container, int codec) {
     case ICAMD_CONTAINER_PVR:
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
              codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
-             codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1;
+             codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
+             codec == ICAMD_EAC_SIGNED_RG11;
     case ICAMD_CONTAINER_PKM:
       return codec == ICAMD_ETC1 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
-             codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1;
+             codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
+             codec == ICAMD_EAC_SIGNED_RG11;
     default: return false;
   }
 }
@@ -113,10 +117,11 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
                                 : codec == ICAMD_BC4 ? 0x8DBBu : codec == ICAMD_BC5 ? 0x8DBDu
                                 : codec == ICAMD_ETC2_RGBA8 ? 0x9278u : codec == ICAMD_ETC2_RGB8 ? 0x9274u
                                 : codec == ICAMD_EAC_R11 ? 0x9270u : codec == ICAMD_EAC_RG11 ? 0x9272u
+                                : codec == ICAMD_EAC_SIGNED_R11 ? 0x9271u : codec == ICAMD_EAC_SIGNED_RG11 ? 0x9273u
                                 : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : 0x8C03u;
       put_le32(out + 28, internal);
-      const uint32_t base = (codec == ICAMD_BC4 || codec == ICAMD_EAC_R11) ? 0x1903u                       // GL_RED
-                            : (codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11) ? 0x8227u                    // GL_RG
+      const uint32_t base = (codec == ICAMD_BC4 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 0x1903u     // GL_RED
+                            : (codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 0x8227u  // GL_RG
                             : (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2 || codec == ICAMD_ETC2_RGBA8 ||
                                codec == ICAMD_ETC2_RGB8A1) ? 0x1908u : 0x1907u;                           // GL_RGBA / GL_RGB
       put_le32(out + 32, base);
@@ -131,9 +136,10 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
     }
     case ICAMD_CONTAINER_PKM: {
       memcpy(out, codec == ICAMD_ETC1 ? "PKM 10" : "PKM 20", 6);
-      // ETC2_RGBA / ETC2_RGB / ETC2_RGBA1 / ETC2_R / ETC2_RG / ETC1_RGB _NO_MIPMAPS
+      // ETC2_RGBA / ETC2_RGB / ETC2_RGBA1 / ETC2_R / ETC2_RG / ETC2_R_SIGNED / ETC2_RG_SIGNED / ETC1_RGB _NO_MIPMAPS
       put_be16(out + 6, codec == ICAMD_ETC2_RGBA8 ? 3 : codec == ICAMD_ETC2_RGB8 ? 1 : codec == ICAMD_ETC2_RGB8A1 ? 4
-                        : codec == ICAMD_EAC_R11 ? 5 : codec == ICAMD_EAC_RG11 ? 6 : 0);
+                        : codec == ICAMD_EAC_R11 ? 5 : codec == ICAMD_EAC_RG11 ? 6 : codec == ICAMD_EAC_SIGNED_R11 ? 7
+                        : codec == ICAMD_EAC_SIGNED_RG11 ? 8 : 0);
       put_be16(out + 8, (width + 3u) & ~3u);       // encoded (block-aligned) size
       put_be16(out + 10, (height + 3u) & ~3u);
       put_be16(out + 12, width);                   // original size
@@ -145,10 +151,12 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 4, 0);        // flags
       put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u
                         : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_ETC2_RGBA8 ? 23u
-                        : codec == ICAMD_ETC2_RGB8 ? 22u : codec == ICAMD_ETC2_RGB8A1 ? 24u : codec == ICAMD_EAC_R11 ? 25u
-                        : codec == ICAMD_EAC_RG11 ? 26u : 11u);
+                        : codec == ICAMD_ETC2_RGB8 ? 22u : codec == ICAMD_ETC2_RGB8A1 ? 24u
+                        : (codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 25u
+                        : (codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 26u : 11u);
       put_le32(out + 16, 0);       // colour space: linear RGB
-      put_le32(out + 20, 0);       // channel type: unsigned byte, normalised
+      // channel type: 0 = unsigned byte, normalised; 1 = signed byte, normalised (what tells signed EAC from unsigned)
+      put_le32(out + 20, (codec == ICAMD_EAC_SIGNED_R11 || codec == ICAMD_EAC_SIGNED_RG11) ? 1u : 0u);
       put_le32(out + 24, height);
       put_le32(out + 28, width);
       put_le32(out + 32, 1);       // depth

@@ -45,9 +45,7 @@ ICAMD_DEV void decode_eac11(uint32_t w0, uint32_t w1, uint32_t rows[4]) {
     uint32_t sel = 0u;
     ICAMD_UNROLL
     for (int x = 0; x < 4; ++x) {
-      const int s = 45 - 3 * (4 * x + y);  // the index field's lowest bit in the 64-bit word
-      const uint32_t idx = (s >= 32 ? hi >> (s - 32) : s <= 29 ? lo >> s : alignbit(hi, lo, (uint32_t)s)) & 7u;
-      sel |= idx << (8 * x);
+      sel |= eac_index(hi, lo, 4 * x + y) << (8 * x);
     }
     rows[y] = perm(thi, tlo, sel);
   }

@@ -105,11 +105,10 @@ ICAMD_DEV uint32_t eac_sse(const uint32_t a[16], const int32_t v[8]) {
   return sse;
 }
 
-// The EAC word of the chosen (table t, multiplier m, base b): a[4 y + x] = alpha of texel (x, y).
-ICAMD_DEV Out8 eac_pack(const uint32_t a[16], uint32_t t, uint32_t m, uint32_t b) {
-  int32_t v[8];
-  eac_values(eac_mags(t & 15u), (int32_t)m, (int32_t)b, v);  // (t differs per lane here: per-lane shifts, once per block)
-  uint32_t hi = b << 24 | m << 20 | t << 16, lo = 0u;  // the 64-bit big-endian word as (hi, lo)
+// a[4 y + x] = the value of texel (x, y).  The word whose header bits (base, multiplier, table: bits 63..48) are `hi` and whose candidate values, in index order, are v:
+// every texel takes the smallest index that reaches its minimum.  a and v below 65536 (sad_u32).
+ICAMD_DEV Out8 eac_pack_values(const uint32_t a[16], const int32_t v[8], uint32_t hi) {
+  uint32_t lo = 0u;  // the 64-bit big-endian word as (hi, lo)
   ICAMD_UNROLL
   for (int x = 0; x < 4; ++x) {
     ICAMD_UNROLL
@@ -131,6 +130,18 @@ ICAMD_DEV Out8 eac_pack(const uint32_t a[16], uint32_t t, uint32_t m, uint32_t b
   }
   const Out8 o = { perm(0u, hi, 0x00010203u), perm(0u, lo, 0x00010203u) };  // big-endian words in memory
   return o;
+}
+// The EAC word of the chosen (table t, multiplier m, base b): a[4 y + x] = alpha of texel (x, y).
+ICAMD_DEV Out8 eac_pack(const uint32_t a[16], uint32_t t, uint32_t m, uint32_t b) {
+  int32_t v[8];
+  eac_values(eac_mags(t & 15u), (int32_t)m, (int32_t)b, v);  // (t differs per lane here: per-lane shifts, once per block)
+  return eac_pack_values(a, v, b << 24 | m << 20 | t << 16);
+}
+
+// The 3-bit index of texel i = 4 x + y (a constant at every call site) in the 64-bit big-endian word (hi, lo).
+ICAMD_DEV uint32_t eac_index(uint32_t hi, uint32_t lo, int i) {
+  const int s = 45 - 3 * i;  // the index field's lowest bit in the 64-bit word
+  return (s >= 32 ? hi >> (s - 32) : s <= 29 ? lo >> s : alignbit(hi, lo, (uint32_t)s)) & 7u;
 }
 
 // The alpha search.  a[4 y + x] = alpha of texel (x, y), each 0..255.
@@ -179,8 +190,7 @@ ICAMD_DEV void decode_eac_alpha(uint32_t w0, uint32_t w1, uint32_t px[16]) {
   for (int x = 0; x < 4; ++x) {
     ICAMD_UNROLL
     for (int y = 0; y < 4; ++y) {
-      const int s = 45 - 3 * (4 * x + y);
-      const uint32_t idx = (s >= 32 ? hi >> (s - 32) : s <= 29 ? lo >> s : alignbit(hi, lo, (uint32_t)s)) & 7u;
+      const uint32_t idx = eac_index(hi, lo, 4 * x + y);
       uint32_t al = (uint32_t)v[0];
       ICAMD_UNROLL
       for (int k = 1; k < 8; ++k) al = idx == (uint32_t)k ? (uint32_t)v[k] : al;

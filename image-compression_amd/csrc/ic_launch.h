@@ -172,6 +172,16 @@ const char *bc45_kernel_name(int codec, int comps);
 hipError_t launch_eac11_encode(int codec, int comps, const GridParams &P, hipStream_t stream);
 hipError_t launch_eac11_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
 const char *eac11_kernel_name(int codec, int comps);  // "" where launch_eac11_encode has no kernel
+// 16-bit and signed EAC R11 / RG11 (extension, eac11_16_kernels.hip): codec ICAMD_EAC_R11 / RG11 / SIGNED_R11 / SIGNED_RG11,
+// chans = 16-bit samples per source pixel, 1..4 (R11) / 2..4 (RG11).  Encode: GridParams (swap_rb and etc_strategy are not
+// read; addresses are 64-bit per lane, so force_gather is not either).  Decode: Bc45DecodeParams, uint16 / int16 rows of
+// row_stride bytes.  Metric: MetricParams as launch_metric (swap_rb and force_gather are not read); the records get sse[k] and
+// max_abs[k] of the 16-bit values, k = 0 (R) and 1 (G).
+hipError_t launch_eac11_16_encode(int codec, int chans, const GridParams &P, hipStream_t stream);
+hipError_t launch_eac11_16_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
+hipError_t launch_eac11_16_metric(int codec, int chans, const MetricParams &P, hipStream_t stream);
+const char *eac11_16_kernel_name(int codec, int chans);         // "" where launch_eac11_16_encode has no kernel
+const char *eac11_16_metric_kernel_name(int codec, int chans);  // "" where launch_eac11_16_metric has no kernel
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

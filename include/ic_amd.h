@@ -154,7 +154,8 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
        ICAMD_ETC2_RGB8 = 18,
        /* EXTENSION: EAC R11 (COMPRESSED_R11_EAC, one channel, 8 bytes per 4 x 4 block) and EAC RG11 (COMPRESSED_RG11_EAC, two
-        * channels, 16 bytes per block: the word of R, then the word of G), in the raster block order of ETC1.  Unsigned only.
+        * channels, 16 bytes per block: the word of R, then the word of G), in the raster block order of ETC1.  Unsigned,
+        * bytes in and out here; 16-bit samples and the signed formats: icamd_encode_eac11_16_device below.
         * They are to the ETC2 family what BC4 / BC5 are to DXT.  A word has the layout of the ETC2 RGBA8 alpha word: byte 0 =
         * base, byte 1 = multiplier << 4 | table, then sixteen 3-bit indices, big-endian, texel i = 4 x + y in bits
         * 47 - 3 i .. 45 - 3 i.
@@ -235,7 +236,17 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * container functions (KTX 0x9276 with GL_RGBA, PKM 2.0 type 4, PVR 24; no DDS) only: no Compressor + format pair selects
         * it, the mip entry points answer ICAMD_ERR_ARG and icamd_mip_chain_size 0.  Mip chains: reachable through
         * icamd_encode_etc2_mips_device, icamd_etc2_mip_chain_size, icamd_etc2_mip_workspace_size and icamd_etc2_mip_kernel_name. */
-       ICAMD_ETC2_RGB8A1 = 21 };
+       ICAMD_ETC2_RGB8A1 = 21,
+       /* EXTENSION: signed EAC R11 (COMPRESSED_SIGNED_R11_EAC, 8 bytes per 4 x 4 block) and signed EAC RG11
+        * (COMPRESSED_SIGNED_RG11_EAC, 16 bytes per block: the word of R, then the word of G).  The word layout is that of
+        * ICAMD_EAC_R11, with byte 0 a two's-complement base.  PARITY UNPINNED (the reference has no EAC).  Signed data is 16-bit in
+        * and out only: the codecs are reachable through icamd_encode_eac11_16_device, icamd_decode_eac11_16_device,
+        * icamd_measure_error_eac11_16_device (where decoding and the encoder's search are stated in full),
+        * icamd_eac11_16_kernel_name, icamd_eac11_16_metric_kernel_name, icamd_encoded_size and the container functions (KTX
+        * 0x9271 with GL_RED / 0x9273 with GL_RG, PKM 2.0 types 7 / 8, PVR formats 25 / 26 with the header's channel-type field
+        * = 1, signed byte normalised; no DDS).  Every other entry point refuses them as it refuses an unknown codec.
+        * Values 22 and 23 are unassigned. */
+       ICAMD_EAC_SIGNED_R11 = 24, ICAMD_EAC_SIGNED_RG11 = 25 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -862,6 +873,69 @@ int icamd_measure_error(int compressor, int format, uint32_t height, uint32_t wi
                         const uint8_t *buffer, const uint8_t *blocks, size_t blocks_size, icamd_error_stats *out);
 /* Name of the __global__ kernel icamd_measure_error_device launches for a configuration ("" if it refuses it). */
 const char *icamd_metric_kernel_name(int codec, int src_components);
+
+/* ---- 16-bit and signed EAC R11 / RG11 (EXTENSION, PARITY UNPINNED: the reference has no EAC) ----
+ * codec: ICAMD_EAC_R11, ICAMD_EAC_RG11 (unsigned, uint16 samples) or ICAMD_EAC_SIGNED_R11, ICAMD_EAC_SIGNED_RG11 (int16 samples).
+ * The words are EAC words (see ICAMD_EAC_R11); blocks in the raster order of ETC1, 8 (R11) / 16 (RG11: R's word, then G's) bytes.
+ * M is the modifier table of ICAMD_ETC2_RGBA8; s = (multiplier == 0 ? 1 : 8 multiplier).
+ *
+ * Decode to 16 bits (Khronos EAC).
+ *   Unsigned: v = clamp(8 base + 4 + M[table][index] * s, 0, 2047); out16 = v << 5 | v >> 6.
+ *   Signed: b = byte 0 as int8, with -128 read as -127; v = clamp(8 b + M[table][index] * s, -1023, 1023);
+ *           out16 = sign(v) * ((|v| << 5) + (|v| >> 5)), an int16 in -32767 .. 32767.
+ *   Known answers, the word 80 0d 7e 49 24 92 49 24.  Read unsigned (base 128, multiplier 0, table 13, indices 3, 7, 4, 4, ...):
+ *   v = 1018, 1037, 1028, ... and out16 = 32591, 33200, 32912, ...  Read signed (base -128 -> -127): v = -1023 (clamped), -1007,
+ *   -1016, ... and out16 = -32767, -32255, -32543, ...  Signed base 127, multiplier 15, table 0, index 7 clamps to 1023 -> 32767.
+ *
+ * Encode from 16-bit samples, a DEFINITION, in the 11-bit domain (restated in numpy in tests/eac11_16_oracle.py; the kernels are
+ * bit-exact against it).  The source has src_channels (1..4) little-endian 16-bit samples per pixel, R = sample 0, G = sample 1
+ * (RG needs at least 2; there is no swap).  Grids, clamp-to-edge replication, the padded-grid fetch, strides and batches as for
+ * ICAMD_EAC_R11 through icamd_encode_device.  Per channel and block:
+ *   target per texel: a = u16 >> 5 (unsigned); with x = max(s16, -32767), a = sign(x) * (|x| >> 5) (signed);
+ *   lo, hi = the smallest and largest a, R = hi - lo; span[t] = M[t][7] - M[t][3]; (Vmin, Vmax) = (0, 2047) unsigned,
+ *   (-1023, 1023) signed;
+ *   candidates, in this order, replacing the best on a STRICTLY smaller sse only:
+ *     for table t = 0..15, with m0 = (2 R + 8 span[t]) / (16 span[t]) (truncating):
+ *       for m in (0, clamp(m0 - 1, 1, 15), clamp(m0, 1, 15), clamp(m0 + 1, 1, 15)):
+ *           s = (m == 0 ? 1 : 8 m), c2 = lo + hi + s, b0 = c2 >> 4 (unsigned) or (c2 + 8) >> 4 (signed; arithmetic shift: floor);
+ *         for b in b0 - 1, b0, b0 + 1, each clamped to 0..255 (unsigned) or -127..127 (signed):
+ *           v_k = clamp(B + M[t][k] s, Vmin, Vmax) with B = 8 b + 4 (unsigned) or 8 b (signed); every texel takes the smallest
+ *           k minimising |a - v_k|; sse = the sum of the squared minima (at most 16 * 2047^2 < 2^27).
+ *   That is 192 candidates (duplicates after clamping are harmless).  The word is (b, m, t) of the best candidate and its
+ *   texels' indices.  Multiplier 0 IS written (its modifier steps are 1/8 of multiplier 1's: smooth content).  The signed encoder
+ *   never writes base -128. */
+/* icamd_encode_eac11_16_device: arguments as icamd_encode_device without etc_strategy and swap_rb.  Status, in this order:
+ * ICAMD_FALSE for a null pointer or height or width 0; ICAMD_ERR_ARG for a codec other than the four, src_channels outside
+ * 1..4 (R11) / 2..4 (RG11), or an odd d_src, row_stride_bytes or src_image_stride_bytes (samples are 2-byte aligned);
+ * ICAMD_OK for n_images == 0; ICAMD_ERR_ARG for row_stride_bytes < width * src_channels * 2.  All answered before a device is
+ * needed.  d_dst: any alignment, icamd_encoded_size(codec, grid) bytes per image.  No allocation, no synchronisation. */
+int icamd_encode_eac11_16_device(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t grid_height,
+                                 uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                 size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                 const void *d_src, void *d_dst, void *hip_stream);
+/* icamd_decode_eac11_16_device: arguments as icamd_decode_device without swap_rb.  Writes `height` rows of width * 2 (R11) /
+ * width * 4 (RG11: R then G per pixel) + padding_bytes_per_row bytes, samples uint16 (unsigned codecs) or int16 (signed),
+ * little-endian; padding bytes are left alone.  ICAMD_FALSE for a null pointer or an empty image; ICAMD_ERR_ARG for a codec
+ * other than the four, an odd padding_bytes_per_row, d_pixels or dst_image_stride_bytes, or a row of 2^32 bytes or more;
+ * ICAMD_OK for n_images == 0.  d_blocks: any alignment.  No allocation, no synchronisation. */
+int icamd_decode_eac11_16_device(int codec, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row, uint32_t n_images,
+                                 size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                 const void *d_blocks, void *d_pixels, void *hip_stream);
+/* icamd_measure_error_eac11_16_device: arguments as icamd_measure_error_device with src_channels for src_components and no
+ * swap_rb; fills n_images icamd_error_stats records.  sse[k] and max_abs[k], k = 0 (R) and 1 (G, RG11 only), compare the
+ * decoder's 16-bit value with the 16-bit source sample AS STORED (not with its 11-bit target), over the pixels inside the
+ * image; the other entries are 0.  ICAMD_FALSE for a null pointer or an empty image; ICAMD_ERR_ARG for a codec other than the
+ * four, src_channels the encoder refuses, an odd d_src, row_stride_bytes or src_image_stride_bytes, a row stride smaller than
+ * a row, a grid smaller than the image, a d_stats that is not 8-byte aligned, or (uint64)height * width > 2^31 (a squared
+ * difference is below 2^32, so every sum stays below 2^63); ICAMD_OK for n_images == 0.  All answered before a device is
+ * needed.  No allocation and no synchronisation (the zeroing of d_stats is stream-ordered work of the call). */
+int icamd_measure_error_eac11_16_device(int codec, int src_channels, uint32_t height, uint32_t width,
+                                        uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                        size_t src_image_stride_bytes, size_t blocks_image_stride_bytes,
+                                        const void *d_src, const void *d_blocks, void *d_stats, void *hip_stream);
+/* Names of the __global__ kernels the two launch for a configuration ("" where they refuse it). */
+const char *icamd_eac11_16_kernel_name(int codec, int src_channels);
+const char *icamd_eac11_16_metric_kernel_name(int codec, int src_channels);
 
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
