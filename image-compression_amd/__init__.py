@@ -63,6 +63,10 @@ ETC2_RGB8A1 = 21
 # EXTENSION (include/ic_amd.h ICAMD_EAC_SIGNED_R11): signed EAC R11 / RG11, 8 / 16 bytes per block, int16 samples in and out.
 # encode_eac11_16_device / decode_eac11_16_device / measure_error_eac11_16_device / containers only (22 and 23 are unassigned)
 EAC_SIGNED_R11, EAC_SIGNED_RG11 = 24, 25
+# EXTENSION (include/ic_amd.h ICAMD_BC7): BC7 / BPTC, 16 bytes per block.  The decoder and the metric read all eight modes; the
+# encoder writes mode 6 from 3- or 4-byte pixels (a definition stated in the header).  encode_device / decode_device (RGBA8 rows)
+# / measure_error_device / encode_batch_sharded_device / containers only (26..31 are unassigned)
+BC7 = 32
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -268,7 +272,7 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     _assert_u8_cuda(blocks)
     # BC4 and EAC_R11 -> R8, BC5 and EAC_RG11 -> RG8
-    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, ETC2_RGB8A1: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, ETC2_RGB8A1: 4, BC7: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

@@ -5,19 +5,20 @@
 // dimensions only), so there is NOTHING in the reference to pin these against: parity unpinned by construction.  The
 // layouts below are written from the public file-format descriptions:
 //   * DDS  -- "DDS " magic + 124-byte DDS_HEADER with a FOURCC pixel format (DXT1 / DXT5, and ATI1 / ATI2 for BC4 / BC5;
-//             the legacy header has no code for ETC1 or PVRTC);
+//             the legacy header has no code for ETC1 or PVRTC); BC7: FOURCC "DX10" followed by the 20-byte DDS_HEADER_DXT10
+//             (dxgiFormat 98 = DXGI_FORMAT_BC7_UNORM, resourceDimension 3 = TEXTURE2D, miscFlag 0, arraySize 1, miscFlags2 0);
 //   * KTX  -- KTX 1.1: 12-byte identifier, 13 little-endian uint32 fields, then per mip level uint32 imageSize + data
 //             (glInternalFormat: COMPRESSED_RGB_S3TC_DXT1_EXT 0x83F0, COMPRESSED_RGBA_S3TC_DXT5_EXT 0x83F3,
 //             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03, COMPRESSED_RED_RGTC1 0x8DBB with base format
 //             GL_RED, COMPRESSED_RG_RGTC2 0x8DBD with base format GL_RG, COMPRESSED_RGBA8_ETC2_EAC 0x9278 with GL_RGBA,
 //             COMPRESSED_R11_EAC 0x9270 with GL_RED, COMPRESSED_RG11_EAC 0x9272 with GL_RG,
 //             COMPRESSED_SIGNED_R11_EAC 0x9271 with GL_RED, COMPRESSED_SIGNED_RG11_EAC 0x9273 with GL_RG,
-//             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA);
+//             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA, COMPRESSED_RGBA_BPTC_UNORM 0x8E8C with GL_RGBA);
 //   * PKM  -- 16-byte big-endian header, exactly one level: "PKM 10" with type 0 for ETC1, "PKM 20" with type 3
 //             (ETC2_RGBA_NO_MIPMAPS) for ETC2 RGBA8, type 4 (ETC2_RGBA1_NO_MIPMAPS) for ETC2 RGB8A1, type 5 / 6 (ETC2_R /
 //             ETC2_RG _NO_MIPMAPS) for EAC R11 / RG11, type 7 / 8 (ETC2_R_SIGNED / ETC2_RG_SIGNED _NO_MIPMAPS) for the signed two;
 //   * PVR  -- PVR v3: 52-byte little-endian header (pixel format 1 = PVRTC 2bpp RGBA, 6 = ETC1, 7 = DXT1, 11 = DXT5,
-//             12 = BC4, 13 = BC5, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11; signed EAC R11 / RG11 are
+//             12 = BC4, 13 = BC5, 15 = BC7, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11; signed EAC R11 / RG11 are
 //             formats 25 / 26 with the channel-type field 1, signed byte normalised, where every other codec has 0),
 //             no metadata, levels follow largest first.  PVRTC data is stored in the Z-order the encoder already
 //             produces (pvrtc_compressor.cc:551-580).
@@ -46,9 +47,9 @@ inline void put_be16(uint8_t *p, uint32_t v) {
   p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v;
 }
 
-inline size_t container_header_size(int container) {
+inline size_t container_header_size(int container, int codec) {
   switch (container) {
-    case ICAMD_CONTAINER_DDS: return 128;
+    case ICAMD_CONTAINER_DDS: return codec == ICAMD_BC7 ? 148 : 128;  // BC7: + DDS_HEADER_DXT10
     case ICAMD_CONTAINER_KTX: return 64;
     case ICAMD_CONTAINER_PKM: return 16;
     case ICAMD_CONTAINER_PVR: return 52;
@@ -58,13 +59,14 @@ inline size_t container_header_size(int container) {
 
 inline bool container_supports(int container, int codec) {
   switch (container) {
-    case ICAMD_CONTAINER_DDS: return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5;
+    case ICAMD_CONTAINER_DDS:
+      return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_BC7;
     case ICAMD_CONTAINER_KTX:
     case ICAMD_CONTAINER_PVR:
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
              codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
              codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
-             codec == ICAMD_EAC_SIGNED_RG11;
+             codec == ICAMD_EAC_SIGNED_RG11 || codec == ICAMD_BC7;
     case ICAMD_CONTAINER_PKM:
       return codec == ICAMD_ETC1 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
              codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
@@ -87,10 +89,10 @@ inline size_t container_level_bytes(int codec, uint32_t height, uint32_t width, 
 // framing bytes in front of every level (KTX: the uint32 imageSize)
 inline size_t container_level_prefix(int container) { return container == ICAMD_CONTAINER_KTX ? 4 : 0; }
 
-// Writes the header of `container` into out (container_header_size bytes).  level0_bytes = size of the first level.
+// Writes the header of `container` for `codec` into out (container_header_size bytes).  level0_bytes = size of the first level.
 inline void container_write_header(int container, int codec, uint32_t height, uint32_t width, uint32_t levels,
                                    size_t level0_bytes, uint8_t *out) {
-  memset(out, 0, container_header_size(container));
+  memset(out, 0, container_header_size(container, codec));
   switch (container) {
     case ICAMD_CONTAINER_DDS: {
       memcpy(out, "DDS ", 4);
@@ -102,8 +104,16 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 28, levels);                                                        // dwMipMapCount
       put_le32(out + 76, 32);                                                            // ddspf.dwSize
       put_le32(out + 80, 0x4u);                                                          // DDPF_FOURCC
-      memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1" : "ATI2", 4);
+      memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1"
+                       : codec == ICAMD_BC5 ? "ATI2" : "DX10", 4);
       put_le32(out + 108, 0x1000u | (levels > 1 ? 0x8u | 0x400000u : 0u));               // DDSCAPS_TEXTURE [COMPLEX MIPMAP]
+      if (codec == ICAMD_BC7) {  // DDS_HEADER_DXT10
+        put_le32(out + 128, 98);  // dxgiFormat: DXGI_FORMAT_BC7_UNORM
+        put_le32(out + 132, 3);   // resourceDimension: D3D10_RESOURCE_DIMENSION_TEXTURE2D
+        put_le32(out + 136, 0);   // miscFlag
+        put_le32(out + 140, 1);   // arraySize
+        put_le32(out + 144, 0);   // miscFlags2: alpha mode unknown
+      }
       break;
     }
     case ICAMD_CONTAINER_KTX: {
@@ -118,12 +128,12 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
                                 : codec == ICAMD_ETC2_RGBA8 ? 0x9278u : codec == ICAMD_ETC2_RGB8 ? 0x9274u
                                 : codec == ICAMD_EAC_R11 ? 0x9270u : codec == ICAMD_EAC_RG11 ? 0x9272u
                                 : codec == ICAMD_EAC_SIGNED_R11 ? 0x9271u : codec == ICAMD_EAC_SIGNED_RG11 ? 0x9273u
-                                : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : 0x8C03u;
+                                : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : codec == ICAMD_BC7 ? 0x8E8Cu : 0x8C03u;
       put_le32(out + 28, internal);
       const uint32_t base = (codec == ICAMD_BC4 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 0x1903u     // GL_RED
                             : (codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 0x8227u  // GL_RG
                             : (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2 || codec == ICAMD_ETC2_RGBA8 ||
-                               codec == ICAMD_ETC2_RGB8A1) ? 0x1908u : 0x1907u;                           // GL_RGBA / GL_RGB
+                               codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_BC7) ? 0x1908u : 0x1907u;                           // GL_RGBA / GL_RGB
       put_le32(out + 32, base);
       put_le32(out + 36, width);
       put_le32(out + 40, height);
@@ -150,7 +160,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out, 0x03525650u);  // "PVR\3"
       put_le32(out + 4, 0);        // flags
       put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u
-                        : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_ETC2_RGBA8 ? 23u
+                        : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_BC7 ? 15u
+                        : codec == ICAMD_ETC2_RGBA8 ? 23u
                         : codec == ICAMD_ETC2_RGB8 ? 22u : codec == ICAMD_ETC2_RGB8A1 ? 24u
                         : (codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 25u
                         : (codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 26u : 11u);

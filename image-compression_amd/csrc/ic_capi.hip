@@ -220,10 +220,10 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr,
 
 // Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 /
 // ETC2 RGB8A1 4,
-// BC4 and EAC R11 1..4, BC5 and EAC RG11 2..4.
+// BC4 and EAC R11 1..4, BC5 and EAC RG11 2..4, BC7 3 or 4.
 bool codec_accepts_components(int codec, int comps) {
   switch (codec) {
-    case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: return comps == 3 || comps == 4;
+    case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: case ICAMD_BC7: return comps == 3 || comps == 4;
     case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: case ICAMD_ETC2_RGB8A1: return comps == 4;
     case ICAMD_BC4: case ICAMD_EAC_R11: return comps >= 1 && comps <= 4;
     case ICAMD_BC5: case ICAMD_EAC_RG11: return comps >= 2 && comps <= 4;
@@ -491,6 +491,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_PVRTC4: return icamd::pvrtc4_kernel_name();
     case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
     case ICAMD_EAC_R11: case ICAMD_EAC_RG11: return icamd::eac11_kernel_name(codec, src_components);
+    case ICAMD_BC7: return icamd::bc7_kernel_name(src_components);
   }
   return "";
 }
@@ -540,7 +541,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     return pvrtc_encode_device_impl(codec, src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
                                     dst_image_stride_bytes, d_src, d_dst, stream, false);
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
-      codec != ICAMD_ETC2_RGB8A1)
+      codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7)
     return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!codec_accepts_components(codec, src_components)) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
   if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
@@ -555,6 +556,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     ICAMD_HIP(icamd::launch_etc2_rgb8(src_components, P, stream), "launch etc2 rgb8");
   else if (codec == ICAMD_ETC2_RGB8A1)
     ICAMD_HIP(icamd::launch_etc2_a1(P, stream), "launch etc2 rgb8a1");
+  else if (codec == ICAMD_BC7)  // EXTENSION (include/ic_amd.h ICAMD_BC7): mode 6 from 3- or 4-component sources
+    ICAMD_HIP(icamd::launch_bc7_encode(src_components, P, stream), "launch bc7");
   else
     ICAMD_HIP(icamd::launch_dxt(codec, src_components, P, stream), "launch dxt");
   return ICAMD_OK;
@@ -585,6 +588,7 @@ int icamd_encode_etc2_device(int codec, int etc_strategy, int etc2_modes, int sr
 } ICAMD_ABI_CATCH
 
 const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes) {
+  if (codec == ICAMD_BC7) return "";  // (as for an unknown codec: not an ETC2-family codec, include/ic_amd.h ICAMD_BC7)
   if (etc2_modes == ICAMD_ETC2_MODES_DEFAULT) return icamd_kernel_name(codec, src_components);
   if (etc2_modes == ICAMD_ETC2_MODES_TH && codec == ICAMD_ETC2_RGB8) return icamd::etc2_th_kernel_name(src_components);
   return "";
@@ -635,6 +639,7 @@ int icamd_encode_etc2_colour_device(int codec, int etc_strategy, int colour_mode
 } ICAMD_ABI_CATCH
 
 const char *icamd_etc2_colour_kernel_name(int codec, int src_components, int colour_modes) {
+  if (codec == ICAMD_BC7) return "";  // (as for an unknown codec)
   if (colour_modes == ICAMD_ETC2_COLOUR_DEFAULT) return icamd_kernel_name(codec, src_components);
   if ((colour_modes != ICAMD_ETC2_COLOUR_PLANAR && colour_modes != ICAMD_ETC2_COLOUR_PLANAR_TH) ||
       !etc2_colour_accepts(codec, src_components))
@@ -853,6 +858,8 @@ static int decode_launch(int codec, int swap_rb, uint32_t height, uint32_t width
     ICAMD_HIP(icamd::launch_etc2_rgb8_decode(P, stream), "launch etc2 rgb8 decode");
   else if (codec == ICAMD_ETC2_RGB8A1)
     ICAMD_HIP(icamd::launch_etc2_a1_decode(P, stream), "launch etc2 rgb8a1 decode");
+  else if (codec == ICAMD_BC7)
+    ICAMD_HIP(icamd::launch_bc7_decode(P, stream), "launch bc7 decode");
   else
     ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
   return ICAMD_OK;
@@ -864,7 +871,7 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
   const bool plane = plane_codec(codec);  // (BC4 / BC5 and EAC R11 / RG11: R8 / RG8 rows)
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 &&
-      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1 && !plane)
+      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7 && !plane)
     return ICAMD_FALSE;
   if (plane && swap_rb) return fail(ICAMD_ERR_ARG, eac11_codec(codec) ? "EAC R11 / RG11 decode: swap_rb must be 0" : "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
@@ -900,7 +907,7 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     swap_rb = 0;
   }
   const uint32_t block_bytes = icamd::codec_block_bytes(codec);
-  const bool rgba_rows = codec == ICAMD_DXT5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8A1 || pvrtc;
+  const bool rgba_rows = codec == ICAMD_DXT5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_BC7 || pvrtc;
   const uint32_t row_stride = width * (rgba_rows ? 4u : 3u) + padding_bytes_per_row;
   const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
   const uint64_t kMaxBlocks = (1ull << 31) - 1;
@@ -1695,7 +1702,7 @@ size_t icamd_container_size(int container, int codec, uint32_t height, uint32_t 
   if (!container_supports(container, codec) || height == 0 || width == 0 || levels == 0 || levels > 32) return 0;
   if (container == ICAMD_CONTAINER_PKM && (levels != 1 || height > 65532u || width > 65532u)) return 0;
   if (codec == ICAMD_PVRTC2 && (height != width || !is_pow2(width))) return 0;
-  size_t total = container_header_size(container);
+  size_t total = container_header_size(container, codec);
   for (uint32_t l = 0; l < levels; ++l) {
     if (l > 0 && (height >> l) == 0 && (width >> l) == 0) return 0;  // past the 1 x 1 level
     const size_t b = container_level_bytes(codec, height, width, l);
@@ -1710,7 +1717,8 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
   using namespace icamd;
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
   if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
-                             codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_EAC_SIGNED_R11 && codec != ICAMD_EAC_SIGNED_RG11))
+                             codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_EAC_SIGNED_R11 && codec != ICAMD_EAC_SIGNED_RG11 &&
+                             codec != ICAMD_BC7))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);
@@ -1718,7 +1726,7 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
   for (uint32_t l = 0; l < levels; ++l)
     if (!level_data[l] || level_sizes[l] != container_level_bytes(codec, height, width, l)) return ICAMD_FALSE;
   container_write_header(container, codec, height, width, levels, level_sizes[0], out);
-  uint8_t *p = out + container_header_size(container);
+  uint8_t *p = out + container_header_size(container, codec);
   for (uint32_t l = 0; l < levels; ++l) {
     if (container_level_prefix(container)) {
       put_le32(p, (uint32_t)level_sizes[l]);  // KTX imageSize; block streams are multiples of 8 bytes: no mip padding

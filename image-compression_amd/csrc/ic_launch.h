@@ -182,6 +182,11 @@ hipError_t launch_eac11_16_decode(int codec, uint32_t n_images, const Bc45Decode
 hipError_t launch_eac11_16_metric(int codec, int chans, const MetricParams &P, hipStream_t stream);
 const char *eac11_16_kernel_name(int codec, int chans);         // "" where launch_eac11_16_encode has no kernel
 const char *eac11_16_metric_kernel_name(int codec, int chans);  // "" where launch_eac11_16_metric has no kernel
+// BC7 (extension, bc7_kernels.hip).  Encode (mode 6): GridParams as for DXT5 (etc_strategy is not read), comps 3 or 4.  Decode
+// (all eight modes): DecodeParams as launch_decode, RGBA8 rows.  The metric kernels are launch_metric's.
+hipError_t launch_bc7_encode(int comps, const GridParams &P, hipStream_t stream);
+hipError_t launch_bc7_decode(const DecodeParams &P, hipStream_t stream);
+const char *bc7_kernel_name(int comps);  // "" unless comps is 3 or 4
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

@@ -15,6 +15,7 @@
 #define ICAMD_METRIC_BLOCK_H_
 
 #include "bc45_block.h"  // blockops_block.h (decode_block_rows), decode_block.h, dxt_block.h (packed 16-bit helpers)
+#include "bc7_block.h"  // decode_bc7
 #include "eac11_block.h"  // decode_eac11
 #include "etc2_a1_block.h"  // decode_etc2_a1
 #include "etc2_block.h"  // decode_etc2_rgba8, decode_etc2_colour
@@ -175,6 +176,26 @@ ICAMD_DEV void metric_etc2_a1_block(const uint32_t *w, bool swap, const uint8_t 
   }
   ICAMD_UNROLL
   for (int y = 0; y < 4; ++y) metric_row4<4>(&S[4 * y], &D[4 * y], a);
+}
+
+// BC7 block `w` (EXTENSION: any of the eight modes, or the reserved form) against the COMPS-byte source pixels with the decoder's
+// own math (decode_bc7, swap included): four channels for COMPS = 4, R, G, B for COMPS = 3; a pixel outside the image compares
+// with itself.  PRECONDITION row < h, col < wd.
+template <int COMPS>
+ICAMD_DEV void metric_bc7_block(const uint32_t *w, bool swap, const uint8_t *img, uint32_t h, uint32_t wd, uint32_t stride,
+                                uint32_t row, uint32_t col, bool wide_ok, MetricAcc &a) {
+  uint32_t S[16], D[16];
+  load_block<COMPS>(img, h, wd, stride, row, col, S, wide_ok);
+  decode_bc7(w, swap, D);
+  if (row + 4 > h || col + 4 > wd) {
+    ICAMD_UNROLL
+    for (int y = 0; y < 4; ++y)
+      ICAMD_UNROLL
+      for (int x = 0; x < 4; ++x)
+        if (row + (uint32_t)y >= h || col + (uint32_t)x >= wd) S[4 * y + x] = D[4 * y + x];
+  }
+  ICAMD_UNROLL
+  for (int y = 0; y < 4; ++y) metric_row4<COMPS>(&S[4 * y], &D[4 * y], a);
 }
 
 // Channel `ch` of the COMPS-byte pixels of the block at (row, col), clamped to the image: r[y] byte x = pixel (x, y).

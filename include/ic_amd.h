@@ -246,7 +246,47 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * 0x9271 with GL_RED / 0x9273 with GL_RG, PKM 2.0 types 7 / 8, PVR formats 25 / 26 with the header's channel-type field
         * = 1, signed byte normalised; no DDS).  Every other entry point refuses them as it refuses an unknown codec.
         * Values 22 and 23 are unassigned. */
-       ICAMD_EAC_SIGNED_R11 = 24, ICAMD_EAC_SIGNED_RG11 = 25 };
+       ICAMD_EAC_SIGNED_R11 = 24, ICAMD_EAC_SIGNED_RG11 = 25,
+       /* EXTENSION: BC7 (BPTC, COMPRESSED_RGBA_BPTC_UNORM, DXGI_FORMAT_BC7_UNORM = 98): 16 bytes per 4 x 4 block, blocks in raster
+        * order as DXT.  PARITY UNPINNED (the reference has no BC7).  Values 26..31 are unassigned.
+        *   Decode (icamd_decode_device, RGBA8 rows, padding / batches / strides / swap_rb as ICAMD_DXT5): all eight modes of the
+        *       BPTC specification -- both partition tables, the anchor tables, unique and shared p-bits, endpoint expansion
+        *       (v << (8 - bits) | v >> (2 bits - 8)), the 2 / 3 / 4-bit weights {0,21,43,64}, {0,9,18,27,37,46,55,64},
+        *       {0,4,9,13,17,21,26,30,34,38,43,47,51,55,60,64} with ((64 - w) e0 + w e1 + 32) >> 6, rotation and index selection of
+        *       modes 4 / 5, alpha 255 in modes 0-3.  Texel i = 4 y + x.  A block whose byte 0 is 0 (reserved) decodes to sixteen
+        *       (0, 0, 0, 0) texels.
+        *   Metric (icamd_measure_error_device, src_components 3 or 4): the decoder's texels against the source, four channels
+        *       for RGBA8 sources, R, G, B for RGB888 sources; records, padded grids and batches as ICAMD_DXT5.
+        *   Encode (icamd_encode_device; src_components 3 or 4, else ICAMD_ERR_ARG; etc_strategy is not read): a DEFINITION that
+        *       writes MODE 6 only (one subset, 7-bit endpoints + one p-bit each, 4-bit indices).  The sixteen texels
+        *       v_p = (R, G, B, A), p = 4 y + x, are those ICAMD_DXT5's block routine is handed (clamp-to-edge replication, the
+        *       same fetch for blocks of a padded grid; swap_rb exchanges bytes 0 and 2); A = 255 for 3-component sources.
+        *       w_k, k = 0..15, are the 4-bit weights above.
+        *       1. Targets.  Per channel lo_c = min_p v_p[c], hi_c = max_p v_p[c]; c* = the channel with the largest hi - lo
+        *          (ties: R before G before B before A); T0 = lo, T1 = hi; for every c != c*, with
+        *          cov_c = 16 sum_p v_p[c*] v_p[c] - (sum_p v_p[c*]) (sum_p v_p[c]): T0_c and T1_c are exchanged if cov_c < 0.
+        *       2. Quantising an endpoint T -> E.  For p in {0, 1}: q_c(p) = clamp((T_c - p + 1) >> 1, 0, 127),
+        *          err(p) = sum_c (2 q_c(p) + p - T_c)^2; p = the one with the smaller err (ties: 0), shared by the four channels;
+        *          E_c = 2 q_c(p) + p.  E0 = Q(T0), E1 = Q(T1).
+        *       3. Indices.  pal_k[c] = ((64 - w_k) E0[c] + w_k E1[c] + 32) >> 6; texel p takes the smallest k that minimises
+        *          sum_c (pal_k[c] - v_p[c])^2; sse = the sum of the sixteen minima.
+        *       4. One least-squares refit.  With w = w_{k_p} of step 3: a = sum (64 - w)^2, b = sum (64 - w) w, c = sum w^2,
+        *          per channel X = sum (64 - w) v_p, Y = sum w v_p, det = a c - b^2.  If det = 0 there is no refit.  Otherwise
+        *          T0'_c = clamp(rdiv(64 (c X - b Y), det), 0, 255), T1'_c = clamp(rdiv(64 (a Y - b X), det), 0, 255) with
+        *          rdiv(n, d) = floor((2 n + d) / (2 d)) (exact integers: the products need 64 bits); steps 2 and 3 run on T', and
+        *          their (E0, E1, k, sse) replace the first pass's only if the new sse is STRICTLY smaller -- so no block's error
+        *          exceeds its first pass's.
+        *       5. Anchor.  If k_0 >= 8: E0 and E1 are exchanged (their p-bits with them) and every k becomes 15 - k (the weights
+        *          are symmetric, w_{15-k} = 64 - w_k: the decoded texels do not change).
+        *       6. Pack, least significant bit first: bits 0..5 = 0, bit 6 = 1; R0, R1, G0, G1, B0, B1, A0, A1 (q, 7 bits each);
+        *          P0, P1; k_0 in 3 bits; k_1..k_15 in 4 bits each.
+        *       Example: sixteen texels (10, 20, 30, 255) give c0 42 41 a1 78 3c fe 7f 00 .. 00 (T0 = T1 = v; p = 0 at err 1
+        *       against p = 1 at err 3; every k = 0; a = 65536, b = c = 0: det = 0).
+        * Reachable through icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device,
+        * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
+        * (DDS with the DX10 extension header, dxgiFormat 98; KTX 0x8E8C with GL_RGBA; PVR 15; no PKM) only: no Compressor + format
+        * pair selects it; the mip, ETC2-specific and 16-bit EAC entry points answer as for an unknown codec. */
+       ICAMD_BC7 = 32 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -665,7 +705,9 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
  * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
  * PVRTC2, BC4, BC5, ETC2 RGBA8, ETC2 RGB8, ETC2 RGB8A1), PKM (ETC1 as "PKM 10" type 0, ETC2 RGB8 / RGBA8 / RGB8A1 as "PKM 20" type 1 / 3 / 4;
- * one level).  PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
+ * one level).  ICAMD_BC7: DDS with the DX10 extension header (FourCC "DX10" + DDS_HEADER_DXT10, dxgiFormat 98; 148 header bytes
+ * where the other codecs have 128), KTX 0x8E8C with GL_RGBA, PVR 15, no PKM.  The signed EAC codecs: see their values.
+ * PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
  * icamd_compress / icamd_downsample return for that size (PVRTC: square power-of-two levels of 8 x 8 and up only). */
 enum { ICAMD_CONTAINER_DDS = 0, ICAMD_CONTAINER_KTX = 1, ICAMD_CONTAINER_PKM = 2, ICAMD_CONTAINER_PVR = 3 };
