@@ -326,14 +326,16 @@ struct TileCoord {
 // row-dependent quantity is workgroup-uniform as well.
 // WIDE_ROWS > 1: the workgroup covers WIDE_ROWS block rows and every lane encodes WIDE_ROWS vertically adjacent blocks
 // (the returned coordinate is the first one; the caller steps brow0 / brow).
+// WIDE_COLS = 64: the workgroup is ONE wave and covers a quarter of a 256-block tile (launch_tiled's wave_workgroups; the DXT
+// kernels, dxt_kernels.hip): tile_col counts 64-block pieces, and full / interior are the wave's own.
 // tile_col: the tile column this workgroup takes (blockIdx.x, unless the kernel deals the columns out differently)
 // tile_row, img: the tile row and the image, for kernels whose grid is not (column tiles, row tiles, images) -- the chain kernels
 // of etc2_mip_kernels.hip, which find level, tile and image of a workgroup in a table; every other kernel takes them from
 // blockIdx.y (+ tile_row0) and blockIdx.z through the overloads below
-template <bool WIDE, uint32_t WIDE_ROWS = 1>
+template <bool WIDE, uint32_t WIDE_ROWS = 1, uint32_t WIDE_COLS = 256>
 __device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t tile_col, uint32_t tile_row, uint32_t img) {
   TileCoord t;
-  const uint32_t cols = WIDE ? 256u : 1u << P.log2_tile_cols, rows = WIDE ? WIDE_ROWS : 256u >> P.log2_tile_cols;
+  const uint32_t cols = WIDE ? WIDE_COLS : 1u << P.log2_tile_cols, rows = WIDE ? WIDE_ROWS : 256u >> P.log2_tile_cols;
   t.lx = WIDE ? threadIdx.x : threadIdx.x & (cols - 1u);
   t.ly = WIDE ? 0u : threadIdx.x >> P.log2_tile_cols;
   t.bcol0 = tile_col * cols;
@@ -346,13 +348,13 @@ __device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t t
   t.valid = t.full || (t.bcol < P.block_cols && t.brow < P.block_rows);
   return t;
 }
-template <bool WIDE, uint32_t WIDE_ROWS = 1>
+template <bool WIDE, uint32_t WIDE_ROWS = 1, uint32_t WIDE_COLS = 256>
 __device__ __forceinline__ TileCoord locate_tile(const GridParams &P, uint32_t tile_col) {
-  return locate_tile<WIDE, WIDE_ROWS>(P, tile_col, blockIdx.y + P.tile_row0, blockIdx.z);
+  return locate_tile<WIDE, WIDE_ROWS, WIDE_COLS>(P, tile_col, blockIdx.y + P.tile_row0, blockIdx.z);
 }
-template <bool WIDE, uint32_t WIDE_ROWS = 1>
+template <bool WIDE, uint32_t WIDE_ROWS = 1, uint32_t WIDE_COLS = 256>
 __device__ __forceinline__ TileCoord locate_tile(const GridParams &P) {
-  return locate_tile<WIDE, WIDE_ROWS>(P, blockIdx.x);
+  return locate_tile<WIDE, WIDE_ROWS, WIDE_COLS>(P, blockIdx.x);
 }
 // locate_tile<false> for lane `tid` of the workgroup: for kernels that derive the coordinate a second time from the hardware's
 // lane index instead of holding it in registers (etc2_rgb8_kernels.hip, etc2_a1_kernels.hip).

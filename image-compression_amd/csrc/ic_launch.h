@@ -2,8 +2,8 @@
 // (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip, blockops_kernels.hip); called by ic_capi.hip.
 // Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC), blockops_plan.h (Pad, Downsample and
 // the chunks of CopySubimage, CreateSolid and the transcode), mip_plan.h (the passes, grids and kernels of the mip chains) and
-// etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape); the
-// launchers here run what a plan says.
+// etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape) and
+// dxt_plan.h (the workgroup size of the DXT encoders); the launchers here run what a plan says.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -46,7 +46,7 @@ inline uint32_t device_compute_units(int dev) {
 // worse coalescing, but the lanes of a wave see more homogeneous content, which is what wave-uniform shortcuts need.
 template <typename Kernel>
 // wave_workgroups: every wave of a tile is launched as its own 64-lane workgroup (grid.x = 4 x column tiles; the kernel
-// undoes it: etc1_locate_tile)
+// undoes it: etc1_locate_tile; the wide DXT1 <- RGBA8 kernels, which dxt_plan.h gives this form: locate_tile<true, 1, 64>)
 hipError_t launch_tiled(Kernel wide_kernel, Kernel narrow_kernel, GridParams P, hipStream_t stream,
                         uint32_t max_log2_cols = 8, uint32_t wide_rows = 1, bool wave_workgroups = false, uint32_t lanes_per_block = 1) {
   if (P.n_images == 0 || P.block_rows == 0 || P.block_cols == 0) return hipSuccess;

@@ -87,8 +87,9 @@ template <int WT> __device__ inline void st8(u2 *p, u2 v) {
 }
 // the mix shape (k_mix, 4096-pixel rows); STORE = 0: no stores (kept loads), 1: 8 B per lane, 2: 16 B from every even lane (its block
 // and its neighbour's), WT / XCD_SWZ as above
-template <int STORE, int WT, bool XCD_SWZ> __global__ void __launch_bounds__(256) k_mix2(const u4 *src, u2 *dst, uint32_t n_blocks) {
-  const uint32_t k = wg_id<XCD_SWZ>(gridDim.x) * 256u + threadIdx.x, row16 = 1024u;
+// LANES: the workgroup's size (r08: the same waves launched as 128- or 64-lane workgroups, grid = n_blocks / LANES)
+template <int STORE, int WT, bool XCD_SWZ, int LANES = 256> __global__ void __launch_bounds__(LANES) k_mix2(const u4 *src, u2 *dst, uint32_t n_blocks) {
+  const uint32_t k = wg_id<XCD_SWZ>(gridDim.x) * (uint32_t)LANES + threadIdx.x, row16 = 1024u;
   const uint32_t brow = k >> 10, bcol = k & 1023u;
   const u4 *p = src + (size_t)brow * 4u * row16 + bcol;
   u4 a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + row16), c = __builtin_nontemporal_load(p + 2 * row16),
@@ -191,6 +192,8 @@ int main() {
       RUN2("r07 mix shape, 16 B stores / 2 lanes", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<2, 0, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
       RUN2("r07 mix shape, XCD-consecutive tiles", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 0, true>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
       RUN2("r07 mix shape, write-through stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 1, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
+      RUN2("r08 write-through, 128-lane workgroups", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 1, false, 128>), dim3(nb / 128), dim3(128), 0, 0, a, (u2 *)b, nb))
+      RUN2("r08 write-through, 64-lane workgroups", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 1, false, 64>), dim3(nb / 64), dim3(64), 0, 0, a, (u2 *)b, nb))
       RUN2("r07 mix shape, sc1 stores (agent)", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 2, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
       RUN2("r07 mix shape, sc0 sc1 nt buffer stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 3, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
       RUN2("r07 mix shape, sc0 buffer stores", 1.125 * bytes, hipLaunchKernelGGL((k_mix2<1, 4, false>), dim3(nb / 256), dim3(256), 0, 0, a, (u2 *)b, nb))
