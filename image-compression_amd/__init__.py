@@ -67,6 +67,10 @@ EAC_SIGNED_R11, EAC_SIGNED_RG11 = 24, 25
 # encoder writes mode 6 from 3- or 4-byte pixels (a definition stated in the header).  encode_device / decode_device (RGBA8 rows)
 # / measure_error_device / encode_batch_sharded_device / containers only (26..31 are unassigned)
 BC7 = 32
+# bc7_modes of encode_bc7_device (include/ic_amd.h icamd_encode_bc7_device): DEFAULT = what encode_device(BC7) writes (mode 6);
+# EXTENDED = per block also a mode-1 candidate (opaque blocks) or a mode-5 candidate (the others), written where strictly closer
+# 
+BC7_MODES_DEFAULT, BC7_MODES_EXTENDED = 0, 1
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -218,6 +222,29 @@ def encode_etc2_colour_device(codec, src, height, width, src_components, *, colo
 def etc2_colour_kernel_name(codec, src_components, colour_modes):
     """icamd_etc2_colour_kernel_name: the kernel of the colour-mode pass, or of what the call forwards to; "" if refused."""
     return lib().icamd_etc2_colour_kernel_name(codec, src_components, colour_modes).decode()
+
+
+def encode_bc7_device(src, height, width, src_components, *, bc7_modes=BC7_MODES_DEFAULT, swap_rb=False, grid_height=None,
+                      grid_width=None, row_stride_bytes=None, n_images=1, src_image_stride_bytes=None, out=None, stream=None):
+    """icamd_encode_bc7_device: encode_device(BC7, ...) with a choice of modes -- BC7_MODES_DEFAULT (encode_device itself) or
+    BC7_MODES_EXTENDED (the fused kernel with the mode-1 / mode-5 candidates).  Returns the output tensor
+    [n_images, encoded_size] (device).  No synchronisation."""
+    _assert_u8_cuda(src)
+    gh = height if grid_height is None else max(grid_height, height)
+    gw = width if grid_width is None else max(grid_width, width)
+    stride = width * src_components if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    per = encoded_size(BC7, gh, gw)
+    if out is None:
+        out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    st = lib().icamd_encode_bc7_device(bc7_modes, src_components, int(swap_rb), height, width, gh, gw, stride, n_images,
+                                       img_stride, per, _ptr(src), _ptr(out), _stream_handle(stream))
+    return out if _check(st, "icamd_encode_bc7_device") else None
+
+
+def bc7_kernel_name(src_components, bc7_modes):
+    """icamd_bc7_kernel_name: the kernel that writes the final bytes (BC7_MODES_DEFAULT: what kernel_name answers); "" if refused."""
+    return lib().icamd_bc7_kernel_name(src_components, bc7_modes).decode()
 
 
 def compress_device(compressor, fmt, src, height, width, *, padding_bytes_per_row=0,

@@ -29,6 +29,8 @@ PROTOTYPES = (
     ("icamd_etc2_kernel_name", s, [i, i, i]),
     ("icamd_encode_etc2_colour_device", i, [i, i, i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
     ("icamd_etc2_colour_kernel_name", s, [i, i, i]),
+    ("icamd_encode_bc7_device", i, [i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_bc7_kernel_name", s, [i, i]),
     ("icamd_decode_device", i, [i, i, u, u, u, u, z, z, p, p, p]),
     ("icamd_decompress", i, [i, i, u, u, u, p, z, p, z]),
     ("icamd_pvrtc2_decompress", i, [u, p, z, p, z]),

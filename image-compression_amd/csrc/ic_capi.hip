@@ -594,6 +594,35 @@ const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes
   return "";
 }
 
+// EXTENSION (include/ic_amd.h ICAMD_BC7_MODES_EXTENDED): every argument is checked before any device work; modes 0 IS
+// icamd_encode_device(ICAMD_BC7), modes 1 the fused kernel of bc7_modes_kernels.hip in its place
+int icamd_encode_bc7_device(int bc7_modes, int src_components, int swap_rb, uint32_t height, uint32_t width,
+                            uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                            size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                            const void *d_src, void *d_dst, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (bc7_modes != ICAMD_BC7_MODES_DEFAULT && bc7_modes != ICAMD_BC7_MODES_EXTENDED)
+    return fail(ICAMD_ERR_ARG, "bc7_modes must be ICAMD_BC7_MODES_DEFAULT or ICAMD_BC7_MODES_EXTENDED");
+  if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
+  if (n_images == 0) return ICAMD_OK;  // (before the stride, as in icamd_encode_device)
+  if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (bc7_modes == ICAMD_BC7_MODES_DEFAULT)
+    return icamd_encode_device(ICAMD_BC7, 0, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
+                               n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, hip_stream);
+  const int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, swap_rb, 0u);
+  ICAMD_HIP(icamd::launch_bc7_modes_encode(src_components, P, static_cast<hipStream_t>(hip_stream)), "launch bc7 modes");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_bc7_kernel_name(int src_components, int bc7_modes) {
+  if (bc7_modes == ICAMD_BC7_MODES_DEFAULT) return icamd::bc7_kernel_name(src_components);
+  if (bc7_modes == ICAMD_BC7_MODES_EXTENDED) return icamd::bc7_modes_kernel_name(src_components);
+  return "";
+}
+
 // EXTENSION (include/ic_amd.h ICAMD_ETC2_COLOUR_PLANAR_TH): planar, T and H colour words for all three ETC2 colour codecs.
 // true for the three codecs with a component count they take
 static bool etc2_colour_accepts(int codec, int src_components) {

@@ -187,6 +187,10 @@ const char *eac11_16_metric_kernel_name(int codec, int chans);  // "" where laun
 hipError_t launch_bc7_encode(int comps, const GridParams &P, hipStream_t stream);
 hipError_t launch_bc7_decode(const DecodeParams &P, hipStream_t stream);
 const char *bc7_kernel_name(int comps);  // "" unless comps is 3 or 4
+// BC7 with the mode-1 / mode-5 candidates (extension, bc7_modes_kernels.hip; icamd_encode_bc7_device with
+// ICAMD_BC7_MODES_EXTENDED): one fused kernel in place of launch_bc7_encode's, the same GridParams.
+hipError_t launch_bc7_modes_encode(int comps, const GridParams &P, hipStream_t stream);
+const char *bc7_modes_kernel_name(int comps);  // "" unless comps is 3 or 4
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

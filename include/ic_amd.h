@@ -482,6 +482,68 @@ int icamd_encode_etc2_colour_device(int codec, int etc_strategy, int colour_mode
                                     const void *d_src, void *d_dst, void *hip_stream);
 const char *icamd_etc2_colour_kernel_name(int codec, int src_components, int colour_modes);
 
+/* EXTENSION: BC7 with a choice of modes.  The codec is ICAMD_BC7; bc7_modes is one of the two values below and
+ * src_components 3 or 4; every other argument means what it means to icamd_encode_device(ICAMD_BC7, ...) (etc_strategy does not
+ * exist here).  Every argument is checked before any device work, in the order of icamd_encode_etc2_device: a null pointer or a
+ * zero height / width returns ICAMD_FALSE; then a bc7_modes or src_components outside the above ICAMD_ERR_ARG; then
+ * n_images == 0 ICAMD_OK; then a row stride shorter than a row ICAMD_ERR_ARG.
+ *   ICAMD_BC7_MODES_DEFAULT   the call IS icamd_encode_device(ICAMD_BC7, ...): the same kernels, the same launches, byte for byte.
+ *   ICAMD_BC7_MODES_EXTENDED  ONE fused kernel in place of those: per block it computes the mode-6 block of ICAMD_BC7 and ONE
+ *                             candidate, and writes the candidate iff it is STRICTLY closer.  A DEFINITION, not a heuristic:
+ * Texels v_p, p = 4 y + x, are exactly those the mode-6 definition at ICAMD_BC7 is handed (edge replication, padded grids, swap_rb,
+ * A = 255 for 3-component sources).  First the mode-6 block and its final sse (sse6), steps 1-5 at ICAMD_BC7, unchanged.
+ *   Block class.  Opaque = all sixteen A = 255 (always so for 3-component sources): the mode-1 candidate.  Every other block: the
+ *       mode-5 candidate.
+ *   Endpoint grids.  A 7-bit value x decodes to e7(x) = (x << 1) | (x >> 6).  "Nearest to T" = the x of the allowed set that
+ *       minimises |e7(x) - T|, ties to the smaller x.
+ *   Sub-fit F(S, C, weights, Q) over a texel set S (not empty) and a channel set C = steps 1-4 at ICAMD_BC7 restricted to S and C:
+ *       targets = the per-channel min / max over S; c* = the channel of C with the largest max - min, ties to the earlier
+ *       channel; for every other channel c of C the targets are exchanged where
+ *       |S| sum_S v[c*] v[c] - (sum_S v[c*]) (sum_S v[c]) < 0; the endpoint bytes E0, E1 come from the quantiser Q, which is
+ *       handed the targets of BOTH endpoints; pal_k[c] = ((64 - w_k) E0[c] + w_k E1[c] + 32) >> 6 over the 2- or 3-bit weights
+ *       at ICAMD_BC7, every texel of S takes the smallest k that minimises sum over C of (pal_k[c] - v_p[c])^2, and the sub-fit's
+ *       sse is the sum of those minima over S; one least-squares refit with the formulas of step 4, every sum taken over S
+ *       (a = sum_S (64 - w)^2, b = sum_S (64 - w) w, c = sum_S w^2, X = sum_S (64 - w) v, Y = sum_S w v); det = 0 means no refit;
+ *       rdiv's result is clamped to 0..255; the refit is quantised by Q and searched again, and replaces the first pass only if
+ *       the sub-fit's sse gets STRICTLY smaller.
+ *   Mode 1 (opaque blocks).
+ *       1. Partition.  For each of the 64 two-subset partitions s of the BPTC specification: n0, n1 = the subsets' texel
+ *          counts, S0, S1 = the (R, G, B) vector sums over the subsets, N_s = n1 |S0|^2 + n0 |S1|^2, d_s = n0 n1.  s beats t
+ *          iff N_s d_t > N_t d_s (exact integers; the products need 64 bits).  The best partition is taken, ties to the smaller
+ *          s: the one with the smallest within-subset scatter.  ONE partition is fitted, not 64.
+ *       2. Subset j = 0, 1 is fitted with F(subset j, {R, G, B}, the 3-bit weights, Q1).  Q1: for p in {0, 1}, every channel of
+ *          both endpoints takes the nearest x with x & 1 = p; err(p) = the sum of the six (e7(x) - T)^2; the p with the smaller
+ *          err wins, ties to 0.  Stored: q = x >> 1 per channel and endpoint, and the subset's one p.
+ *       3. sse1 = the sum of the two sub-fits' sse (alpha decodes to 255 exactly and adds nothing).
+ *       4. Anchors.  Subset 0's anchor is texel 0, subset 1's the specification's anchor of the partition.  Where an anchor's
+ *          index is >= 4, that subset's endpoints are exchanged and its indices become 7 - k.
+ *       5. Pack, least significant bit first: bit 0 = 0, bit 1 = 1; the partition (6 bits); R of (subset 0 E0, subset 0 E1,
+ *          subset 1 E0, subset 1 E1), 6 bits each; G likewise; B likewise; p of subset 0, p of subset 1; the sixteen indices in
+ *          texel order, 3 bits each, the two anchors' in 2 bits.
+ *   Mode 5 (the other blocks), rotation 0 only (rotations 1-3 are decoded, never written).
+ *       1. Colour: F(all sixteen texels, {R, G, B}, the 2-bit weights, Q5).  Q5: per channel and endpoint the nearest x of
+ *          0..127; no p-bit.
+ *       2. Alpha: F(all sixteen texels, {A}, the 2-bit weights, identity): the endpoints are the 8-bit targets themselves.  (One
+ *          channel: c* = A and nothing is exchanged.)
+ *       3. sse5 = the sum of the two.
+ *       4. Anchor flips, applied to the colour indices and to the alpha indices separately: an index of texel 0 that is >= 2
+ *          exchanges that plane's endpoints and turns its indices into 3 - k.
+ *       5. Pack: bits 0..4 = 0, bit 5 = 1; rotation 00; R0 R1 G0 G1 B0 B1 (x, 7 bits each); A0 A1 (8 bits each); the colour
+ *          indices (31 bits: texel 0 in 1 bit, the others 2 bits each); the alpha indices (31 bits likewise).
+ *   Choice.  The candidate replaces the mode-6 block iff its sse is STRICTLY smaller than sse6; every sse is over the four
+ *       channels.  So no block's error exceeds ICAMD_BC7_MODES_DEFAULT's.
+ * icamd_bc7_kernel_name names the kernel that writes the final bytes under ICAMD_BC7_MODES_EXTENDED; under
+ * ICAMD_BC7_MODES_DEFAULT it answers what icamd_kernel_name(ICAMD_BC7, ...) answers; "" outside the domain.
+ * icamd_encode_device, the sharded batch entry, the mip entry points and every other export behave as before; they do not reach
+ * ICAMD_BC7_MODES_EXTENDED. */
+enum { ICAMD_BC7_MODES_DEFAULT = 0,    /* what icamd_encode_device writes: mode 6 */
+       ICAMD_BC7_MODES_EXTENDED = 1 }; /* + a mode-1 candidate on opaque blocks, a mode-5 candidate on the others */
+int icamd_encode_bc7_device(int bc7_modes, int src_components, int swap_rb, uint32_t height, uint32_t width,
+                            uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                            size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                            const void *d_src, void *d_dst, void *hip_stream);
+const char *icamd_bc7_kernel_name(int src_components, int bc7_modes);
+
 /* ---- "next" row 8f.1: block decoders on device (Compressor::Decompress, compressor.h:85-86;
  * helper.h:218-262, dxtc.cc:167-267, etc.cc:198-289).  Writes height rows of
  * width*comps + padding_bytes_per_row bytes (comps = 4 for DXT5, PVRTC2 and PVRTC4, else 3).
