@@ -71,6 +71,11 @@ BC7 = 32
 # EXTENDED = per block also a mode-1 candidate (opaque blocks) or a mode-5 candidate (the others), written where strictly closer
 # 
 BC7_MODES_DEFAULT, BC7_MODES_EXTENDED = 0, 1
+# EXTENSION (include/ic_amd.h ICAMD_BC6H_UF16): BC6H / BPTC float, unsigned and signed, 16 bytes per block of RGB halves.  The
+# decoder and the metric read all fourteen modes; the encoder writes the one-subset 10-bit mode from RGB16F / RGBA16F pixels (a
+# definition stated in the header).  encode_bc6h_device / decode_bc6h_device / measure_error_bc6h_device / containers (DDS, KTX)
+# only (33 is unassigned)
+BC6H_UF16, BC6H_SF16 = 34, 35
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -1058,3 +1063,83 @@ def psnr16_from_stats(sse, n_pixels, n_channels, signed=False):
     total = float(sse.sum()) if hasattr(sse, "sum") else float(sum(sse))
     peak = 32767.0 if signed else 65535.0
     return math.inf if total == 0 else 10.0 * math.log10(peak ** 2 * n_pixels * n_channels / total)
+
+
+# ---- BC6H (include/ic_amd.h icamd_encode_bc6h_device)
+# codec: BC6H_UF16 or BC6H_SF16.  Pixel tensors are torch.float16 (one element per sample), or the same bits as torch.int16 /
+# torch.uint16, or the same memory as torch.uint8 (little-endian bytes); all four are accepted.  Blocks are torch.uint8.  Strides
+# and paddings are always in BYTES.
+
+def _assert_halves_cuda(t):
+    assert t.is_cuda and t.is_contiguous() and t.dtype in (torch.float16, torch.int16, torch.uint16, torch.uint8)
+
+
+def bc6h_kernel_name(codec, src_channels, metric=False):
+    """icamd_bc6h_kernel_name, or with metric=True icamd_bc6h_metric_kernel_name; "" for a refused combination."""
+    fn = lib().icamd_bc6h_metric_kernel_name if metric else lib().icamd_bc6h_kernel_name
+    return fn(codec, src_channels).decode()
+
+
+def encode_bc6h_device(codec, src, height, width, src_channels, *, grid_height=None, grid_width=None, row_stride_bytes=None,
+                       n_images=1, src_image_stride_bytes=None, out=None, stream=None):
+    """icamd_encode_bc6h_device on `src`: a contiguous CUDA tensor of halves (see above), src_channels (3 or 4) per pixel.
+    Returns the torch.uint8 blocks [n_images, encoded_size] (device), or None where the call answers false.  No synchronisation."""
+    _assert_halves_cuda(src)
+    gh = height if grid_height is None else max(grid_height, height)
+    gw = width if grid_width is None else max(grid_width, width)
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    per = encoded_size(codec, gh, gw)
+    if out is None:
+        out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, per, "encode_bc6h_device")
+    st = lib().icamd_encode_bc6h_device(codec, src_channels, height, width, gh, gw, stride, n_images, img_stride, per,
+                                        _ptr(src), _ptr(out), _stream_handle(stream))
+    return out if _check(st, "icamd_encode_bc6h_device") else None
+
+
+def decode_bc6h_device(codec, blocks, height, width, *, padding_bytes_per_row=0, n_images=1, stream=None):
+    """icamd_decode_bc6h_device: torch.uint8 blocks -> a [n_images, height * (width * 4 + padding_bytes_per_row / 2)] tensor of
+    torch.float16: RGBA16F rows, A = 1; the padding samples are zero.  None where the call answers false.  No synchronisation."""
+    _assert_u8_cuda(blocks)
+    per_out = height * (width * 8 + padding_bytes_per_row)
+    out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)
+    st = lib().icamd_decode_bc6h_device(codec, height, width, padding_bytes_per_row, n_images, encoded_size(codec, height, width),
+                                        per_out, _ptr(blocks), _ptr(out), _stream_handle(stream))
+    if not _check(st, "icamd_decode_bc6h_device"):
+        return None
+    return out.view(torch.float16)
+
+
+def measure_error_bc6h_device(codec, src, blocks, height, width, src_channels, *, grid_height=None, grid_width=None,
+                              row_stride_bytes=None, n_images=1, src_image_stride_bytes=None, blocks_image_stride_bytes=None,
+                              out=None, stream=None):
+    """icamd_measure_error_bc6h_device: `blocks` (torch.uint8, as encode_bc6h_device writes them for the grid) against the halves
+    `src` (as encode_bc6h_device reads them).  Returns ([n, 4] int64 sums of squared t-domain differences, [n, 4] int32 largest
+    absolute differences; entries 0, 1, 2 = R, G, B) as device tensors, or None where the call answers false.  `out`: a
+    caller-owned [n_images, 48] uint8 device tensor for the raw records.  No synchronisation."""
+    _assert_halves_cuda(src)
+    _assert_u8_cuda(blocks)
+    gh = height if grid_height is None else grid_height
+    gw = width if grid_width is None else grid_width
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    blk_stride = encoded_size(codec, max(gh, height), max(gw, width)) if blocks_image_stride_bytes is None \
+        else blocks_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, ERROR_STATS_BYTES), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, ERROR_STATS_BYTES, "measure_error_bc6h_device")
+    st = lib().icamd_measure_error_bc6h_device(codec, src_channels, height, width, gh, gw, stride, n_images, img_stride,
+                                               blk_stride, _ptr(src), _ptr(blocks), _ptr(out), _stream_handle(stream))
+    if not _check(st, "icamd_measure_error_bc6h_device"):
+        return None
+    return _split_stats(out)
+
+
+def psnr_bc6h_from_stats(sse, n_pixels, n_channels=3):
+    """10 log10(peak^2 N C / SSE) in the t domain, peak 31743 (the largest finite half's bit pattern); inf for a perfect match."""
+    import math
+    total = float(sse.sum()) if hasattr(sse, "sum") else float(sum(sse))
+    return math.inf if total == 0 else 10.0 * math.log10(31743.0 ** 2 * n_pixels * n_channels / total)

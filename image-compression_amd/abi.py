@@ -88,6 +88,11 @@ PROTOTYPES = (
     ("icamd_measure_error_eac11_16_device", i, [i, i, u, u, u, u, u, u, z, z, p, p, p, p]),
     ("icamd_eac11_16_kernel_name", s, [i, i]),
     ("icamd_eac11_16_metric_kernel_name", s, [i, i]),
+    ("icamd_encode_bc6h_device", i, [i, i, u, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_decode_bc6h_device", i, [i, u, u, u, u, z, z, p, p, p]),
+    ("icamd_measure_error_bc6h_device", i, [i, i, u, u, u, u, u, u, z, z, p, p, p, p]),
+    ("icamd_bc6h_kernel_name", s, [i, i]),
+    ("icamd_bc6h_metric_kernel_name", s, [i, i]),
     ("icamd_device_count", i, []),
     ("icamd_last_error", s, []),
     ("icamd_version", s, []),

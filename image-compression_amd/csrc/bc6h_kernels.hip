@@ -1,0 +1,210 @@
+// bc6h_kernels.hip -- BC6H (BPTC float) for gfx950 (EXTENSION, include/ic_amd.h icamd_encode_bc6h_device): the
+// one-subset encoder, the decoder of all fourteen modes and the metric; see bc6h_block.h for the block math.
+//
+// Encode: one 4 x 4 block per lane on the tiles of launch_tiled like BC7 (a wave reads 64 consecutive blocks' row segments and
+// writes 64 consecutive 16-byte blocks).  The fetch is the 16-bit EAC encoder's: four row loads of 8 C bytes at a 64-bit lane
+// address (any 2-byte alignment, any even row padding) where the block lies in the image, the clamp-to-edge gather otherwise, so
+// GridParams::force_gather is not read.  Integer only, everything in registers (no LDS, no scratch).
+// Decode: blocks in raster order like bc7_decode_one; RGBA16F rows, A = 0x3C00: two 16-byte stores per pixel row of a block,
+// 8-byte stores per pixel on the blocks the image's edge clips.  Lanes of a wave hold different modes: no wave-uniform shortcut.
+// Metric: the launch shape of the 16-bit EAC metric (blocks in raster order of the images' own grids, four per lane); sums are
+// 64-bit from the lane on, lanes meet by wave shuffles and every wave adds its sums to the image's record.
+#include "bc6h_block.h"
+#include "ic_launch.h"
+#include "ic_amd.h"
+
+namespace icamd {
+
+namespace {
+constexpr uint32_t kBc6hMetricBlocksPerLane = 4;
+}  // namespace
+
+template <int C, bool SIGNED, bool WIDE>
+__device__ __forceinline__ void bc6h_encode_one(const GridParams &P) {
+  const TileCoord t = locate_tile<WIDE>(P);
+  if (!t.valid) return;
+  uint32_t rg[16], b[16], out[4];
+  bc6h_fetch<C>(P.src + (uint64_t)t.img * P.src_image_stride, P.height, P.width, P.row_stride, t.brow * 4u, t.bcol * 4u, rg, b);
+  encode_bc6h<SIGNED>(rg, b, out);
+  store_stream16(tile_dst<16>(P, t), out[0], out[1], out[2], out[3]);
+}
+
+template <bool SIGNED>
+__device__ __forceinline__ void bc6h_decode_one(const DecodeParams &P, uint32_t k) {
+  const uint32_t img = fastdiv(k, P.div_bpi);
+  const uint32_t rem = k - img * P.blocks_per_image;
+  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const U4 v = load_stream(reinterpret_cast<const U4 *>(P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * 16u));
+  const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+  uint32_t rg[16], b[16];
+  decode_bc6h<SIGNED>(w, rg, b);
+  uint8_t *dst = P.pixels + (size_t)img * P.dst_image_stride;
+  const uint32_t row = brow * 4, col = bcol * 4;
+  constexpr uint32_t kOne = 0x3c000000u;  // A = 1.0 in the high half
+  if (row + 4 <= P.height && col + 4 <= P.width) {
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+      uint8_t *q = dst + (size_t)(row + y) * P.row_stride + (size_t)col * 8u;
+      store_stream16(q, rg[4 * y], b[4 * y] | kOne, rg[4 * y + 1], b[4 * y + 1] | kOne);
+      store_stream16(q + 16, rg[4 * y + 2], b[4 * y + 2] | kOne, rg[4 * y + 3], b[4 * y + 3] | kOne);
+    }
+  } else {
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (row + y < P.height && col + x < P.width)
+          store_stream8(dst + (size_t)(row + y) * P.row_stride + (size_t)(col + x) * 8u, rg[4 * y + x], b[4 * y + x] | kOne);
+  }
+}
+
+__device__ __forceinline__ void bc6h_wave_reduce(Bc6hAcc &a) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      a.sse[k] += (uint64_t)__shfl_xor((unsigned long long)a.sse[k], off);
+      a.mx[k] = umax(a.mx[k], (uint32_t)__shfl_xor((int)a.mx[k], off));
+    }
+  }
+}
+__device__ __forceinline__ void bc6h_commit(const MetricParams &P, uint32_t img, const Bc6hAcc &a) {
+  icamd_error_stats *rec = reinterpret_cast<icamd_error_stats *>(P.stats) + img;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (a.sse[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&rec->sse[k]), (unsigned long long)a.sse[k]);
+    if (a.mx[k]) atomicMax(&rec->max_abs[k], a.mx[k]);
+  }
+}
+// One commit per wave where its lanes hold blocks of one image, one per lane where they do not (small images in a batch).
+// Every lane of the wave calls this (lanes without a block bring zeros).
+__device__ __forceinline__ void bc6h_flush_wave(const MetricParams &P, uint32_t img, Bc6hAcc &a) {
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)img);
+  if (wave_all(img == first)) {
+    bc6h_wave_reduce(a);
+    if ((threadIdx.x & 63u) == 0u) bc6h_commit(P, first, a);
+  } else {
+    bc6h_commit(P, img, a);
+  }
+}
+
+template <int C, bool SIGNED>
+__device__ __forceinline__ void bc6h_metric(const MetricParams &P) {
+  const uint32_t chunk0 = blockIdx.x * (kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane);
+  const uint32_t last = umin(chunk0 + kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane, P.total_blocks) - 1u;
+  const uint32_t img_first = fastdiv(chunk0, P.div_bpi), img_last = fastdiv(last, P.div_bpi);
+  const bool one_image = img_first == img_last;  // workgroup-uniform
+  Bc6hAcc acc;
+  bc6h_clear(acc);
+#pragma nounroll
+  for (uint32_t j = 0; j < kBc6hMetricBlocksPerLane; ++j) {
+    const uint32_t k = chunk0 + j * kThreadsPerWorkgroup + threadIdx.x;
+    uint32_t img = img_last;
+    if (k < P.total_blocks) {
+      img = one_image ? img_first : fastdiv(k, P.div_bpi);
+      const uint32_t rem = k - img * P.blocks_per_image;
+      const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+      const uint8_t *blk = P.blocks + (size_t)img * P.blocks_image_stride + ((size_t)brow * P.grid_cols + bcol) * 16u;
+      const U4 v = load_stream(reinterpret_cast<const U4 *>(blk));
+      const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+      metric_bc6h_block<C, SIGNED>(w, P.src + (size_t)img * P.src_image_stride, P.height, P.width, P.row_stride, brow * 4u,
+                                   bcol * 4u, acc);
+    }
+    if (!one_image) {
+      bc6h_flush_wave(P, img, acc);
+      bc6h_clear(acc);
+    }
+  }
+  if (one_image) bc6h_flush_wave(P, img_first, acc);
+}
+
+extern "C" {
+
+// *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape
+#define ICAMD_BC6H_KERNELS(X)                                                                                               \
+  X(bc6h_uf16_rgb16f, ICAMD_BC6H_UF16, 3, false)                                                                            \
+  X(bc6h_uf16_rgba16f, ICAMD_BC6H_UF16, 4, false)                                                                           \
+  X(bc6h_sf16_rgb16f, ICAMD_BC6H_SF16, 3, true)                                                                             \
+  X(bc6h_sf16_rgba16f, ICAMD_BC6H_SF16, 4, true)
+
+#define ICAMD_BC6H_DEFINE(stem, codec, chans, is_signed)                                                                    \
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_kernel(GridParams P) {                             \
+    bc6h_encode_one<chans, is_signed, true>(P);                                                                             \
+  }                                                                                                                         \
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_narrow_kernel(GridParams P) {                      \
+    bc6h_encode_one<chans, is_signed, false>(P);                                                                            \
+  }                                                                                                                         \
+  __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_metric_##stem##_kernel(MetricParams P) {                    \
+    bc6h_metric<chans, is_signed>(P);                                                                                       \
+  }
+ICAMD_BC6H_KERNELS(ICAMD_BC6H_DEFINE)
+#undef ICAMD_BC6H_DEFINE
+
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc6h_uf16_decode_kernel(DecodeParams P) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k < P.total_blocks) bc6h_decode_one<false>(P, k);
+}
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc6h_sf16_decode_kernel(DecodeParams P) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k < P.total_blocks) bc6h_decode_one<true>(P, k);
+}
+
+}  // extern "C"
+
+namespace {
+struct Bc6hKernel {
+  int codec, chans;
+  void (*wide)(GridParams);
+  void (*narrow)(GridParams);
+  void (*metric)(MetricParams);
+  const char *name, *metric_name;
+};
+#define ICAMD_BC6H_ENTRY(stem, codec, chans, is_signed) \
+  { codec, chans, icamd_##stem##_kernel, icamd_##stem##_narrow_kernel, icamd_metric_##stem##_kernel, "icamd_" #stem "_kernel", \
+    "icamd_metric_" #stem "_kernel" },
+const Bc6hKernel kBc6hKernels[] = { ICAMD_BC6H_KERNELS(ICAMD_BC6H_ENTRY) };
+#undef ICAMD_BC6H_ENTRY
+const Bc6hKernel *find_bc6h(int codec, int chans) {
+  for (const Bc6hKernel &k : kBc6hKernels)
+    if (k.codec == codec && k.chans == chans) return &k;
+  return nullptr;
+}
+}  // namespace
+#undef ICAMD_BC6H_KERNELS
+
+const char *bc6h_kernel_name(int codec, int chans) {
+  const Bc6hKernel *k = find_bc6h(codec, chans);
+  return k ? k->name : "";
+}
+const char *bc6h_metric_kernel_name(int codec, int chans) {
+  const Bc6hKernel *k = find_bc6h(codec, chans);
+  return k ? k->metric_name : "";
+}
+
+hipError_t launch_bc6h_encode(int codec, int chans, const GridParams &P, hipStream_t stream) {
+  const Bc6hKernel *k = find_bc6h(codec, chans);
+  if (!k) return hipErrorInvalidValue;
+  return launch_tiled(k->wide, k->narrow, P, stream);
+}
+
+hipError_t launch_bc6h_decode(int codec, const DecodeParams &P, hipStream_t stream) {
+  if (codec != ICAMD_BC6H_UF16 && codec != ICAMD_BC6H_SF16) return hipErrorInvalidValue;
+  if (P.total_blocks == 0) return hipSuccess;
+  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+  hipLaunchKernelGGL(codec == ICAMD_BC6H_SF16 ? icamd_bc6h_sf16_decode_kernel : icamd_bc6h_uf16_decode_kernel,
+                     dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), dim3(kThreadsPerWorkgroup), 0, stream,
+                     P);
+  return hipGetLastError();
+}
+
+hipError_t launch_bc6h_metric(int codec, int chans, const MetricParams &P, hipStream_t stream) {
+  if (P.total_blocks == 0) return hipSuccess;
+  const Bc6hKernel *k = find_bc6h(codec, chans);
+  if (!k) return hipErrorInvalidValue;
+  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+  const uint32_t per = kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane;
+  hipLaunchKernelGGL(k->metric, dim3((P.total_blocks + per - 1u) / per), dim3(kThreadsPerWorkgroup), 0, stream, P);
+  return hipGetLastError();
+}
+
+}  // namespace icamd

@@ -10,10 +10,10 @@ namespace icamd {
 
 // Bytes of one 4 x 4 block (PVRTC included: 8 bytes per 8 x 4 / 4 x 4 block): 16 for DXT5 (alpha half + colour half) and BC5
 // (two BC4 halves), ETC2 RGBA8 (EAC alpha word + colour word), EAC RG11 and signed EAC RG11 (two EAC words), 8 for every other
-// codec (ETC2 RGB8, ETC2 RGB8A1, EAC R11 and signed EAC R11 among them).  BC7: 16.
+// codec (ETC2 RGB8, ETC2 RGB8A1, EAC R11 and signed EAC R11 among them).  BC7 and BC6H (both formats): 16.
 constexpr uint32_t codec_block_bytes(int codec) {
   return (codec == ICAMD_DXT5 || codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_EAC_RG11 ||
-          codec == ICAMD_EAC_SIGNED_RG11 || codec == ICAMD_BC7) ? 16u : 8u;
+          codec == ICAMD_EAC_SIGNED_RG11 || codec == ICAMD_BC7 || codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16) ? 16u : 8u;
 }
 
 }  // namespace icamd

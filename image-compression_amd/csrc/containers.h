@@ -7,13 +7,15 @@
 //   * DDS  -- "DDS " magic + 124-byte DDS_HEADER with a FOURCC pixel format (DXT1 / DXT5, and ATI1 / ATI2 for BC4 / BC5;
 //             the legacy header has no code for ETC1 or PVRTC); BC7: FOURCC "DX10" followed by the 20-byte DDS_HEADER_DXT10
 //             (dxgiFormat 98 = DXGI_FORMAT_BC7_UNORM, resourceDimension 3 = TEXTURE2D, miscFlag 0, arraySize 1, miscFlags2 0);
+//             BC6H: the same two headers with dxgiFormat 95 = DXGI_FORMAT_BC6H_UF16 / 96 = DXGI_FORMAT_BC6H_SF16;
 //   * KTX  -- KTX 1.1: 12-byte identifier, 13 little-endian uint32 fields, then per mip level uint32 imageSize + data
 //             (glInternalFormat: COMPRESSED_RGB_S3TC_DXT1_EXT 0x83F0, COMPRESSED_RGBA_S3TC_DXT5_EXT 0x83F3,
 //             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03, COMPRESSED_RED_RGTC1 0x8DBB with base format
 //             GL_RED, COMPRESSED_RG_RGTC2 0x8DBD with base format GL_RG, COMPRESSED_RGBA8_ETC2_EAC 0x9278 with GL_RGBA,
 //             COMPRESSED_R11_EAC 0x9270 with GL_RED, COMPRESSED_RG11_EAC 0x9272 with GL_RG,
 //             COMPRESSED_SIGNED_R11_EAC 0x9271 with GL_RED, COMPRESSED_SIGNED_RG11_EAC 0x9273 with GL_RG,
-//             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA, COMPRESSED_RGBA_BPTC_UNORM 0x8E8C with GL_RGBA);
+//             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA, COMPRESSED_RGBA_BPTC_UNORM 0x8E8C with GL_RGBA,
+//             COMPRESSED_RGB_BPTC_UNSIGNED_FLOAT 0x8E8F and COMPRESSED_RGB_BPTC_SIGNED_FLOAT 0x8E8E with GL_RGB);
 //   * PKM  -- 16-byte big-endian header, exactly one level: "PKM 10" with type 0 for ETC1, "PKM 20" with type 3
 //             (ETC2_RGBA_NO_MIPMAPS) for ETC2 RGBA8, type 4 (ETC2_RGBA1_NO_MIPMAPS) for ETC2 RGB8A1, type 5 / 6 (ETC2_R /
 //             ETC2_RG _NO_MIPMAPS) for EAC R11 / RG11, type 7 / 8 (ETC2_R_SIGNED / ETC2_RG_SIGNED _NO_MIPMAPS) for the signed two;
@@ -47,9 +49,11 @@ inline void put_be16(uint8_t *p, uint32_t v) {
   p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v;
 }
 
+inline bool container_bc6h(int codec) { return codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16; }
+
 inline size_t container_header_size(int container, int codec) {
   switch (container) {
-    case ICAMD_CONTAINER_DDS: return codec == ICAMD_BC7 ? 148 : 128;  // BC7: + DDS_HEADER_DXT10
+    case ICAMD_CONTAINER_DDS: return codec == ICAMD_BC7 || container_bc6h(codec) ? 148 : 128;  // BC7, BC6H: + DDS_HEADER_DXT10
     case ICAMD_CONTAINER_KTX: return 64;
     case ICAMD_CONTAINER_PKM: return 16;
     case ICAMD_CONTAINER_PVR: return 52;
@@ -60,8 +64,11 @@ inline size_t container_header_size(int container, int codec) {
 inline bool container_supports(int container, int codec) {
   switch (container) {
     case ICAMD_CONTAINER_DDS:
-      return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_BC7;
+      return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_BC7 ||
+             container_bc6h(codec);
     case ICAMD_CONTAINER_KTX:
+      if (container_bc6h(codec)) return true;  // (BC6H: DDS and KTX only)
+      [[fallthrough]];
     case ICAMD_CONTAINER_PVR:
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
              codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
@@ -107,8 +114,9 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1"
                        : codec == ICAMD_BC5 ? "ATI2" : "DX10", 4);
       put_le32(out + 108, 0x1000u | (levels > 1 ? 0x8u | 0x400000u : 0u));               // DDSCAPS_TEXTURE [COMPLEX MIPMAP]
-      if (codec == ICAMD_BC7) {  // DDS_HEADER_DXT10
-        put_le32(out + 128, 98);  // dxgiFormat: DXGI_FORMAT_BC7_UNORM
+      if (codec == ICAMD_BC7 || container_bc6h(codec)) {  // DDS_HEADER_DXT10
+        // dxgiFormat: DXGI_FORMAT_BC7_UNORM, DXGI_FORMAT_BC6H_UF16, DXGI_FORMAT_BC6H_SF16
+        put_le32(out + 128, codec == ICAMD_BC7 ? 98 : codec == ICAMD_BC6H_UF16 ? 95 : 96);
         put_le32(out + 132, 3);   // resourceDimension: D3D10_RESOURCE_DIMENSION_TEXTURE2D
         put_le32(out + 136, 0);   // miscFlag
         put_le32(out + 140, 1);   // arraySize
@@ -128,7 +136,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
                                 : codec == ICAMD_ETC2_RGBA8 ? 0x9278u : codec == ICAMD_ETC2_RGB8 ? 0x9274u
                                 : codec == ICAMD_EAC_R11 ? 0x9270u : codec == ICAMD_EAC_RG11 ? 0x9272u
                                 : codec == ICAMD_EAC_SIGNED_R11 ? 0x9271u : codec == ICAMD_EAC_SIGNED_RG11 ? 0x9273u
-                                : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : codec == ICAMD_BC7 ? 0x8E8Cu : 0x8C03u;
+                                : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : codec == ICAMD_BC7 ? 0x8E8Cu
+                                : codec == ICAMD_BC6H_UF16 ? 0x8E8Fu : codec == ICAMD_BC6H_SF16 ? 0x8E8Eu : 0x8C03u;
       put_le32(out + 28, internal);
       const uint32_t base = (codec == ICAMD_BC4 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 0x1903u     // GL_RED
                             : (codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 0x8227u  // GL_RG

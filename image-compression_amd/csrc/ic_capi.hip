@@ -889,6 +889,8 @@ static int decode_launch(int codec, int swap_rb, uint32_t height, uint32_t width
     ICAMD_HIP(icamd::launch_etc2_a1_decode(P, stream), "launch etc2 rgb8a1 decode");
   else if (codec == ICAMD_BC7)
     ICAMD_HIP(icamd::launch_bc7_decode(P, stream), "launch bc7 decode");
+  else if (codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16)  // (icamd_decode_bc6h_device only: RGBA16F rows)
+    ICAMD_HIP(icamd::launch_bc6h_decode(codec, P, stream), "launch bc6h decode");
   else
     ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
   return ICAMD_OK;
@@ -1225,6 +1227,121 @@ const char *icamd_eac11_16_kernel_name(int codec, int src_channels) { return ica
 const char *icamd_eac11_16_metric_kernel_name(int codec, int src_channels) {
   return icamd::eac11_16_metric_kernel_name(codec, src_channels);
 }
+
+// ---- BC6H (EXTENSION, include/ic_amd.h icamd_encode_bc6h_device; csrc/bc6h_kernels.hip) ----
+// Every argument check comes before any device work; the order of the checks is that of the 16-bit EAC entry points.
+static bool bc6h_codec(int codec) { return codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16; }
+// The source rules the encoder and the metric share: the codec, the channel count, 2-byte alignment of the samples.
+static int bc6h_check_source(int codec, int src_channels, uint32_t row_stride_bytes, size_t src_image_stride_bytes, const void *d_src) {
+  if (!bc6h_codec(codec)) return fail(ICAMD_ERR_ARG, "BC6H: the codec must be ICAMD_BC6H_UF16 or ICAMD_BC6H_SF16");
+  if (src_channels != 3 && src_channels != 4) return fail(ICAMD_ERR_ARG, "BC6H needs 3 or 4 source channels");
+  if (reinterpret_cast<uintptr_t>(d_src) % 2u || row_stride_bytes % 2u || src_image_stride_bytes % 2u)
+    return fail(ICAMD_ERR_ARG, "BC6H: d_src, row_stride_bytes and src_image_stride_bytes must be even");
+  return ICAMD_OK;
+}
+
+int icamd_encode_bc6h_device(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t grid_height,
+                             uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images, size_t src_image_stride_bytes,
+                             size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  int rc = bc6h_check_source(codec, src_channels, row_stride_bytes, src_image_stride_bytes, d_src);
+  if (rc != ICAMD_OK) return rc;
+  if (n_images == 0) return ICAMD_OK;
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_channels * 2u)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, 0, 0);
+  ICAMD_HIP(icamd::launch_bc6h_encode(codec, src_channels, P, static_cast<hipStream_t>(hip_stream)), "launch bc6h");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+int icamd_decode_bc6h_device(int codec, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_blocks, void *d_pixels,
+                             void *hip_stream) try {
+  if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
+  if (!bc6h_codec(codec)) return fail(ICAMD_ERR_ARG, "BC6H: the codec must be ICAMD_BC6H_UF16 or ICAMD_BC6H_SF16");
+  if (padding_bytes_per_row % 2u || reinterpret_cast<uintptr_t>(d_pixels) % 2u || dst_image_stride_bytes % 2u)
+    return fail(ICAMD_ERR_ARG, "BC6H decode: padding_bytes_per_row, d_pixels and dst_image_stride_bytes must be even");
+  const uint64_t row_bytes = (uint64_t)width * 8u + padding_bytes_per_row;
+  if (row_bytes > 0xffffffffull) return fail(ICAMD_ERR_ARG, "BC6H decode: a row of 2^32 bytes or more");
+  if (n_images == 0) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
+  uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
+  // as icamd_decode_device: whole images, as many per launch as the 32-bit block index allows; a single image of 2^31 blocks
+  // or more in bands of block rows
+  const uint64_t block_cols = num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols, kMaxBlocks = (1ull << 31) - 1;
+  if (bpi <= kMaxBlocks) {
+    const uint64_t per_launch = kMaxBlocks / bpi;
+    for (uint64_t first = 0; first < n_images; first += per_launch) {
+      rc = decode_launch(codec, 0, height, width, (uint32_t)row_bytes, (uint32_t)std::min<uint64_t>(per_launch, n_images - first),
+                         src_image_stride_bytes, dst_image_stride_bytes, blocks + first * src_image_stride_bytes,
+                         pixels + first * dst_image_stride_bytes, stream);
+      if (rc != ICAMD_OK) return rc;
+    }
+    return ICAMD_OK;
+  }
+  const uint32_t band = (uint32_t)(kMaxBlocks / block_cols);
+  for (uint32_t i = 0; i < n_images; ++i)
+    for (uint64_t r0 = 0; r0 < num_blocks4(height); r0 += band) {
+      const uint32_t rows = (uint32_t)std::min<uint64_t>((uint64_t)band * 4u, (uint64_t)height - r0 * 4u);
+      rc = decode_launch(codec, 0, rows, width, (uint32_t)row_bytes, 1, 0, 0, blocks + i * src_image_stride_bytes + r0 * block_cols * 16u,
+                         pixels + i * dst_image_stride_bytes + r0 * 4u * row_bytes, stream);
+      if (rc != ICAMD_OK) return rc;
+    }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t grid_height,
+                                    uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                    size_t src_image_stride_bytes, size_t blocks_image_stride_bytes, const void *d_src,
+                                    const void *d_blocks, void *d_stats, void *hip_stream) try {
+  if (!d_src || !d_blocks || !d_stats || height == 0 || width == 0) return ICAMD_FALSE;
+  int rc = bc6h_check_source(codec, src_channels, row_stride_bytes, src_image_stride_bytes, d_src);
+  if (rc != ICAMD_OK) return rc;
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_channels * 2u)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  if (grid_height < height || grid_width < width) return fail(ICAMD_ERR_ARG, "block grid smaller than the image");
+  if (reinterpret_cast<uintptr_t>(d_stats) % 8u) return fail(ICAMD_ERR_ARG, "d_stats must be 8-byte aligned");
+  if ((uint64_t)height * width > (1ull << 31)) return fail(ICAMD_ERR_ARG, "more than 2^31 pixels in one image");
+  if (n_images == 0) return ICAMD_OK;
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
+  uint8_t *stats = static_cast<uint8_t *>(d_stats);
+  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
+  // an image of at most 2^31 pixels has fewer than 2^31 blocks: whole images, as many per launch as the 32-bit block index allows
+  const uint64_t bpi = (uint64_t)num_blocks4(height) * num_blocks4(width), per_launch = ((1ull << 31) - 1) / bpi;
+  for (uint64_t first = 0; first < n_images; first += per_launch) {
+    icamd::MetricParams P;
+    P.src = src + first * src_image_stride_bytes;
+    P.blocks = blocks + first * blocks_image_stride_bytes;
+    P.stats = stats + first * sizeof(icamd_error_stats);
+    P.src_image_stride = src_image_stride_bytes;
+    P.blocks_image_stride = blocks_image_stride_bytes;
+    P.height = height;
+    P.width = width;
+    P.block_rows = num_blocks4(height);
+    P.block_cols = num_blocks4(width);
+    P.grid_cols = num_blocks4(grid_width);
+    P.row_stride = row_stride_bytes;
+    P.blocks_per_image = (uint32_t)bpi;
+    P.total_blocks = (uint32_t)(bpi * std::min<uint64_t>(per_launch, n_images - first));
+    P.swap_rb = P.force_gather = 0;
+    P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
+    P.div_cols = icamd::make_fastdiv(P.block_cols);
+    ICAMD_HIP(icamd::launch_bc6h_metric(codec, src_channels, P, stream), "launch bc6h metric");
+  }
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_bc6h_kernel_name(int codec, int src_channels) { return icamd::bc6h_kernel_name(codec, src_channels); }
+const char *icamd_bc6h_metric_kernel_name(int codec, int src_channels) { return icamd::bc6h_metric_kernel_name(codec, src_channels); }
 
 // ---- compressed-domain operations
 
@@ -1747,7 +1864,7 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
   if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
                              codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_EAC_SIGNED_R11 && codec != ICAMD_EAC_SIGNED_RG11 &&
-                             codec != ICAMD_BC7))
+                             codec != ICAMD_BC7 && codec != ICAMD_BC6H_UF16 && codec != ICAMD_BC6H_SF16))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);

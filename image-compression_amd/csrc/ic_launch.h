@@ -191,6 +191,15 @@ const char *bc7_kernel_name(int comps);  // "" unless comps is 3 or 4
 // ICAMD_BC7_MODES_EXTENDED): one fused kernel in place of launch_bc7_encode's, the same GridParams.
 hipError_t launch_bc7_modes_encode(int comps, const GridParams &P, hipStream_t stream);
 const char *bc7_modes_kernel_name(int comps);  // "" unless comps is 3 or 4
+// BC6H (extension, bc6h_kernels.hip; icamd_encode_bc6h_device): codec ICAMD_BC6H_UF16 / ICAMD_BC6H_SF16, chans = halves per source
+// pixel, 3 or 4.  Encode (mode field 00011): GridParams (swap_rb, etc_strategy and force_gather are not read: addresses are 64-bit
+// per lane).  Decode (all fourteen modes): DecodeParams as launch_decode (swap_rb is not read), RGBA16F rows.  Metric: MetricParams
+// as launch_eac11_16_metric; the records get sse[k] and max_abs[k] of the t-domain values, k = 0, 1, 2 (R, G, B).
+hipError_t launch_bc6h_encode(int codec, int chans, const GridParams &P, hipStream_t stream);
+hipError_t launch_bc6h_decode(int codec, const DecodeParams &P, hipStream_t stream);
+hipError_t launch_bc6h_metric(int codec, int chans, const MetricParams &P, hipStream_t stream);
+const char *bc6h_kernel_name(int codec, int chans);         // "" where launch_bc6h_encode has no kernel
+const char *bc6h_metric_kernel_name(int codec, int chans);  // "" where launch_bc6h_metric has no kernel
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

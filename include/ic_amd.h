@@ -286,7 +286,15 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
         * (DDS with the DX10 extension header, dxgiFormat 98; KTX 0x8E8C with GL_RGBA; PVR 15; no PKM) only: no Compressor + format
         * pair selects it; the mip, ETC2-specific and 16-bit EAC entry points answer as for an unknown codec. */
-       ICAMD_BC7 = 32 };
+       ICAMD_BC7 = 32,
+       /* EXTENSION: BC6H (BPTC float; DXGI_FORMAT_BC6H_UF16 = 95 / _SF16 = 96, COMPRESSED_RGB_BPTC_UNSIGNED_FLOAT 0x8E8F /
+        * _SIGNED_FLOAT 0x8E8E): 16 bytes per 4 x 4 block of RGB halves, blocks in raster order as DXT.  PARITY UNPINNED (the
+        * reference has no BC6H).  Value 33 is unassigned.  Half floats in and out only: the codecs are reachable through
+        * icamd_encode_bc6h_device, icamd_decode_bc6h_device, icamd_measure_error_bc6h_device (where the format, the encoder's
+        * definition and the metric are stated in full), icamd_bc6h_kernel_name, icamd_bc6h_metric_kernel_name, icamd_encoded_size
+        * and the container functions (DDS with the DX10 extension header, dxgiFormat 95 / 96; KTX 0x8E8F / 0x8E8E with GL_RGB; no
+        * PKM, no PVR).  Every other entry point refuses them as it refuses an unknown codec. */
+       ICAMD_BC6H_UF16 = 34, ICAMD_BC6H_SF16 = 35 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
@@ -767,7 +775,8 @@ int icamd_gather_blocks_rccl(void *comm, int rank, int world, int root, const si
  * nothing to pin these against.  Host-side byte framing only (no device work), layouts from the public format
  * descriptions (csrc/containers.h): DDS (DXT1 / DXT5, BC4 as ATI1, BC5 as ATI2), KTX 1.1 and PVR v3 (DXT1, DXT5, ETC1,
  * PVRTC2, BC4, BC5, ETC2 RGBA8, ETC2 RGB8, ETC2 RGB8A1), PKM (ETC1 as "PKM 10" type 0, ETC2 RGB8 / RGBA8 / RGB8A1 as "PKM 20" type 1 / 3 / 4;
- * one level).  ICAMD_BC7: DDS with the DX10 extension header (FourCC "DX10" + DDS_HEADER_DXT10, dxgiFormat 98; 148 header bytes
+ * one level).  ICAMD_BC6H_UF16 / _SF16: DDS (DX10 header, dxgiFormat 95 / 96) and KTX (0x8E8F / 0x8E8E, GL_RGB) only.
+ * ICAMD_BC7: DDS with the DX10 extension header (FourCC "DX10" + DDS_HEADER_DXT10, dxgiFormat 98; 148 header bytes
  * where the other codecs have 128), KTX 0x8E8C with GL_RGBA, PVR 15, no PKM.  The signed EAC codecs: see their values.
  * PVRTC4 is not framed (ICAMD_ERR_ARG from icamd_container_write).
  * Level l of a height x width texture is max(1, height >> l) x max(1, width >> l) pixels, its bytes exactly what
@@ -1040,6 +1049,102 @@ int icamd_measure_error_eac11_16_device(int codec, int src_channels, uint32_t he
 /* Names of the __global__ kernels the two launch for a configuration ("" where they refuse it). */
 const char *icamd_eac11_16_kernel_name(int codec, int src_channels);
 const char *icamd_eac11_16_metric_kernel_name(int codec, int src_channels);
+
+/* ---- BC6H: BPTC float (EXTENSION, PARITY UNPINNED: the reference has no BC6H) ----
+ * codec: ICAMD_BC6H_UF16 (unsigned) or ICAMD_BC6H_SF16 (signed).  A sample is an IEEE binary16 BIT PATTERN, little-endian; all
+ * arithmetic below is on integers.  Texel i = 4 y + x.  Blocks are 16 bytes, read as a 128-bit little-endian number, bit 0 first.
+ *
+ * Decode: the whole format.  The independent decoder the tests hold this to is Pillow's (DDS, dxgiFormat 95 / 96); where the
+ * public descriptions and that decoder differ, THIS TEXT STATES WHAT THE DECODER DOES (marked [*]).
+ *   Modes.  Bits 0..1 = 00 or 01: a 2-bit mode field; otherwise bits 0..4 are the mode field.  Fourteen modes; the fields 10011,
+ *     10111, 11011, 11111 are reserved and decode to R = G = B = 0 (A as below).  Per mode (csrc/bc6h_mode_tables.inc holds the
+ *     placement of every header bit; tests/bc6h_oracle.py states it a second time):
+ *       field  endpoint bits  delta bits R G B  transformed  subsets      field  endpoint bits  delta bits  transformed  subsets
+ *       00     10             5 5 5             yes          2            11010  8              5 5 6       yes          2
+ *       01     7              6 6 6             yes          2            11110  6              (6 6 6)     no           2
+ *       00010  11             5 4 4             yes          2            00011  10             (10 each)   no           1
+ *       00110  11             4 5 4             yes          2            00111  11             9 9 9       yes          1
+ *       01010  11             4 4 5             yes          2            01011  12             8 8 8       yes          1
+ *       01110  9              5 5 5             yes          2            01111  16             4 4 4       yes          1
+ *       10010  8              6 5 5             yes          2
+ *       10110  8              5 6 5             yes          2
+ *     Two-subset modes: the header is 82 bits, the 5-bit partition its last field; partitions and anchors are the first 32
+ *     entries of BC7's two-subset tables; indices are 3 bits (2 bits for texel 0 and for the second subset's anchor), weights
+ *     {0,9,18,27,37,46,55,64}.  One-subset modes: the header is 65 bits; indices are 4 bits (3 for texel 0), weights BC7's 4-bit
+ *     set.  Subset 0 interpolates endpoints 0 and 1, subset 1 endpoints 2 and 3.
+ *   Endpoints, per colour, bits = the mode's endpoint bits.  Endpoint 0 is the stored field; in the signed format it is
+ *     sign-extended from `bits`.  Transformed modes: e_k = (e_0 + sext(delta_k)) & (2^bits - 1), the delta sign-extended from
+ *     its own width; in the signed format e_k is then read as a 16-bit two's-complement number -- it is NOT sign-extended from
+ *     `bits`, so only the 16-bit mode sees negative transformed endpoints [*].  Untransformed modes: the stored fields, in the
+ *     signed format each sign-extended from `bits`.
+ *   Un-quantise c.  Unsigned: bits >= 15: c; c == 0: 0; c == 2^bits - 1: 0xFFFF; else ((c << 16) + 0x8000) >> bits.
+ *     Signed: bits >= 16: c; otherwise on |c|: 0 -> 0; >= 2^(bits-1) - 1 -> 0x7FFF; else ((|c| << 15) + 0x4000) >> (bits - 1);
+ *     the sign is put back.
+ *   Interpolate: x = (a (64 - w) + b w) >> 6, an arithmetic shift, WITHOUT a rounding term [*].
+ *   Finish: unsigned (x * 31) >> 6; signed x < 0 ? (((-x) * 31) >> 5) | 0x8000 : (x * 31) >> 5.  The result is the half's bits.
+ *   Known answers: the unsigned block 03 | e << 5 | e << 15 | ... (mode field 00011, all six endpoints e, indices 0) decodes
+ *     e = 100 to 3115, 300 to 9315, 400 to 12415, 480 to 14895, 495 to 15360 (1.0), 1023 to 31743 (0x7BFF).
+ *
+ * Encode, a DEFINITION (restated in numpy in tests/bc6h_oracle.py; the kernels are bit-exact against it).  It writes mode field
+ * 00011 only: one subset, 10-bit endpoints stored directly, 4-bit indices.  The source has src_channels (3 or 4) halves per
+ * pixel, R, G, B = samples 0, 1, 2 (the fourth is not read).  Grids, clamp-to-edge replication, the padded-grid fetch, strides
+ * and batches as for ICAMD_BC7.
+ *   The t domain.  A half h with magnitude m = h & 0x7FFF has the target t: unsigned format: 0 for a NaN (m > 0x7C00) and for
+ *     any h with the sign bit set, else min(m, 0x7BFF); signed format: 0 for a NaN, else +-min(m, 0x7BFF) (-0 gives 0).  t is
+ *     monotone in the float's value.  D(q) = t(finish(un-quantise(q))) at 10 bits for q in 0..1023 (unsigned) or -511..511
+ *     (signed; -512 is never written): 0, 31 q + 15, ..., D(1023) = 31743; signed +-(62 |q| + 31), D(+-511) = +-31743.
+ *   1. Targets, as step 1 of ICAMD_BC7 over the three channels of t_p: lo_c, hi_c; c* = the channel with the largest hi - lo
+ *      (ties: R before G before B); T0 = lo, T1 = hi; for c != c*, T0_c and T1_c are exchanged if
+ *      16 sum_p t_p[c*] t_p[c] - (sum_p t_p[c*]) (sum_p t_p[c]) < 0 (64-bit sums).
+ *   2. Quantise, per channel: E_c = the smallest q that minimises |D(q) - T_c|.  (The kernels try T / 31 resp. T / 62, truncating,
+ *      and its two neighbours; tests/test_bc6h_host.py proves that equal for every T.)
+ *   3. Indices.  pal_k[c] = t(finish(((64 - w_k) U0_c + w_k U1_c) >> 6)) with U = un-quantise(E): exactly what the decoder
+ *      makes of index k (no rounding term, see Decode).  Texel p takes the smallest k that minimises sum_c (pal_k[c] - t_p[c])^2.
+ *      Widths: one channel's square is below 2^32 in both formats; a texel's sum is below 2^32 in the unsigned format
+ *      (3 * 31743^2) and needs 64 bits in the signed one (3 * 63486^2); sse, the sum of the sixteen minima, is 64-bit.
+ *   4. One refit: step 4 of ICAMD_BC7 on t_p (three channels), T0', T1' clamped to 0..31743 (unsigned) or -31743..31743 (signed;
+ *      rdiv is a floor division); steps 2 and 3 run on T' and replace the first pass only on a STRICTLY smaller sse.
+ *   5. Anchor.  If k_0 >= 8: E0 and E1 are exchanged and every k becomes 15 - k (the interpolation is symmetric: the decoded
+ *      texels do not change).
+ *   6. Pack: bits 0..4 = 00011 (the byte 0x03 | ...); E0 of R, G, B at bits 5, 15, 25 and E1 of R, G, B at bits 35, 45, 55
+ *      (10 bits each, two's complement in the signed format); k_0 in 3 bits at bit 65; k_1..k_15 in 4 bits each.
+ *   Example: sixteen texels (1.0, 0.5, 0.25) = halves (0x3C00, 0x3800, 0x3400), unsigned, give
+ *     e3 3d e7 5a 7b cf b9 d6 00 .. 00: t = (15360, 14336, 13312), E0 = E1 = (495, 462, 429) with D = 15360, 14337, 13314 (sse 80),
+ *     every k = 0, a = 65536 and b = c = 0: det = 0, no refit.  The signed format gives e3 9e 73 ac b9 e7 1c 6b 00 .. 00:
+ *     E = (247, 231, 214) with D = 15345, 14353, 13299 (sse 10928).
+ *
+ * Metric: per image and channel k = 0, 1, 2 (R, G, B; entry 3 is 0), sse[k] and max_abs[k] of d = t(decoded half) - t(source
+ * half) with the encoder's map t of the codec's format applied to both, over the pixels inside the image. */
+/* icamd_encode_bc6h_device: arguments as icamd_encode_eac11_16_device.  Status, in this order: ICAMD_FALSE for a null pointer or
+ * height or width 0; ICAMD_ERR_ARG for a codec other than the two, src_channels other than 3 or 4, or an odd d_src,
+ * row_stride_bytes or src_image_stride_bytes (samples are 2-byte aligned); ICAMD_OK for n_images == 0; ICAMD_ERR_ARG for
+ * row_stride_bytes < width * src_channels * 2.  All answered before a device is needed.  d_dst: any alignment,
+ * icamd_encoded_size(codec, grid) bytes per image.  No allocation, no synchronisation. */
+int icamd_encode_bc6h_device(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t grid_height,
+                             uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_src, void *d_dst, void *hip_stream);
+/* icamd_decode_bc6h_device: arguments as icamd_decode_eac11_16_device.  Writes `height` rows of width RGBA16F pixels (8 bytes:
+ * R, G, B as decoded, A = 0x3C00 = 1.0) + padding_bytes_per_row bytes; padding bytes are left alone.  ICAMD_FALSE for a null
+ * pointer or an empty image; ICAMD_ERR_ARG for a codec other than the two, an odd padding_bytes_per_row, d_pixels or
+ * dst_image_stride_bytes, or a row of 2^32 bytes or more; ICAMD_OK for n_images == 0.  d_blocks: any alignment.  No allocation,
+ * no synchronisation. */
+int icamd_decode_bc6h_device(int codec, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row, uint32_t n_images,
+                             size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                             const void *d_blocks, void *d_pixels, void *hip_stream);
+/* icamd_measure_error_bc6h_device: arguments as icamd_measure_error_eac11_16_device; fills n_images icamd_error_stats records
+ * (Metric, above).  ICAMD_FALSE for a null pointer or an empty image; ICAMD_ERR_ARG for a codec other than the two, src_channels
+ * the encoder refuses, an odd d_src, row_stride_bytes or src_image_stride_bytes, a row stride smaller than a row, a grid smaller
+ * than the image, a d_stats that is not 8-byte aligned, or (uint64)height * width > 2^31 (a squared difference is below 2^32,
+ * so every sum stays below 2^63); ICAMD_OK for n_images == 0.  All answered before a device is needed.  No allocation and no
+ * synchronisation (the zeroing of d_stats is stream-ordered work of the call). */
+int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height, uint32_t width,
+                                    uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                    size_t src_image_stride_bytes, size_t blocks_image_stride_bytes,
+                                    const void *d_src, const void *d_blocks, void *d_stats, void *hip_stream);
+/* Names of the __global__ kernels the two launch for a configuration ("" where they refuse it). */
+const char *icamd_bc6h_kernel_name(int codec, int src_channels);
+const char *icamd_bc6h_metric_kernel_name(int codec, int src_channels);
 
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
