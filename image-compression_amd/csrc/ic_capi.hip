@@ -21,6 +21,7 @@
 
 #include "codec_info.h"
 #include "containers.h"
+#include "decode_plan.h"
 #include "ic_abi.h"
 #include "ic_launch.h"
 
@@ -232,7 +233,6 @@ bool codec_accepts_components(int codec, int comps) {
 }
 // The one- and two-channel codecs (R, or R and G, of 1..4-byte pixels; R8 / RG8 rows out): BC4 / BC5 and EAC R11 / RG11.
 bool plane_codec(int codec) { return codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
-bool two_plane_codec(int codec) { return codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11; }
 bool eac11_codec(int codec) { return codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
 
 // The sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650): a square power of two of at least 8 x 8 (for a square
@@ -862,38 +862,37 @@ int icamd_compress_and_pad(int compressor, int etc_strategy, int format, uint32_
                               padded_width, padding_bytes_per_row, buffer, out, out_size);
 } ICAMD_ABI_CATCH
 
-// One launch: fewer than 2^31 blocks (the decode kernels index blocks with 32 bits).
-static int decode_launch(int codec, int swap_rb, uint32_t height, uint32_t width, uint32_t row_stride,
-                         uint32_t n_images, size_t src_image_stride, size_t dst_image_stride, const uint8_t *blocks,
-                         uint8_t *pixels, hipStream_t stream) {
-  icamd::DecodeParams P;
-  P.blocks = blocks;
-  P.pixels = pixels;
-  P.src_image_stride = src_image_stride;
-  P.dst_image_stride = dst_image_stride;
-  P.height = height;
-  P.width = width;
-  P.block_rows = num_blocks4(height);
-  P.block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width);  // PVRTC 2 bpp: 8x4-pixel blocks
-  P.row_stride = row_stride;
-  P.blocks_per_image = P.block_rows * P.block_cols;
-  P.total_blocks = P.blocks_per_image * n_images;
-  P.swap_rb = swap_rb ? 1u : 0u;
-  P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
-  P.div_cols = icamd::make_fastdiv(P.block_cols);
-  if (codec == ICAMD_ETC2_RGBA8)
-    ICAMD_HIP(icamd::launch_etc2_decode(P, stream), "launch etc2 decode");
-  else if (codec == ICAMD_ETC2_RGB8)
-    ICAMD_HIP(icamd::launch_etc2_rgb8_decode(P, stream), "launch etc2 rgb8 decode");
-  else if (codec == ICAMD_ETC2_RGB8A1)
-    ICAMD_HIP(icamd::launch_etc2_a1_decode(P, stream), "launch etc2 rgb8a1 decode");
-  else if (codec == ICAMD_BC7)
-    ICAMD_HIP(icamd::launch_bc7_decode(P, stream), "launch bc7 decode");
-  else if (codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16)  // (icamd_decode_bc6h_device only: RGBA16F rows)
-    ICAMD_HIP(icamd::launch_bc6h_decode(codec, P, stream), "launch bc6h decode");
-  else
-    ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
-  return ICAMD_OK;
+// Blocks per block row of a stored image.  PVRTC 2 bpp: 8x4-pixel blocks
+static uint32_t codec_block_cols(int codec, uint32_t width) { return codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width); }
+
+// The launches of a checked decode call, one per piece of decode_plan.h (the decode kernels index blocks with 32 bits): whole
+// images, or bands of block rows of a single image of 2^31 blocks or more.
+static int decode_pieces(int codec, int swap_rb, uint32_t height, uint32_t width, uint32_t row_stride, uint32_t n_images,
+                         size_t src_image_stride, size_t dst_image_stride, const void *d_blocks, void *d_pixels, void *hip_stream) {
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
+  uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
+  const uint32_t block_cols = codec_block_cols(codec, width);
+  const uint64_t block_row_bytes = (uint64_t)block_cols * icamd::codec_block_bytes(codec);
+  return icamd::for_each_launch_piece(height, block_cols, n_images, [&](const icamd::LaunchPiece &piece) -> int {
+    const icamd::DecodeParams P = icamd::decode_params(
+        blocks + piece.first_image * src_image_stride + piece.first_block_row * block_row_bytes,
+        pixels + piece.first_image * dst_image_stride + (uint64_t)piece.first_block_row * 4u * row_stride, src_image_stride,
+        dst_image_stride, piece.pixel_rows, width, block_cols, row_stride, piece.image_count, swap_rb != 0);
+    if (codec == ICAMD_ETC2_RGBA8)
+      ICAMD_HIP(icamd::launch_etc2_decode(P, stream), "launch etc2 decode");
+    else if (codec == ICAMD_ETC2_RGB8)
+      ICAMD_HIP(icamd::launch_etc2_rgb8_decode(P, stream), "launch etc2 rgb8 decode");
+    else if (codec == ICAMD_ETC2_RGB8A1)
+      ICAMD_HIP(icamd::launch_etc2_a1_decode(P, stream), "launch etc2 rgb8a1 decode");
+    else if (codec == ICAMD_BC7)
+      ICAMD_HIP(icamd::launch_bc7_decode(P, stream), "launch bc7 decode");
+    else if (codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16)  // (icamd_decode_bc6h_device only: RGBA16F rows)
+      ICAMD_HIP(icamd::launch_bc6h_decode(codec, P, stream), "launch bc6h decode");
+    else
+      ICAMD_HIP(icamd::launch_decode(codec, P, stream), "launch decode");
+    return ICAMD_OK;
+  });
 }
 
 int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
@@ -908,22 +907,13 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
   if (n_images == 0) return ICAMD_OK;
   int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
-  uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
+  const uint32_t row_stride = width * icamd::codec_decoded_pixel_bytes(codec) + padding_bytes_per_row;
   if (plane) {
     // EXTENSION (include/ic_amd.h ICAMD_BC4, ICAMD_EAC_R11): R8 / RG8 rows; 64-bit addressing and chunked grids, so no banding is needed
-    icamd::Bc45DecodeParams P;
-    P.blocks = blocks;
-    P.pixels = pixels;
-    P.src_image_stride = src_image_stride_bytes;
-    P.dst_image_stride = dst_image_stride_bytes;
-    P.height = height;
-    P.width = width;
-    P.block_rows = num_blocks4(height);
-    P.block_cols = num_blocks4(width);
-    P.row_stride = width * (two_plane_codec(codec) ? 2u : 1u) + padding_bytes_per_row;
-    P.log2_tile_cols = P.tile_row0 = 0;
+    const icamd::Bc45DecodeParams P =
+        icamd::bc45_decode_params(static_cast<const uint8_t *>(d_blocks), static_cast<uint8_t *>(d_pixels), src_image_stride_bytes,
+                                  dst_image_stride_bytes, height, width, row_stride);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     if (eac11_codec(codec))
       ICAMD_HIP(icamd::launch_eac11_decode(codec, n_images, P, stream), "launch eac r11 / rg11 decode");
     else
@@ -936,35 +926,11 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
     // all): the sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650), RGBA8 out, no row padding, one launch per <= 2^30 blocks
     if (!is_pow2(width) || width != height || width < 8 || padding_bytes_per_row != 0) return ICAMD_FALSE;
     swap_rb = 0;
+    if ((uint64_t)num_blocks4(height) * codec_block_cols(codec, width) > icamd::kMaxLaunchBlocks)
+      return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
   }
-  const uint32_t block_bytes = icamd::codec_block_bytes(codec);
-  const bool rgba_rows = codec == ICAMD_DXT5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_BC7 || pvrtc;
-  const uint32_t row_stride = width * (rgba_rows ? 4u : 3u) + padding_bytes_per_row;
-  const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
-  const uint64_t kMaxBlocks = (1ull << 31) - 1;
-  if (pvrtc && bpi > kMaxBlocks) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
-  if (bpi <= kMaxBlocks) {  // whole images, as many per launch as the 32-bit block index allows
-    const uint64_t per_launch = std::max<uint64_t>(1, kMaxBlocks / bpi);
-    for (uint64_t first = 0; first < n_images; first += per_launch) {
-      const uint32_t count = (uint32_t)std::min<uint64_t>(per_launch, n_images - first);
-      rc = decode_launch(codec, swap_rb, height, width, row_stride, count, src_image_stride_bytes,
-                         dst_image_stride_bytes, blocks + first * src_image_stride_bytes,
-                         pixels + first * dst_image_stride_bytes, stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-    return ICAMD_OK;
-  }
-  // a single image of 2^31 blocks or more: bands of block rows (blocks are row-major, helper.h:218-262)
-  const uint32_t band = (uint32_t)(kMaxBlocks / block_cols);
-  for (uint32_t i = 0; i < n_images; ++i)
-    for (uint64_t r0 = 0; r0 < num_blocks4(height); r0 += band) {
-      const uint32_t rows = (uint32_t)std::min<uint64_t>((uint64_t)band * 4u, (uint64_t)height - r0 * 4u);
-      rc = decode_launch(codec, swap_rb, rows, width, row_stride, 1, 0, 0,
-                         blocks + i * src_image_stride_bytes + r0 * block_cols * block_bytes,
-                         pixels + i * dst_image_stride_bytes + r0 * 4u * row_stride, stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-  return ICAMD_OK;
+  return decode_pieces(codec, swap_rb, height, width, row_stride, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_blocks,
+                       d_pixels, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_decompress(int compressor, int format, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
@@ -995,31 +961,28 @@ int icamd_pvrtc2_decompress(uint32_t size, const uint8_t *blocks, size_t blocks_
 
 // ---- quality metric (extension, include/ic_amd.h): blocks against source pixels
 
-// One launch: fewer than 2^31 blocks over the images' own block grids (height x width is the part of the image this launch
-// covers; grid_cols the pitch of a block row of the stored grid).
-static int metric_launch(int codec, int comps, int swap_rb, uint32_t height, uint32_t width, uint32_t grid_cols,
-                         uint32_t row_stride, uint32_t n_images, size_t src_image_stride, size_t blocks_image_stride,
-                         const uint8_t *src, const uint8_t *blocks, uint8_t *stats, hipStream_t stream) {
-  icamd::MetricParams P;
-  P.src = src;
-  P.blocks = blocks;
-  P.stats = stats;
-  P.src_image_stride = src_image_stride;
-  P.blocks_image_stride = blocks_image_stride;
-  P.height = height;
-  P.width = width;
-  P.block_rows = num_blocks4(height);
-  P.block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width);  // PVRTC 2 bpp: 8x4-pixel blocks
-  P.grid_cols = grid_cols;
-  P.row_stride = row_stride;
-  P.blocks_per_image = P.block_rows * P.block_cols;
-  P.total_blocks = P.blocks_per_image * n_images;
-  P.swap_rb = swap_rb ? 1u : 0u;
-  P.force_gather = (uint64_t)row_stride * 3u + 8192u >= (1ull << 32) ? 1u : 0u;  // as launch_tiled
-  P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
-  P.div_cols = icamd::make_fastdiv(P.block_cols);
-  ICAMD_HIP(icamd::launch_metric(codec, comps, P, stream), "launch metric");
-  return ICAMD_OK;
+// The launches of a checked metric call: the records are zeroed, then one launch per piece of decode_plan.h over the images' own
+// block grids (grid_width gives the pitch of a block row of the stored grid).  The bands of a single image of 2^31 blocks or more
+// all add to the image's one record.
+using MetricLauncher = hipError_t (*)(int codec, int comps, const icamd::MetricParams &P, hipStream_t stream);
+static int metric_pieces(MetricLauncher launch, const char *what, int codec, int comps, int swap_rb, uint32_t height, uint32_t width,
+                         uint32_t grid_width, uint32_t row_stride, uint32_t n_images, size_t src_image_stride,
+                         size_t blocks_image_stride, const void *d_src, const void *d_blocks, void *d_stats, void *hip_stream) {
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
+  uint8_t *stats = static_cast<uint8_t *>(d_stats);
+  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
+  const uint32_t block_cols = codec_block_cols(codec, width), grid_cols = num_blocks4(grid_width);
+  const uint64_t grid_row_bytes = (uint64_t)grid_cols * icamd::codec_block_bytes(codec);
+  return icamd::for_each_launch_piece(height, block_cols, n_images, [&](const icamd::LaunchPiece &piece) -> int {
+    const icamd::MetricParams P = icamd::metric_params(
+        src + piece.first_image * src_image_stride + (uint64_t)piece.first_block_row * 4u * row_stride,
+        blocks + piece.first_image * blocks_image_stride + piece.first_block_row * grid_row_bytes,
+        stats + piece.first_image * sizeof(icamd_error_stats), src_image_stride, blocks_image_stride, piece.pixel_rows, width,
+        block_cols, grid_cols, row_stride, piece.image_count, swap_rb != 0);
+    ICAMD_HIP(launch(codec, comps, P, stream), what);
+    return ICAMD_OK;
+  });
 }
 
 int icamd_measure_error_device(int codec, int src_components, int swap_rb, uint32_t height, uint32_t width,
@@ -1037,46 +1000,19 @@ int icamd_measure_error_device(int codec, int src_components, int swap_rb, uint3
   if (grid_height < height || grid_width < width) return fail(ICAMD_ERR_ARG, "block grid smaller than the image");
   if (reinterpret_cast<uintptr_t>(d_stats) % 8u) return fail(ICAMD_ERR_ARG, "d_stats must be 8-byte aligned");
   if ((uint64_t)height * width > (1ull << 47)) return fail(ICAMD_ERR_ARG, "more than 2^47 pixels in one image");
-  const uint64_t kMaxBlocks = (1ull << 31) - 1;
-  const uint64_t block_cols = codec == ICAMD_PVRTC2 ? width / 8u : num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols;
   if (pvrtc) {  // what the PVRTC decoders need (icamd_decode_device), and the encoder's row rule
     if (!is_pow2(width) || width != height || width < 8 || grid_height != height || grid_width != width ||
         row_stride_bytes != width * 4u)
       return ICAMD_FALSE;
-    if (bpi > kMaxBlocks) return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
+    if ((uint64_t)num_blocks4(height) * codec_block_cols(codec, width) > icamd::kMaxLaunchBlocks)
+      return fail(ICAMD_ERR_ARG, "PVRTC texture too large to decode");
     swap_rb = 0;
   }
   if (n_images == 0) return ICAMD_OK;
-  int rc = require_device();
+  const int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
-  uint8_t *stats = static_cast<uint8_t *>(d_stats);
-  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
-  const uint32_t grid_cols = num_blocks4(grid_width), block_bytes = icamd::codec_block_bytes(codec);
-  if (bpi <= kMaxBlocks) {  // whole images, as many per launch as the 32-bit block index allows
-    const uint64_t per_launch = std::max<uint64_t>(1, kMaxBlocks / bpi);
-    for (uint64_t first = 0; first < n_images; first += per_launch) {
-      const uint32_t count = (uint32_t)std::min<uint64_t>(per_launch, n_images - first);
-      rc = metric_launch(codec, src_components, swap_rb, height, width, grid_cols, row_stride_bytes, count,
-                         src_image_stride_bytes, blocks_image_stride_bytes, src + first * src_image_stride_bytes,
-                         blocks + first * blocks_image_stride_bytes, stats + first * sizeof(icamd_error_stats), stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-    return ICAMD_OK;
-  }
-  // a single image of 2^31 blocks or more: bands of block rows, all adding to the image's one record
-  const uint32_t band = (uint32_t)(kMaxBlocks / block_cols);
-  for (uint32_t i = 0; i < n_images; ++i)
-    for (uint64_t r0 = 0; r0 < num_blocks4(height); r0 += band) {
-      const uint32_t rows = (uint32_t)std::min<uint64_t>((uint64_t)band * 4u, (uint64_t)height - r0 * 4u);
-      rc = metric_launch(codec, src_components, swap_rb, rows, width, grid_cols, row_stride_bytes, 1, 0, 0,
-                         src + i * src_image_stride_bytes + r0 * 4u * row_stride_bytes,
-                         blocks + i * blocks_image_stride_bytes + r0 * grid_cols * block_bytes,
-                         stats + (size_t)i * sizeof(icamd_error_stats), stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-  return ICAMD_OK;
+  return metric_pieces(icamd::launch_metric, "launch metric", codec, src_components, swap_rb, height, width, grid_width,
+                       row_stride_bytes, n_images, src_image_stride_bytes, blocks_image_stride_bytes, d_src, d_blocks, d_stats, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_measure_error(int compressor, int format, uint32_t height, uint32_t width, uint32_t padding_bytes_per_row,
@@ -1164,17 +1100,9 @@ int icamd_decode_eac11_16_device(int codec, uint32_t height, uint32_t width, uin
   if (n_images == 0) return ICAMD_OK;
   const int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  icamd::Bc45DecodeParams P;
-  P.blocks = static_cast<const uint8_t *>(d_blocks);
-  P.pixels = static_cast<uint8_t *>(d_pixels);
-  P.src_image_stride = src_image_stride_bytes;
-  P.dst_image_stride = dst_image_stride_bytes;
-  P.height = height;
-  P.width = width;
-  P.block_rows = num_blocks4(height);
-  P.block_cols = num_blocks4(width);
-  P.row_stride = (uint32_t)row_bytes;
-  P.log2_tile_cols = P.tile_row0 = 0;
+  const icamd::Bc45DecodeParams P =
+      icamd::bc45_decode_params(static_cast<const uint8_t *>(d_blocks), static_cast<uint8_t *>(d_pixels), src_image_stride_bytes,
+                                dst_image_stride_bytes, height, width, (uint32_t)row_bytes);
   ICAMD_HIP(icamd::launch_eac11_16_decode(codec, n_images, P, static_cast<hipStream_t>(hip_stream)), "launch 16-bit eac r11 / rg11 decode");
   return ICAMD_OK;
 } ICAMD_ABI_CATCH
@@ -1194,33 +1122,9 @@ int icamd_measure_error_eac11_16_device(int codec, int src_channels, uint32_t he
   if (n_images == 0) return ICAMD_OK;
   rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
-  uint8_t *stats = static_cast<uint8_t *>(d_stats);
-  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
-  // an image of at most 2^31 pixels has fewer than 2^31 blocks: whole images, as many per launch as the 32-bit block index allows
-  const uint64_t bpi = (uint64_t)num_blocks4(height) * num_blocks4(width), per_launch = ((1ull << 31) - 1) / bpi;
-  for (uint64_t first = 0; first < n_images; first += per_launch) {
-    icamd::MetricParams P;
-    P.src = src + first * src_image_stride_bytes;
-    P.blocks = blocks + first * blocks_image_stride_bytes;
-    P.stats = stats + first * sizeof(icamd_error_stats);
-    P.src_image_stride = src_image_stride_bytes;
-    P.blocks_image_stride = blocks_image_stride_bytes;
-    P.height = height;
-    P.width = width;
-    P.block_rows = num_blocks4(height);
-    P.block_cols = num_blocks4(width);
-    P.grid_cols = num_blocks4(grid_width);
-    P.row_stride = row_stride_bytes;
-    P.blocks_per_image = (uint32_t)bpi;
-    P.total_blocks = (uint32_t)(bpi * std::min<uint64_t>(per_launch, n_images - first));
-    P.swap_rb = P.force_gather = 0;
-    P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
-    P.div_cols = icamd::make_fastdiv(P.block_cols);
-    ICAMD_HIP(icamd::launch_eac11_16_metric(codec, src_channels, P, stream), "launch 16-bit eac metric");
-  }
-  return ICAMD_OK;
+  // an image of at most 2^31 pixels has fewer than 2^31 blocks: whole images only
+  return metric_pieces(icamd::launch_eac11_16_metric, "launch 16-bit eac metric", codec, src_channels, 0, height, width, grid_width, row_stride_bytes,
+                       n_images, src_image_stride_bytes, blocks_image_stride_bytes, d_src, d_blocks, d_stats, hip_stream);
 } ICAMD_ABI_CATCH
 
 const char *icamd_eac11_16_kernel_name(int codec, int src_channels) { return icamd::eac11_16_kernel_name(codec, src_channels); }
@@ -1264,36 +1168,13 @@ int icamd_decode_bc6h_device(int codec, uint32_t height, uint32_t width, uint32_
   if (!bc6h_codec(codec)) return fail(ICAMD_ERR_ARG, "BC6H: the codec must be ICAMD_BC6H_UF16 or ICAMD_BC6H_SF16");
   if (padding_bytes_per_row % 2u || reinterpret_cast<uintptr_t>(d_pixels) % 2u || dst_image_stride_bytes % 2u)
     return fail(ICAMD_ERR_ARG, "BC6H decode: padding_bytes_per_row, d_pixels and dst_image_stride_bytes must be even");
-  const uint64_t row_bytes = (uint64_t)width * 8u + padding_bytes_per_row;
+  const uint64_t row_bytes = (uint64_t)width * icamd::codec_decoded_pixel_bytes(codec) + padding_bytes_per_row;
   if (row_bytes > 0xffffffffull) return fail(ICAMD_ERR_ARG, "BC6H decode: a row of 2^32 bytes or more");
   if (n_images == 0) return ICAMD_OK;
-  int rc = require_device();
+  const int rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const uint8_t *blocks = static_cast<const uint8_t *>(d_blocks);
-  uint8_t *pixels = static_cast<uint8_t *>(d_pixels);
-  // as icamd_decode_device: whole images, as many per launch as the 32-bit block index allows; a single image of 2^31 blocks
-  // or more in bands of block rows
-  const uint64_t block_cols = num_blocks4(width), bpi = (uint64_t)num_blocks4(height) * block_cols, kMaxBlocks = (1ull << 31) - 1;
-  if (bpi <= kMaxBlocks) {
-    const uint64_t per_launch = kMaxBlocks / bpi;
-    for (uint64_t first = 0; first < n_images; first += per_launch) {
-      rc = decode_launch(codec, 0, height, width, (uint32_t)row_bytes, (uint32_t)std::min<uint64_t>(per_launch, n_images - first),
-                         src_image_stride_bytes, dst_image_stride_bytes, blocks + first * src_image_stride_bytes,
-                         pixels + first * dst_image_stride_bytes, stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-    return ICAMD_OK;
-  }
-  const uint32_t band = (uint32_t)(kMaxBlocks / block_cols);
-  for (uint32_t i = 0; i < n_images; ++i)
-    for (uint64_t r0 = 0; r0 < num_blocks4(height); r0 += band) {
-      const uint32_t rows = (uint32_t)std::min<uint64_t>((uint64_t)band * 4u, (uint64_t)height - r0 * 4u);
-      rc = decode_launch(codec, 0, rows, width, (uint32_t)row_bytes, 1, 0, 0, blocks + i * src_image_stride_bytes + r0 * block_cols * 16u,
-                         pixels + i * dst_image_stride_bytes + r0 * 4u * row_bytes, stream);
-      if (rc != ICAMD_OK) return rc;
-    }
-  return ICAMD_OK;
+  return decode_pieces(codec, 0, height, width, (uint32_t)row_bytes, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_blocks,
+                       d_pixels, hip_stream);
 } ICAMD_ABI_CATCH
 
 int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t grid_height,
@@ -1311,33 +1192,9 @@ int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height
   if (n_images == 0) return ICAMD_OK;
   rc = require_device();
   if (rc != ICAMD_OK) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const uint8_t *src = static_cast<const uint8_t *>(d_src), *blocks = static_cast<const uint8_t *>(d_blocks);
-  uint8_t *stats = static_cast<uint8_t *>(d_stats);
-  ICAMD_HIP(icamd::launch_metric_clear(stats, n_images, stream), "launch metric clear");
-  // an image of at most 2^31 pixels has fewer than 2^31 blocks: whole images, as many per launch as the 32-bit block index allows
-  const uint64_t bpi = (uint64_t)num_blocks4(height) * num_blocks4(width), per_launch = ((1ull << 31) - 1) / bpi;
-  for (uint64_t first = 0; first < n_images; first += per_launch) {
-    icamd::MetricParams P;
-    P.src = src + first * src_image_stride_bytes;
-    P.blocks = blocks + first * blocks_image_stride_bytes;
-    P.stats = stats + first * sizeof(icamd_error_stats);
-    P.src_image_stride = src_image_stride_bytes;
-    P.blocks_image_stride = blocks_image_stride_bytes;
-    P.height = height;
-    P.width = width;
-    P.block_rows = num_blocks4(height);
-    P.block_cols = num_blocks4(width);
-    P.grid_cols = num_blocks4(grid_width);
-    P.row_stride = row_stride_bytes;
-    P.blocks_per_image = (uint32_t)bpi;
-    P.total_blocks = (uint32_t)(bpi * std::min<uint64_t>(per_launch, n_images - first));
-    P.swap_rb = P.force_gather = 0;
-    P.div_bpi = icamd::make_fastdiv(P.blocks_per_image);
-    P.div_cols = icamd::make_fastdiv(P.block_cols);
-    ICAMD_HIP(icamd::launch_bc6h_metric(codec, src_channels, P, stream), "launch bc6h metric");
-  }
-  return ICAMD_OK;
+  // an image of at most 2^31 pixels has fewer than 2^31 blocks: whole images only
+  return metric_pieces(icamd::launch_bc6h_metric, "launch bc6h metric", codec, src_channels, 0, height, width, grid_width, row_stride_bytes,
+                       n_images, src_image_stride_bytes, blocks_image_stride_bytes, d_src, d_blocks, d_stats, hip_stream);
 } ICAMD_ABI_CATCH
 
 const char *icamd_bc6h_kernel_name(int codec, int src_channels) { return icamd::bc6h_kernel_name(codec, src_channels); }

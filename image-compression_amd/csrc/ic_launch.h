@@ -2,8 +2,9 @@
 // (dxt_kernels.hip, etc1_kernels.hip, pvrtc_kernels.hip, decode_kernels.hip, blockops_kernels.hip); called by ic_capi.hip.
 // Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC), blockops_plan.h (Pad, Downsample and
 // the chunks of CopySubimage, CreateSolid and the transcode), mip_plan.h (the passes, grids and kernels of the mip chains) and
-// etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape) and
-// dxt_plan.h (the workgroup size of the DXT encoders); the launchers here run what a plan says.
+// etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape),
+// dxt_plan.h (the workgroup size of the DXT encoders) and decode_plan.h (the pieces of a decode or metric call, fewer than 2^31
+// blocks each); the launchers here run what a plan says.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -133,6 +134,27 @@ struct DecodeParams {
   uint32_t blocks_per_image, total_blocks, swap_rb;
   FastDiv div_bpi, div_cols;
 };
+// One launch (a piece of decode_plan.h): n_images images of height x width pixels, block_cols blocks per block row.
+inline DecodeParams decode_params(const uint8_t *blocks, uint8_t *pixels, uint64_t src_image_stride, uint64_t dst_image_stride,
+                                  uint32_t height, uint32_t width, uint32_t block_cols, uint32_t row_stride, uint32_t n_images,
+                                  bool swap_rb) {
+  DecodeParams P;
+  P.blocks = blocks;
+  P.pixels = pixels;
+  P.src_image_stride = src_image_stride;
+  P.dst_image_stride = dst_image_stride;
+  P.height = height;
+  P.width = width;
+  P.block_rows = (height + 3u) / 4u;
+  P.block_cols = block_cols;
+  P.row_stride = row_stride;
+  P.blocks_per_image = P.block_rows * block_cols;
+  P.total_blocks = P.blocks_per_image * n_images;
+  P.swap_rb = swap_rb ? 1u : 0u;
+  P.div_bpi = make_fastdiv(P.blocks_per_image);
+  P.div_cols = make_fastdiv(block_cols);
+  return P;
+}
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
 hipError_t launch_etc2_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGBA8 -> RGBA8 rows (etc2_kernels.hip)
 hipError_t launch_etc2_rgb8_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGB8 -> RGB888 rows (etc2_rgb8_kernels.hip)
@@ -151,6 +173,30 @@ struct MetricParams {
   uint32_t force_gather;  // rows too long for 32-bit row offsets: every block gathers with 64-bit addresses
   FastDiv div_bpi, div_cols;
 };
+// One launch (a piece of decode_plan.h), as decode_params; force_gather is the encoders' rule (encode_tile_shape).
+inline MetricParams metric_params(const uint8_t *src, const uint8_t *blocks, uint8_t *stats, uint64_t src_image_stride,
+                                  uint64_t blocks_image_stride, uint32_t height, uint32_t width, uint32_t block_cols,
+                                  uint32_t grid_cols, uint32_t row_stride, uint32_t n_images, bool swap_rb) {
+  MetricParams P;
+  P.src = src;
+  P.blocks = blocks;
+  P.stats = stats;
+  P.src_image_stride = src_image_stride;
+  P.blocks_image_stride = blocks_image_stride;
+  P.height = height;
+  P.width = width;
+  P.block_rows = (height + 3u) / 4u;
+  P.block_cols = block_cols;
+  P.grid_cols = grid_cols;
+  P.row_stride = row_stride;
+  P.blocks_per_image = P.block_rows * block_cols;
+  P.total_blocks = P.blocks_per_image * n_images;
+  P.swap_rb = swap_rb ? 1u : 0u;
+  P.force_gather = encode_tile_shape(block_cols, row_stride, 8u).force_gather;
+  P.div_bpi = make_fastdiv(P.blocks_per_image);
+  P.div_cols = make_fastdiv(block_cols);
+  return P;
+}
 hipError_t launch_metric(int codec, int comps, const MetricParams &P, hipStream_t stream);
 hipError_t launch_metric_clear(void *stats, uint64_t n_images, hipStream_t stream);  // zeroes n_images records (8-byte aligned)
 const char *metric_kernel_name(int codec, int comps);
@@ -164,6 +210,10 @@ struct Bc45DecodeParams {
   uint32_t height, width, block_rows, block_cols, row_stride;
   uint32_t log2_tile_cols, tile_row0;
 };
+inline Bc45DecodeParams bc45_decode_params(const uint8_t *blocks, uint8_t *pixels, uint64_t src_image_stride,
+                                           uint64_t dst_image_stride, uint32_t height, uint32_t width, uint32_t row_stride) {
+  return { blocks, pixels, src_image_stride, dst_image_stride, height, width, (height + 3u) / 4u, (width + 3u) / 4u, row_stride, 0u, 0u };
+}
 hipError_t launch_bc45_encode(int codec, int comps, const GridParams &P, hipStream_t stream);
 hipError_t launch_bc45_decode(int codec, uint32_t n_images, const Bc45DecodeParams &P, hipStream_t stream);
 const char *bc45_kernel_name(int codec, int comps);

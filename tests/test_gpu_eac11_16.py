@@ -192,9 +192,9 @@ def test_decode_through_the_c_abi_leaves_the_padding_alone(dev, codec):
     k = A.comps_out(codec)
     row = w * k * 2 + PAD
     slot = h * row + 10
-    per = A.encoded_size(codec, h, w)
+    per = A.encoded_size(codec, h, w) + 24  # the block streams 24 bytes further apart than their size
     words = [A.random_words(codec, h, w, seed=950 + i) for i in range(n)]
-    d = _to_dev(b"\0" + b"".join(words), dev)  # the blocks at an odd address
+    d = _to_dev(b"\0" + b"".join(wd + bytes(24) for wd in words), dev)  # the blocks at an odd address
     out = torch.full((2 + n * slot,), 0x5a, dtype=torch.uint8, device=dev)
     st = pkg.lib().icamd_decode_eac11_16_device(codec, h, w, PAD, n, per, slot, d.data_ptr() + 1, out.data_ptr() + 2, None)
     assert st == 0
