@@ -76,6 +76,10 @@ BC7_MODES_DEFAULT, BC7_MODES_EXTENDED = 0, 1
 # definition stated in the header).  encode_bc6h_device / decode_bc6h_device / measure_error_bc6h_device / containers (DDS, KTX)
 # only (33 is unassigned)
 BC6H_UF16, BC6H_SF16 = 34, 35
+# bc6h_modes of encode_bc6h_modes_device (include/ic_amd.h icamd_encode_bc6h_modes_device): DEFAULT = what encode_bc6h_device
+# writes (mode field 00011); EXTENDED = one fused kernel that also fits one two-subset candidate per block and writes it where
+# it is strictly closer in the t domain.
+BC6H_MODES_DEFAULT, BC6H_MODES_EXTENDED = 0, 1
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -1097,6 +1101,32 @@ def encode_bc6h_device(codec, src, height, width, src_channels, *, grid_height=N
     st = lib().icamd_encode_bc6h_device(codec, src_channels, height, width, gh, gw, stride, n_images, img_stride, per,
                                         _ptr(src), _ptr(out), _stream_handle(stream))
     return out if _check(st, "icamd_encode_bc6h_device") else None
+
+
+def encode_bc6h_modes_device(codec, src, height, width, src_channels, *, bc6h_modes=BC6H_MODES_DEFAULT, grid_height=None,
+                             grid_width=None, row_stride_bytes=None, n_images=1, src_image_stride_bytes=None, out=None, stream=None):
+    """icamd_encode_bc6h_modes_device: encode_bc6h_device with a choice of modes -- BC6H_MODES_DEFAULT (encode_bc6h_device itself)
+    or BC6H_MODES_EXTENDED (the fused kernel with the two-subset candidate).  Returns the torch.uint8 blocks
+    [n_images, encoded_size] (device), or None where the call answers false.  No synchronisation."""
+    _assert_halves_cuda(src)
+    gh = height if grid_height is None else max(grid_height, height)
+    gw = width if grid_width is None else max(grid_width, width)
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    per = encoded_size(codec, gh, gw)
+    if out is None:
+        out = torch.empty((n_images, per), dtype=torch.uint8, device=src.device)
+    else:
+        _check_out(out, n_images, per, "encode_bc6h_modes_device")
+    st = lib().icamd_encode_bc6h_modes_device(codec, bc6h_modes, src_channels, height, width, gh, gw, stride, n_images, img_stride,
+                                              per, _ptr(src), _ptr(out), _stream_handle(stream))
+    return out if _check(st, "icamd_encode_bc6h_modes_device") else None
+
+
+def bc6h_modes_kernel_name(codec, src_channels, bc6h_modes):
+    """icamd_bc6h_modes_kernel_name: the kernel that writes the final bytes (BC6H_MODES_DEFAULT: what bc6h_kernel_name answers);
+    "" if refused."""
+    return lib().icamd_bc6h_modes_kernel_name(codec, src_channels, bc6h_modes).decode()
 
 
 def decode_bc6h_device(codec, blocks, height, width, *, padding_bytes_per_row=0, n_images=1, stream=None):

@@ -93,6 +93,8 @@ PROTOTYPES = (
     ("icamd_measure_error_bc6h_device", i, [i, i, u, u, u, u, u, u, z, z, p, p, p, p]),
     ("icamd_bc6h_kernel_name", s, [i, i]),
     ("icamd_bc6h_metric_kernel_name", s, [i, i]),
+    ("icamd_encode_bc6h_modes_device", i, [i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_bc6h_modes_kernel_name", s, [i, i, i]),
     ("icamd_device_count", i, []),
     ("icamd_last_error", s, []),
     ("icamd_version", s, []),

@@ -333,9 +333,10 @@ ICAMD_DEV int32_t bc6h_floor_div_clamped(int64_t N, uint64_t D) {
   return -(int32_t)umin(bc6h_div15((uint64_t)(-N) + D - 1u, D), 0x7bffu);  // floor of a negative quotient = -ceil(|N| / D)
 }
 
-// rg / b: the block's sixteen pixels as bc6h_fetch hands them.  out: the 16 bytes of the definition's block.
+// rg / b: the block's sixteen pixels as bc6h_fetch hands them.  out: the 16 bytes of the definition's block.  Returns the
+// block's final sse (step 4's; bc6h_modes_block.h compares its candidate with it).
 template <bool SIGNED>
-ICAMD_DEV void encode_bc6h(const uint32_t rg[16], const uint32_t b[16], uint32_t out[4]) {
+ICAMD_DEV uint64_t encode_bc6h_sse(const uint32_t rg[16], const uint32_t b[16], uint32_t out[4]) {
   int32_t t[16][3];
   ICAMD_UNROLL
   for (int i = 0; i < 16; ++i) {
@@ -445,6 +446,11 @@ ICAMD_DEV void encode_bc6h(const uint32_t rg[16], const uint32_t b[16], uint32_t
   out[1] = (uint32_t)(lo64 >> 32);
   out[2] = (uint32_t)hi64;
   out[3] = (uint32_t)(hi64 >> 32);
+  return sse;
+}
+template <bool SIGNED>
+ICAMD_DEV void encode_bc6h(const uint32_t rg[16], const uint32_t b[16], uint32_t out[4]) {
+  (void)encode_bc6h_sse<SIGNED>(rg, b, out);
 }
 
 // ---- metric

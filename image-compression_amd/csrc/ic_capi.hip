@@ -1200,6 +1200,38 @@ int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height
 const char *icamd_bc6h_kernel_name(int codec, int src_channels) { return icamd::bc6h_kernel_name(codec, src_channels); }
 const char *icamd_bc6h_metric_kernel_name(int codec, int src_channels) { return icamd::bc6h_metric_kernel_name(codec, src_channels); }
 
+// EXTENSION (include/ic_amd.h ICAMD_BC6H_MODES_EXTENDED): every argument is checked before any device work, in the order of
+// icamd_encode_bc6h_device; modes 0 IS icamd_encode_bc6h_device, modes 1 the fused kernel of bc6h_modes_kernels.hip in its place
+int icamd_encode_bc6h_modes_device(int codec, int bc6h_modes, int src_channels, uint32_t height, uint32_t width,
+                                   uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                   size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src, void *d_dst,
+                                   void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (!bc6h_codec(codec)) return fail(ICAMD_ERR_ARG, "BC6H: the codec must be ICAMD_BC6H_UF16 or ICAMD_BC6H_SF16");
+  if (bc6h_modes != ICAMD_BC6H_MODES_DEFAULT && bc6h_modes != ICAMD_BC6H_MODES_EXTENDED)
+    return fail(ICAMD_ERR_ARG, "bc6h_modes must be ICAMD_BC6H_MODES_DEFAULT or ICAMD_BC6H_MODES_EXTENDED");
+  if (bc6h_modes == ICAMD_BC6H_MODES_DEFAULT)
+    return icamd_encode_bc6h_device(codec, src_channels, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                    src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, hip_stream);
+  int rc = bc6h_check_source(codec, src_channels, row_stride_bytes, src_image_stride_bytes, d_src);
+  if (rc != ICAMD_OK) return rc;
+  if (n_images == 0) return ICAMD_OK;
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * (uint32_t)src_channels * 2u)
+    return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  const icamd::GridParams P = grid_params(d_src, d_dst, height, width, grid_height, grid_width, row_stride_bytes, n_images,
+                                          src_image_stride_bytes, dst_image_stride_bytes, 0, 0);
+  ICAMD_HIP(icamd::launch_bc6h_modes_encode(codec, src_channels, P, static_cast<hipStream_t>(hip_stream)), "launch bc6h modes");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_bc6h_modes_kernel_name(int codec, int src_channels, int bc6h_modes) {
+  if (bc6h_modes == ICAMD_BC6H_MODES_DEFAULT) return icamd::bc6h_kernel_name(codec, src_channels);
+  if (bc6h_modes == ICAMD_BC6H_MODES_EXTENDED) return icamd::bc6h_modes_kernel_name(codec, src_channels);
+  return "";
+}
+
 // ---- compressed-domain operations
 
 int icamd_pad_batch_device(int compressor, int etc_strategy, int format, uint32_t ch, uint32_t cw, uint32_t n_images,

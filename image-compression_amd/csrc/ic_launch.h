@@ -250,6 +250,10 @@ hipError_t launch_bc6h_decode(int codec, const DecodeParams &P, hipStream_t stre
 hipError_t launch_bc6h_metric(int codec, int chans, const MetricParams &P, hipStream_t stream);
 const char *bc6h_kernel_name(int codec, int chans);         // "" where launch_bc6h_encode has no kernel
 const char *bc6h_metric_kernel_name(int codec, int chans);  // "" where launch_bc6h_metric has no kernel
+// BC6H with the two-subset candidate (extension, bc6h_modes_kernels.hip; icamd_encode_bc6h_modes_device with
+// ICAMD_BC6H_MODES_EXTENDED): one fused kernel in place of launch_bc6h_encode's, the same GridParams.
+hipError_t launch_bc6h_modes_encode(int codec, int chans, const GridParams &P, hipStream_t stream);
+const char *bc6h_modes_kernel_name(int codec, int chans);  // "" where launch_bc6h_modes_encode has no kernel
 
 // Mip chains (mip_kernels.hip).  One pass: the input level (src, COMPS bytes per pixel, height x width, row_stride) of each of
 // n_images images and up to eight local levels j = 0..7 of it (level j = max(1, height >> j) x max(1, width >> j)).  Bit j of

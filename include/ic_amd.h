@@ -1146,6 +1146,73 @@ int icamd_measure_error_bc6h_device(int codec, int src_channels, uint32_t height
 const char *icamd_bc6h_kernel_name(int codec, int src_channels);
 const char *icamd_bc6h_metric_kernel_name(int codec, int src_channels);
 
+/* ---- BC6H with a two-subset candidate (EXTENSION, opt-in, PARITY UNPINNED) ----
+ * icamd_encode_bc6h_modes_device is icamd_encode_bc6h_device with one more argument, bc6h_modes:
+ *   ICAMD_BC6H_MODES_DEFAULT   the call IS icamd_encode_bc6h_device: the same kernels, the same launches, byte for byte.
+ *   ICAMD_BC6H_MODES_EXTENDED  ONE fused kernel in place of those: per block it computes the one-subset block of
+ *                              icamd_encode_bc6h_device and ONE two-subset candidate, and writes the candidate iff it is
+ *                              STRICTLY closer in the t domain.
+ * Statuses, in this order, all before a device is needed: ICAMD_FALSE for a null pointer or height or width 0; ICAMD_ERR_ARG for
+ * a codec other than the two, a bc6h_modes other than the two, src_channels other than 3 or 4, or an odd d_src,
+ * row_stride_bytes or src_image_stride_bytes; ICAMD_OK for n_images == 0; ICAMD_ERR_ARG for row_stride_bytes < width *
+ * src_channels * 2; ICAMD_ERR_NO_DEVICE without a GPU.  No allocation, no synchronisation, capturable on one stream.  The
+ * decoder, the metric and the containers read and frame every mode already.
+ *
+ * The candidate, a DEFINITION (restated in numpy in tests/bc6h_modes_oracle.py; the kernels are bit-exact against it).  The
+ * texels t_p are exactly those of the one-subset definition above (the t domain of the codec's format, edge replication, padded
+ * grids, channels); that definition's steps 1-6 give the one-subset block and its final sse, sse1.
+ *   Grids.  An endpoint of b bits is q in 0 .. 2^b - 1 (unsigned) or -(2^(b-1) - 1) .. 2^(b-1) - 1 (signed).
+ *     D_b(q) = t(finish(un-quantise_b(q))); Q_b(T) = the smallest q that minimises |D_b(q) - T|.  (The kernels try
+ *     T / (31 * 2^(10-b)) resp. T / (62 * 2^(10-b)), truncating, and its two neighbours; tests/test_bc6h_modes_host.py proves that
+ *     equal for every T and b = 6..10.)
+ *   1. Partition.  For s = 0..31 (the two-subset partitions of Decode): n0, n1 = the subsets' texel counts, S0, S1 = their
+ *      (R, G, B) sums of t; N_s = n1 |S0|^2 + n0 |S1|^2, d_s = n0 n1; s beats s' iff N_s d_s' > N_s' d_s (exact integers below
+ *      2^50).  The best partition, ties to the smaller s.  ONE partition is fitted.
+ *   2. Targets.  Subset j: step 1 of the one-subset definition over the subset's texels (the factor 16 of the exchange test
+ *      becomes the subset's texel count): T0_j, T1_j.
+ *   3. Mode ladder, tried in this order; the first feasible mode is the candidate's:
+ *        field  endpoint bits b  delta bits R G B
+ *        00     10               5 5 5
+ *        01110  9                5 5 5
+ *        10010  8                6 5 5
+ *        10110  8                5 6 5
+ *        11010  8                5 5 6
+ *        01     7                6 6 6
+ *        11110  6                none: four endpoints stored directly; always feasible
+ *      E = Q_b of the twelve targets: E[0], E[1] = subset 0's, E[2], E[3] = subset 1's.  A transformed mode is feasible iff for
+ *      every channel c of delta width w, both x in {E[0][c], E[1][c]} and every endpoint y: -2^(w-1) <= y[c] - x <= 2^(w-1) - 1
+ *      (both of subset 0's endpoints can be the base, so step 5 cannot push a delta out of range; no wrap-around is used), and,
+ *      in the signed format, all twelve E >= 0 (Decode does not sign-extend transformed endpoints from b bits [*], a
+ *      specification decoder does; with non-negative endpoints they agree, and a block with a negative endpoint goes to 11110,
+ *      which sign-extends in both).  The three 11-bit two-subset modes are decoded, never written.
+ *   4. Sub-fits at the mode's b, subset 0 then subset 1.  pal_k[c] = t(finish(((64 - w_k) U0_c + w_k U1_c) >> 6)) over the
+ *      3-bit weights, U = un-quantise_b(E).  Every texel of the subset takes the smallest k of the least squared distance over
+ *      three channels; the sub-sse is the sum of the minima.  One refit: step 4 of the one-subset definition with the sums over
+ *      the subset and the 3-bit weights (det = 0: none), T' clamped as there, E' = Q_b(T'), searched again; it replaces the first
+ *      pass iff its sub-sse is STRICTLY smaller AND E' with the other subset's current endpoints is still feasible for the mode
+ *      (subset 1 is checked against subset 0's final endpoints).  sse2 = the two sub-sses.  Widths as in the one-subset definition.
+ *   5. Anchors: texel 0 for subset 0, the partition's anchor for subset 1.  Where the anchor's k >= 4 the subset's endpoints are
+ *      exchanged and its k become 7 - k (the weights are symmetric: the decoded texels do not change).
+ *   6. Pack: the mode field; E[0] in b bits per channel; in the transformed modes E[1..3] as (E[k] - E[0]) & (2^w - 1), in 11110
+ *      as they are in 6 bits, two's complement; the 5-bit partition; every header bit where csrc/bc6h_mode_tables.inc puts it; the
+ *      sixteen k from bit 82 in texel order, 3 bits each, the two anchors' in 2.
+ *   Choice: the candidate is written iff sse2 < sse1.  So no block's t-domain error exceeds ICAMD_BC6H_MODES_DEFAULT's.
+ *   Example: ICAMD_BC6H_UF16, a block whose rows 0..3 hold the halves (0x3C00, 0x3800, 0x3400), (0x3C40, 0x3800, 0x3400),
+ *     (0x3D00, 0x3700, 0x3480), (0x3D00, 0x3740, 0x3480) gives e4 3d e7 5a 13 15 40 80 50 a4 01 e0 ff ff 3f 49: sse1 = 16024;
+ *     partition 13 (rows 0-1 | rows 2-3), mode field 00 at the first rung, first pass E = (495, 462, 429), (497, 462, 429) |
+ *     (503, 454, 433), (503, 456, 433) with sub-sses 56 and 884, neither refit strictly better, subset 1's anchor (texel 15) at
+ *     k = 7: its endpoints exchanged; sse2 = 940 < sse1, so the candidate is written.  ICAMD_BC6H_SF16 gives
+ *     e4 9e 73 ac 09 1b 60 50 08 a2 29 e9 ff ff 7f db (sse1 = 23840, sse2 = 13944).
+ * icamd_bc6h_modes_kernel_name names the kernel that writes the final bytes under ICAMD_BC6H_MODES_EXTENDED; under
+ * ICAMD_BC6H_MODES_DEFAULT it answers what icamd_bc6h_kernel_name answers; "" outside the domain. */
+enum { ICAMD_BC6H_MODES_DEFAULT = 0,    /* what icamd_encode_bc6h_device writes: field 00011 */
+       ICAMD_BC6H_MODES_EXTENDED = 1 }; /* + one two-subset candidate per block, written where strictly closer */
+int icamd_encode_bc6h_modes_device(int codec, int bc6h_modes, int src_channels, uint32_t height, uint32_t width,
+                                   uint32_t grid_height, uint32_t grid_width, uint32_t row_stride_bytes, uint32_t n_images,
+                                   size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                   const void *d_src, void *d_dst, void *hip_stream);
+const char *icamd_bc6h_modes_kernel_name(int codec, int src_channels, int bc6h_modes);
+
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
 const char *icamd_last_error(void);       /* thread-local message for the last negative status */
