@@ -1,6 +1,7 @@
 """CPU tier of the cut of a decode or metric call into launches (image-compression_amd/csrc/decode_plan.h): whole images, as many
 per launch as stay below 2^31 blocks, or bands of block rows of one image of 2^31 blocks or more.  The banded launches need 16 GiB
-of blocks and more, so no GPU test reaches them; the cut is host-only arithmetic and is pinned here.
+of blocks and more, so no GPU test reaches the bands (the whole-image groups of a call of more than 2^31 - 1 blocks run in
+tests/test_gpu_walk_regimes.py, on images that overlap); the cut is host-only arithmetic and is pinned here.
 tests/host_emul/decode_plan_driver.cc, built with g++ against the header alone, prints the pieces.  The expected lists are worked
 out by hand from the rules (groups of max(1, limit // blocks_per_image) images; bands of limit // block_cols block rows, the last
 one height - 4 * first_block_row pixel rows), not taken from a run.

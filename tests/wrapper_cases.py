@@ -237,8 +237,10 @@ METRIC_GRIDS = {(64, 64, 1), (8, 8, 1), (256, 256, 1), (61, 59, 1), (5, 3, 1), (
 
 
 def fastdiv_divisors():
-    """The issue's divisors, and block_cols, blocks_per_image and the blocks of the whole batch of every metric launch."""
-    d = {1, 2, 3, 5, 7, 255, 256, 257, 1023, 65535, 65536, (1 << 31) - 1}
+    """The issue's divisors, and block_cols, blocks_per_image and the blocks of the whole batch of every metric launch; the same
+    of every launch of the walk table (tests/walk_cases.py), the launches of more than 2^31 - 1 blocks among them."""
+    import walk_cases  # (here: this module stays plain numpy for those who only want the operand sets)
+    d = {1, 2, 3, 5, 7, 255, 256, 257, 1023, 65535, 65536, (1 << 31) - 1} | walk_cases.fastdiv_grids()
     for h, w, n in METRIC_GRIDS:
         rows = (h + 3) // 4
         for cols in ((w + 3) // 4, (w + 7) // 8):  # (PVRTC 2 bpp: blocks of 8 x 4 pixels)
