@@ -7,7 +7,7 @@
 // GridParams::force_gather is not read.  Integer only, everything in registers (no LDS, no scratch).
 // Decode: blocks in raster order like bc7_decode_one; RGBA16F rows, A = 0x3C00: two 16-byte stores per pixel row of a block,
 // 8-byte stores per pixel on the blocks the image's edge clips.  Lanes of a wave hold different modes: no wave-uniform shortcut.
-// Metric: the launch shape of the 16-bit EAC metric (blocks in raster order of the images' own grids, four per lane); sums are
+// Metric: the walk of metric_walk.inc (blocks in raster order of the images' own grids, four per lane) over Bc6hAcc; sums are
 // 64-bit from the lane on, lanes meet by wave shuffles and every wave adds its sums to the image's record.
 #include "bc6h_block.h"
 #include "ic_launch.h"
@@ -15,9 +15,7 @@
 
 namespace icamd {
 
-namespace {
-constexpr uint32_t kBc6hMetricBlocksPerLane = 4;
-}  // namespace
+#include "metric_walk.inc"
 
 template <int C, bool SIGNED, bool WIDE>
 __device__ __forceinline__ void bc6h_encode_one(const GridParams &P) {
@@ -31,9 +29,7 @@ __device__ __forceinline__ void bc6h_encode_one(const GridParams &P) {
 
 template <bool SIGNED>
 __device__ __forceinline__ void bc6h_decode_one(const DecodeParams &P, uint32_t k) {
-  const uint32_t img = fastdiv(k, P.div_bpi);
-  const uint32_t rem = k - img * P.blocks_per_image;
-  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const auto [img, rem, brow, bcol] = raster_block(P, k);
   const U4 v = load_stream(reinterpret_cast<const U4 *>(P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * 16u));
   const uint32_t w[4] = { v.x, v.y, v.z, v.w };
   uint32_t rg[16], b[16];
@@ -58,64 +54,15 @@ __device__ __forceinline__ void bc6h_decode_one(const DecodeParams &P, uint32_t 
   }
 }
 
-__device__ __forceinline__ void bc6h_wave_reduce(Bc6hAcc &a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      a.sse[k] += (uint64_t)__shfl_xor((unsigned long long)a.sse[k], off);
-      a.mx[k] = umax(a.mx[k], (uint32_t)__shfl_xor((int)a.mx[k], off));
-    }
-  }
-}
-__device__ __forceinline__ void bc6h_commit(const MetricParams &P, uint32_t img, const Bc6hAcc &a) {
-  icamd_error_stats *rec = reinterpret_cast<icamd_error_stats *>(P.stats) + img;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (a.sse[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&rec->sse[k]), (unsigned long long)a.sse[k]);
-    if (a.mx[k]) atomicMax(&rec->max_abs[k], a.mx[k]);
-  }
-}
-// One commit per wave where its lanes hold blocks of one image, one per lane where they do not (small images in a batch).
-// Every lane of the wave calls this (lanes without a block bring zeros).
-__device__ __forceinline__ void bc6h_flush_wave(const MetricParams &P, uint32_t img, Bc6hAcc &a) {
-  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)img);
-  if (wave_all(img == first)) {
-    bc6h_wave_reduce(a);
-    if ((threadIdx.x & 63u) == 0u) bc6h_commit(P, first, a);
-  } else {
-    bc6h_commit(P, img, a);
-  }
-}
-
 template <int C, bool SIGNED>
 __device__ __forceinline__ void bc6h_metric(const MetricParams &P) {
-  const uint32_t chunk0 = blockIdx.x * (kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane);
-  const uint32_t last = umin(chunk0 + kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane, P.total_blocks) - 1u;
-  const uint32_t img_first = fastdiv(chunk0, P.div_bpi), img_last = fastdiv(last, P.div_bpi);
-  const bool one_image = img_first == img_last;  // workgroup-uniform
-  Bc6hAcc acc;
-  bc6h_clear(acc);
-#pragma nounroll
-  for (uint32_t j = 0; j < kBc6hMetricBlocksPerLane; ++j) {
-    const uint32_t k = chunk0 + j * kThreadsPerWorkgroup + threadIdx.x;
-    uint32_t img = img_last;
-    if (k < P.total_blocks) {
-      img = one_image ? img_first : fastdiv(k, P.div_bpi);
-      const uint32_t rem = k - img * P.blocks_per_image;
-      const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
-      const uint8_t *blk = P.blocks + (size_t)img * P.blocks_image_stride + ((size_t)brow * P.grid_cols + bcol) * 16u;
-      const U4 v = load_stream(reinterpret_cast<const U4 *>(blk));
-      const uint32_t w[4] = { v.x, v.y, v.z, v.w };
-      metric_bc6h_block<C, SIGNED>(w, P.src + (size_t)img * P.src_image_stride, P.height, P.width, P.row_stride, brow * 4u,
-                                   bcol * 4u, acc);
-    }
-    if (!one_image) {
-      bc6h_flush_wave(P, img, acc);
-      bc6h_clear(acc);
-    }
-  }
-  if (one_image) bc6h_flush_wave(P, img_first, acc);
+  metric_walk<MetricWideOps<Bc6hAcc, 3>>(P, [&](uint32_t img, uint32_t brow, uint32_t bcol, Bc6hAcc &acc) {
+    const uint8_t *blk = P.blocks + (size_t)img * P.blocks_image_stride + ((size_t)brow * P.grid_cols + bcol) * 16u;
+    const U4 v = load_stream(reinterpret_cast<const U4 *>(blk));
+    const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+    metric_bc6h_block<C, SIGNED>(w, P.src + (size_t)img * P.src_image_stride, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u,
+                                 acc);
+  });
 }
 
 extern "C" {
@@ -189,22 +136,13 @@ hipError_t launch_bc6h_encode(int codec, int chans, const GridParams &P, hipStre
 
 hipError_t launch_bc6h_decode(int codec, const DecodeParams &P, hipStream_t stream) {
   if (codec != ICAMD_BC6H_UF16 && codec != ICAMD_BC6H_SF16) return hipErrorInvalidValue;
-  if (P.total_blocks == 0) return hipSuccess;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  hipLaunchKernelGGL(codec == ICAMD_BC6H_SF16 ? icamd_bc6h_sf16_decode_kernel : icamd_bc6h_uf16_decode_kernel,
-                     dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), dim3(kThreadsPerWorkgroup), 0, stream,
-                     P);
-  return hipGetLastError();
+  return launch_raster_decode(codec == ICAMD_BC6H_SF16 ? icamd_bc6h_sf16_decode_kernel : icamd_bc6h_uf16_decode_kernel, P, stream);
 }
 
 hipError_t launch_bc6h_metric(int codec, int chans, const MetricParams &P, hipStream_t stream) {
-  if (P.total_blocks == 0) return hipSuccess;
   const Bc6hKernel *k = find_bc6h(codec, chans);
   if (!k) return hipErrorInvalidValue;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  const uint32_t per = kThreadsPerWorkgroup * kBc6hMetricBlocksPerLane;
-  hipLaunchKernelGGL(k->metric, dim3((P.total_blocks + per - 1u) / per), dim3(kThreadsPerWorkgroup), 0, stream, P);
-  return hipGetLastError();
+  return launch_metric_walk(k->metric, P, stream);
 }
 
 }  // namespace icamd

@@ -21,9 +21,7 @@ __device__ __forceinline__ void bc7_encode_one(const GridParams &P) {
 
 // Blocks in raster order of the images' block grids; RGBA8 rows.  Blocks the image's edge clips are written pixel by pixel.
 __device__ __forceinline__ void bc7_decode_one(const DecodeParams &P, uint32_t k) {
-  const uint32_t img = fastdiv(k, P.div_bpi);
-  const uint32_t rem = k - img * P.blocks_per_image;
-  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const auto [img, rem, brow, bcol] = raster_block(P, k);
   const U4 v = load_stream(reinterpret_cast<const U4 *>(P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * 16u));
   const uint32_t w[4] = { v.x, v.y, v.z, v.w };
   uint32_t px[16];
@@ -70,11 +68,7 @@ hipError_t launch_bc7_encode(int comps, const GridParams &P, hipStream_t stream)
 }
 
 hipError_t launch_bc7_decode(const DecodeParams &P, hipStream_t stream) {
-  if (P.total_blocks == 0) return hipSuccess;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  hipLaunchKernelGGL(icamd_bc7_decode_kernel, dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup),
-                     dim3(kThreadsPerWorkgroup), 0, stream, P);
-  return hipGetLastError();
+  return launch_raster_decode(icamd_bc7_decode_kernel, P, stream);
 }
 
 }  // namespace icamd

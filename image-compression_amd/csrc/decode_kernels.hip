@@ -12,9 +12,7 @@ namespace icamd {
 template <int CODEC>
 __device__ __forceinline__ void decode_one(const DecodeParams &P, uint32_t k) {
   constexpr int COMPS = CODEC == ICAMD_DXT5 ? 4 : 3;
-  const uint32_t img = fastdiv(k, P.div_bpi);
-  const uint32_t rem = k - img * P.blocks_per_image;
-  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const auto [img, rem, brow, bcol] = raster_block(P, k);
   const uint8_t *src = P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * codec_block_bytes(CODEC);
   const bool swap = P.swap_rb != 0;
   uint32_t w[4] = { 0, 0, 0, 0 };
@@ -82,8 +80,7 @@ template <int BPP>
 __device__ __forceinline__ void pvrtc_decode_generic(const DecodeParams &P) {
   const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
   if (k >= P.total_blocks) return;
-  const uint32_t img = fastdiv(k, P.div_bpi), rem = k - img * P.blocks_per_image;
-  const uint32_t by = fastdiv(rem, P.div_cols), bx = rem - by * P.block_cols;  // block_cols = width / 8 (2 bpp), / 4 (4 bpp)
+  const auto [img, rem, by, bx] = raster_block(P, k);  // block_cols = width / 8 (2 bpp), / 4 (4 bpp)
   const U2 *blocks = reinterpret_cast<const U2 *>(P.blocks + (size_t)img * P.src_image_stride);
   uint32_t mod[9], col[9];
 #pragma unroll
@@ -177,21 +174,17 @@ __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_pvrtc4_decode_tile
 
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream) {
   if (P.total_blocks == 0) return hipSuccess;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  const dim3 grid((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), block(kThreadsPerWorkgroup);
-  if (codec == ICAMD_DXT1) hipLaunchKernelGGL(icamd_dxt1_decode_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_DXT5) hipLaunchKernelGGL(icamd_dxt5_decode_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_ETC1) hipLaunchKernelGGL(icamd_etc1_decode_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_PVRTC2 && P.block_cols >= kPvrtcTileW && P.block_rows >= kPvrtcTileH &&
-           (P.block_cols & (P.block_cols - 1u)) == 0u && (P.block_rows & (P.block_rows - 1u)) == 0u)
-    hipLaunchKernelGGL(icamd_pvrtc2_decode_tile_kernel, grid, block, 0, stream, P);  // whole tiles: total_blocks / 256 workgroups
-  else if (codec == ICAMD_PVRTC2) hipLaunchKernelGGL(icamd_pvrtc2_decode_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_PVRTC4 && P.block_cols >= kPvrtcTileW && P.block_rows >= kPvrtcTileH &&
-           (P.block_cols & (P.block_cols - 1u)) == 0u && (P.block_rows & (P.block_rows - 1u)) == 0u)
-    hipLaunchKernelGGL(icamd_pvrtc4_decode_tile_kernel, grid, block, 0, stream, P);
-  else if (codec == ICAMD_PVRTC4) hipLaunchKernelGGL(icamd_pvrtc4_decode_kernel, grid, block, 0, stream, P);
+  // PVRTC block grids of whole tiles: one workgroup per tile, total_blocks / 256 of them, which is the raster decoders' grid
+  const bool tiles = P.block_cols >= kPvrtcTileW && P.block_rows >= kPvrtcTileH && (P.block_cols & (P.block_cols - 1u)) == 0u &&
+                     (P.block_rows & (P.block_rows - 1u)) == 0u;
+  void (*kernel)(DecodeParams);
+  if (codec == ICAMD_DXT1) kernel = icamd_dxt1_decode_kernel;
+  else if (codec == ICAMD_DXT5) kernel = icamd_dxt5_decode_kernel;
+  else if (codec == ICAMD_ETC1) kernel = icamd_etc1_decode_kernel;
+  else if (codec == ICAMD_PVRTC2) kernel = tiles ? icamd_pvrtc2_decode_tile_kernel : icamd_pvrtc2_decode_kernel;
+  else if (codec == ICAMD_PVRTC4) kernel = tiles ? icamd_pvrtc4_decode_tile_kernel : icamd_pvrtc4_decode_kernel;
   else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_raster_decode(kernel, P, stream);
 }
 
 }  // namespace icamd

@@ -9,7 +9,7 @@
 // 16 bytes once.  One body, templated on the channel count, RG and signedness.
 // Decode: the lane groups of lane_groups.h with 16 bytes of blocks per lane (K = 2 R11 blocks, or one RG11 block) and 16-byte
 // row stores of 16-bit samples.
-// Metric: the launch shape of metric_kernels.hip (blocks in raster order of the images' own grids, four per lane); sums are
+// Metric: the walk of metric_walk.inc (blocks in raster order of the images' own grids, four per lane) over Eac16Acc; sums are
 // 64-bit from the lane on, lanes meet by wave shuffles and every wave adds its sums to the image's record.
 #include "eac11_16_block.h"
 #include "codec_info.h"
@@ -19,10 +19,11 @@
 
 namespace icamd {
 
+#include "metric_walk.inc"
+
 namespace {
 constexpr bool codec_rg(int codec) { return codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11; }
 constexpr bool codec_signed(int codec) { return codec == ICAMD_EAC_SIGNED_R11 || codec == ICAMD_EAC_SIGNED_RG11; }
-constexpr uint32_t kMetric16BlocksPerLane = 4;
 }  // namespace
 
 template <int C, bool RG, bool SIGNED>
@@ -81,70 +82,21 @@ __device__ __forceinline__ void eac11_16_decode(const Bc45DecodeParams &P) {
   }
 }
 
-__device__ __forceinline__ void eac16_wave_reduce(Eac16Acc &a) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      a.sse[k] += (uint64_t)__shfl_xor((unsigned long long)a.sse[k], off);
-      a.mx[k] = umax(a.mx[k], (uint32_t)__shfl_xor((int)a.mx[k], off));
-    }
-  }
-}
-__device__ __forceinline__ void eac16_commit(const MetricParams &P, uint32_t img, const Eac16Acc &a) {
-  icamd_error_stats *rec = reinterpret_cast<icamd_error_stats *>(P.stats) + img;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (a.sse[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&rec->sse[k]), (unsigned long long)a.sse[k]);
-    if (a.mx[k]) atomicMax(&rec->max_abs[k], a.mx[k]);
-  }
-}
-// One commit per wave where its lanes hold blocks of one image, one per lane where they do not (small images in a batch).
-// Every lane of the wave calls this (lanes without a block bring zeros).
-__device__ __forceinline__ void eac16_flush_wave(const MetricParams &P, uint32_t img, Eac16Acc &a) {
-  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)img);
-  if (wave_all(img == first)) {
-    eac16_wave_reduce(a);
-    if ((threadIdx.x & 63u) == 0u) eac16_commit(P, first, a);
-  } else {
-    eac16_commit(P, img, a);
-  }
-}
-
 template <int C, bool RG, bool SIGNED>
 __device__ __forceinline__ void eac11_16_metric(const MetricParams &P) {
-  const uint32_t chunk0 = blockIdx.x * (kThreadsPerWorkgroup * kMetric16BlocksPerLane);
-  const uint32_t last = umin(chunk0 + kThreadsPerWorkgroup * kMetric16BlocksPerLane, P.total_blocks) - 1u;
-  const uint32_t img_first = fastdiv(chunk0, P.div_bpi), img_last = fastdiv(last, P.div_bpi);
-  const bool one_image = img_first == img_last;  // workgroup-uniform
-  Eac16Acc acc;
-  eac16_clear(acc);
-#pragma nounroll
-  for (uint32_t j = 0; j < kMetric16BlocksPerLane; ++j) {
-    const uint32_t k = chunk0 + j * kThreadsPerWorkgroup + threadIdx.x;
-    uint32_t img = img_last;
-    if (k < P.total_blocks) {
-      img = one_image ? img_first : fastdiv(k, P.div_bpi);
-      const uint32_t rem = k - img * P.blocks_per_image;
-      const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
-      const uint8_t *b = P.blocks + (size_t)img * P.blocks_image_stride + ((size_t)brow * P.grid_cols + bcol) * (RG ? 16u : 8u);
-      uint32_t w[4] = { 0u, 0u, 0u, 0u };
-      if (RG) {
-        const U4 v = load_stream(reinterpret_cast<const U4 *>(b));
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-      } else {
-        const U2 v = load_stream(reinterpret_cast<const U2 *>(b));
-        w[0] = v.x; w[1] = v.y;
-      }
-      metric_eac11_16_block<C, RG, SIGNED>(w, P.src + (size_t)img * P.src_image_stride, P.height, P.width, P.row_stride,
-                                           brow * 4u, bcol * 4u, acc);
+  metric_walk<MetricWideOps<Eac16Acc, 2>>(P, [&](uint32_t img, uint32_t brow, uint32_t bcol, Eac16Acc &acc) {
+    const uint8_t *b = P.blocks + (size_t)img * P.blocks_image_stride + ((size_t)brow * P.grid_cols + bcol) * (RG ? 16u : 8u);
+    uint32_t w[4] = { 0u, 0u, 0u, 0u };
+    if (RG) {
+      const U4 v = load_stream(reinterpret_cast<const U4 *>(b));
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+      const U2 v = load_stream(reinterpret_cast<const U2 *>(b));
+      w[0] = v.x; w[1] = v.y;
     }
-    if (!one_image) {
-      eac16_flush_wave(P, img, acc);
-      eac16_clear(acc);
-    }
-  }
-  if (one_image) eac16_flush_wave(P, img_first, acc);
+    metric_eac11_16_block<C, RG, SIGNED>(w, P.src + (size_t)img * P.src_image_stride, P.height, P.width, P.row_stride, brow * 4u,
+                                         bcol * 4u, acc);
+  });
 }
 
 extern "C" {
@@ -264,13 +216,9 @@ hipError_t launch_eac11_16_decode(int codec, uint32_t n_images, const Bc45Decode
 }
 
 hipError_t launch_eac11_16_metric(int codec, int chans, const MetricParams &P, hipStream_t stream) {
-  if (P.total_blocks == 0) return hipSuccess;
   const Eac16MetricKernel *k = find_eac16(kEac16MetricKernels, codec, chans);
   if (!k) return hipErrorInvalidValue;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  const uint32_t per = kThreadsPerWorkgroup * kMetric16BlocksPerLane;
-  hipLaunchKernelGGL(k->fn, dim3((P.total_blocks + per - 1u) / per), dim3(kThreadsPerWorkgroup), 0, stream, P);
-  return hipGetLastError();
+  return launch_metric_walk(k->fn, P, stream);
 }
 
 }  // namespace icamd

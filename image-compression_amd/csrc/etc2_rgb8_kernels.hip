@@ -17,9 +17,7 @@
 namespace icamd {
 
 __device__ __forceinline__ void etc2_rgb8_decode_one(const DecodeParams &P, uint32_t k) {
-  const uint32_t img = fastdiv(k, P.div_bpi);
-  const uint32_t rem = k - img * P.blocks_per_image;
-  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  const auto [img, rem, brow, bcol] = raster_block(P, k);
   const U2 v = load_stream(reinterpret_cast<const U2 *>(P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * 8u));
   uint32_t px[16];
   decode_etc2_colour(v.x, v.y, px);
@@ -83,11 +81,7 @@ hipError_t launch_etc2_rgb8(int comps, const GridParams &P, hipStream_t stream) 
 }
 
 hipError_t launch_etc2_rgb8_decode(const DecodeParams &P, hipStream_t stream) {
-  if (P.total_blocks == 0) return hipSuccess;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  hipLaunchKernelGGL(icamd_etc2_rgb8_decode_kernel, dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup),
-                     dim3(kThreadsPerWorkgroup), 0, stream, P);
-  return hipGetLastError();
+  return launch_raster_decode(icamd_etc2_rgb8_decode_kernel, P, stream);
 }
 
 }  // namespace icamd

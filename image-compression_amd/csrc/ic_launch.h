@@ -4,7 +4,8 @@
 // the chunks of CopySubimage, CreateSolid and the transcode), mip_plan.h (the passes, grids and kernels of the mip chains) and
 // etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape),
 // dxt_plan.h (the workgroup size of the DXT encoders) and decode_plan.h (the pieces of a decode or metric call, fewer than 2^31
-// blocks each); the launchers here run what a plan says.
+// blocks each); the launchers here run what a plan says.  The raster decoders' cut of a block index (raster_block) and their
+// launch (launch_raster_decode) are here, next to DecodeParams; the metric kernels' walk and launch are in metric_walk.inc.
 #ifndef ICAMD_IC_LAUNCH_H_
 #define ICAMD_IC_LAUNCH_H_
 
@@ -154,6 +155,25 @@ inline DecodeParams decode_params(const uint8_t *blocks, uint8_t *pixels, uint64
   P.div_bpi = make_fastdiv(P.blocks_per_image);
   P.div_cols = make_fastdiv(block_cols);
   return P;
+}
+// Block k of a launch, in raster order of the images' block grids: image img, block rem of it = (brow, bcol).
+struct RasterBlock {
+  uint32_t img, rem, brow, bcol;
+};
+__device__ __forceinline__ RasterBlock raster_block(const DecodeParams &P, uint32_t k) {
+  const uint32_t img = fastdiv(k, P.div_bpi);
+  const uint32_t rem = k - img * P.blocks_per_image;
+  const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
+  return { img, rem, brow, bcol };
+}
+// One block per lane, 256 a workgroup: the launch of every raster decoder.
+template <typename Kernel>
+hipError_t launch_raster_decode(Kernel kernel, const DecodeParams &P, hipStream_t stream) {
+  if (P.total_blocks == 0) return hipSuccess;
+  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+  hipLaunchKernelGGL(kernel, dim3((P.total_blocks + kThreadsPerWorkgroup - 1) / kThreadsPerWorkgroup), dim3(kThreadsPerWorkgroup), 0,
+                     stream, P);
+  return hipGetLastError();
 }
 hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream);
 hipError_t launch_etc2_decode(const DecodeParams &P, hipStream_t stream);  // ETC2 RGBA8 -> RGBA8 rows (etc2_kernels.hip)

@@ -1,8 +1,9 @@
 // metric_kernels.hip -- icamd_measure_error_device for gfx950: the error of compressed blocks against their source pixels,
 // per image and channel (sum of squared differences, largest absolute difference), without a decoded image in memory.
-// One block per lane as in the decoders: load the block words and the block's source pixels, decode in registers
+// A lane takes a block as in the decoders: load the block words and the block's source pixels, decode in registers
 // (metric_block.h: the decoders' own math), accumulate in the lane; lanes meet by wave shuffles, waves through LDS, and a
-// workgroup adds one 64-bit sum and one 32-bit maximum per compared channel to the image's record.
+// workgroup adds one 64-bit sum and one 32-bit maximum per compared channel to the image's record.  Which blocks a lane takes
+// and who commits when is the walk of metric_walk.inc, shared with eac11_16_kernels.hip and bc6h_kernels.hip.
 #include "metric_block.h"
 #include "codec_info.h"
 #include "ic_launch.h"
@@ -11,10 +12,8 @@
 
 namespace icamd {
 
-// Blocks per lane of the raster kernels: a workgroup covers 256 * kMetricBlocksPerLane consecutive blocks (lane t takes
-// blocks t, t + 256, ...: a wave still reads 64 consecutive blocks at a time), a quarter of the atomics of one block per
-// lane.  The range budget of metric_block.h holds for 4 blocks of 32 pixels.
-constexpr uint32_t kMetricBlocksPerLane = 4;
+#include "metric_walk.inc"
+
 constexpr uint32_t kMetricWaves = kThreadsPerWorkgroup / 64;
 
 __device__ __forceinline__ void metric_wave_reduce(MetricAcc &a) {
@@ -38,17 +37,13 @@ __device__ __forceinline__ void metric_commit(const MetricParams &P, uint32_t im
   }
 }
 
-// The lanes of a wave may hold blocks of different images (small images in a batch): one commit per wave where they agree,
-// one per lane where they do not.  Every lane of the wave calls this (lanes without a block bring zeros).
-__device__ __forceinline__ void metric_flush_wave(const MetricParams &P, uint32_t img, MetricAcc &a) {
-  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)img);
-  if (wave_all(img == first)) {
-    metric_wave_reduce(a);
-    if ((threadIdx.x & 63u) == 0u) metric_commit(P, first, a);
-  } else {
-    metric_commit(P, img, a);
-  }
-}
+// MetricAcc (packed 32-bit sums of 4 channels) for the walk of metric_walk.inc
+struct MetricPackedOps {
+  using Acc = MetricAcc;
+  static __device__ __forceinline__ void clear(MetricAcc &a) { metric_clear(a); }
+  static __device__ __forceinline__ void wave_reduce(MetricAcc &a) { metric_wave_reduce(a); }
+  static __device__ __forceinline__ void commit(const MetricParams &P, uint32_t img, const MetricAcc &a) { metric_commit(P, img, a); }
+};
 
 // The whole workgroup holds blocks of image `img` (uniform): one commit.  Contains a barrier.
 __device__ __forceinline__ void metric_flush_workgroup(const MetricParams &P, uint32_t img, MetricAcc &a,
@@ -76,32 +71,10 @@ __device__ __forceinline__ void metric_flush_workgroup(const MetricParams &P, ui
   }
 }
 
-// Blocks in raster order of the images' own block grids, kMetricBlocksPerLane per lane.  one(img, brow, bcol, acc) adds
-// block (brow, bcol) of image img to acc.
+// The walk of metric_walk.inc; a workgroup whose blocks lie in one image commits once, through LDS.
 template <typename One>
 __device__ __forceinline__ void metric_raster(const MetricParams &P, uint32_t (*part)[6], One one) {
-  const uint32_t chunk0 = blockIdx.x * (kThreadsPerWorkgroup * kMetricBlocksPerLane);
-  const uint32_t last = umin(chunk0 + kThreadsPerWorkgroup * kMetricBlocksPerLane, P.total_blocks) - 1u;
-  const uint32_t img_first = fastdiv(chunk0, P.div_bpi), img_last = fastdiv(last, P.div_bpi);
-  const bool one_image = img_first == img_last;  // workgroup-uniform
-  MetricAcc acc;
-  metric_clear(acc);
-#pragma nounroll
-  for (uint32_t j = 0; j < kMetricBlocksPerLane; ++j) {
-    const uint32_t k = chunk0 + j * kThreadsPerWorkgroup + threadIdx.x;
-    uint32_t img = img_last;
-    if (k < P.total_blocks) {
-      img = one_image ? img_first : fastdiv(k, P.div_bpi);
-      const uint32_t rem = k - img * P.blocks_per_image;
-      const uint32_t brow = fastdiv(rem, P.div_cols), bcol = rem - brow * P.block_cols;
-      one(img, brow, bcol, acc);
-    }
-    if (!one_image) {
-      metric_flush_wave(P, img, acc);
-      metric_clear(acc);
-    }
-  }
-  if (one_image) metric_flush_workgroup(P, img_first, acc, part);
+  metric_walk<MetricPackedOps>(P, one, [&](uint32_t img, MetricAcc &acc) { metric_flush_workgroup(P, img, acc, part); });
 }
 
 template <int CODEC, int COMPS>
@@ -314,22 +287,15 @@ hipError_t launch_metric(int codec, int comps, const MetricParams &P, hipStream_
   if (P.total_blocks == 0) return hipSuccess;
   const MetricKernel *k = find_metric_kernel(codec, comps);
   if (!k) return hipErrorInvalidValue;
-  (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
-  const dim3 block(kThreadsPerWorkgroup);
   if (codec == ICAMD_PVRTC2 || codec == ICAMD_PVRTC4) {
     const bool tiles = P.block_cols >= kPvrtcTileW && P.block_rows >= kPvrtcTileH;  // (powers of two: the caller checked)
-    if (tiles)  // whole tiles: total_blocks / 256 workgroups
-      hipLaunchKernelGGL(k->fn, dim3(P.total_blocks / kThreadsPerWorkgroup), block, 0, stream, P);
-    else {
-      const uint32_t per = kThreadsPerWorkgroup * kMetricBlocksPerLane;
-      hipLaunchKernelGGL(codec == ICAMD_PVRTC2 ? icamd_metric_pvrtc2_kernel : icamd_metric_pvrtc4_kernel,
-                         dim3((P.total_blocks + per - 1u) / per), block, 0, stream, P);
-    }
+    if (!tiles) return launch_metric_walk(codec == ICAMD_PVRTC2 ? icamd_metric_pvrtc2_kernel : icamd_metric_pvrtc4_kernel, P, stream);
+    (void)hipGetLastError();  // a stale error of another library on this thread is not this launch's
+    // whole tiles: total_blocks / 256 workgroups
+    hipLaunchKernelGGL(k->fn, dim3(P.total_blocks / kThreadsPerWorkgroup), dim3(kThreadsPerWorkgroup), 0, stream, P);
     return hipGetLastError();
   }
-  const uint32_t per = kThreadsPerWorkgroup * kMetricBlocksPerLane;
-  hipLaunchKernelGGL(k->fn, dim3((P.total_blocks + per - 1u) / per), block, 0, stream, P);
-  return hipGetLastError();
+  return launch_metric_walk(k->fn, P, stream);
 }
 
 }  // namespace icamd

@@ -1,10 +1,11 @@
 """The block-walk cases of the decode and metric kernels: one table of kernel families and one set of case generators, plain
 numpy, no GPU.  Every decode and metric kernel cuts a flat block index k with fastdiv into image, block row and block column;
 workgroups cover consecutive indices, 256 per workgroup in the decoders (one block per lane) and 1024 in the metrics (lane t holds
-blocks t, t + 256, t + 512 and t + 768).  The metric walk exists three times (metric_raster of csrc/metric_kernels.hip,
-eac11_16_metric of csrc/eac11_16_kernels.hip, bc6h_metric of csrc/bc6h_kernels.hip) and chooses between one commit per workgroup,
-one per wave whose lanes agree on the image, and one per lane; the raster decoder body exists eight times.  The regimes below
-are the shapes at which those choices and the last workgroup's occupancy differ.
+blocks t, t + 256, t + 512 and t + 768).  The metric walk exists once (metric_walk of csrc/metric_walk.inc; the kernels of
+csrc/metric_kernels.hip, csrc/eac11_16_kernels.hip and csrc/bc6h_kernels.hip bring their accumulators and per-block bodies) and
+chooses between one commit per workgroup, one per wave whose lanes agree on the image, and one per lane; the raster decoder
+bodies cut their index with raster_block of csrc/ic_launch.h.  The regimes below are the shapes at which those choices and the
+last workgroup's occupancy differ.
 
 tests/test_walk_cases_host.py (CPU tier) restates the walk and holds every regime to what it is named for, and runs every
 definition once; tests/test_gpu_walk_regimes.py (GPU tier) runs the kernels.  Expected values come from the existing oracles
@@ -62,16 +63,17 @@ def _d(name, entry, codec, pixel_bytes, definition):
 _SRC8 = {1: "r8", 2: "rg8", 3: "rgb888", 4: "rgba8"}
 _SRC16 = {1: "r16", 2: "rg16", 3: "rgb16", 4: "rgba16"}
 METRIC_FAMILIES = (
-    # kMetricKernels of csrc/metric_kernels.hip: metric_raster, and the PVRTC raster and tile forms (the shape chooses)
+    # kMetricKernels of csrc/metric_kernels.hip: metric_walk with a workgroup commit through LDS (metric_raster), and the PVRTC
+    # raster and tile forms (the shape chooses)
     [_m("metric_%s_%s" % (d, _SRC8[c]), "measure_error_device", codec, c, d) for d, codec, comps in [
         ("dxt1", DXT1, (3, 4)), ("dxt5", DXT5, (4,)), ("etc1", ETC1, (3, 4)), ("etc2_rgba8", ETC2_RGBA8, (4,)),
         ("etc2_rgb8", ETC2_RGB8, (3, 4)), ("etc2_rgb8a1", ETC2_RGB8A1, (4,)), ("bc4", BC4, (1, 2, 3, 4)), ("bc5", BC5, (2, 3, 4)),
         ("eac_r11", EAC_R11, (1, 2, 3, 4)), ("eac_rg11", EAC_RG11, (2, 3, 4)), ("bc7", BC7, (3, 4)), ("pvrtc2", PVRTC2, (4,)),
         ("pvrtc4", PVRTC4, (4,))] for c in comps] +
-    # ICAMD_EAC16_METRIC_KERNELS of csrc/eac11_16_kernels.hip: eac11_16_metric
+    # ICAMD_EAC16_METRIC_KERNELS of csrc/eac11_16_kernels.hip: eac11_16_metric, metric_walk with 64-bit sums of 2 channels
     [_m("metric_%s_%s" % (d, _SRC16[c]), "measure_error_eac11_16_device", EAC16_CODEC[d], c, d, sample_bytes=2)
      for d in ("eac16_r11", "eac16_rg11", "eac16_signed_r11", "eac16_signed_rg11") for c in range(DEFINITIONS[d][2], 5)] +
-    # ICAMD_BC6H_KERNELS of csrc/bc6h_kernels.hip: bc6h_metric
+    # ICAMD_BC6H_KERNELS of csrc/bc6h_kernels.hip: bc6h_metric, metric_walk with 64-bit sums of 3 channels
     [_m("metric_%s_%s" % (d, {3: "rgb16f", 4: "rgba16f"}[c]), "measure_error_bc6h_device", codec, c, d, sample_bytes=2)
      for d, codec in (("bc6h_uf16", B6.BC6H_UF16), ("bc6h_sf16", B6.BC6H_SF16)) for c in (3, 4)])
 DECODE_FAMILIES = [
