@@ -1129,6 +1129,108 @@ def bc6h_modes_kernel_name(codec, src_channels, bc6h_modes):
     return lib().icamd_bc6h_modes_kernel_name(codec, src_channels, bc6h_modes).decode()
 
 
+# ---- half-float pixel pyramid and the mip chains of BC7 and BC6H (EXTENSION, include/ic_amd.h)
+def mip_f16_kernel_name(src_channels):
+    """icamd_mip_f16_kernel_name: the half-float pyramid's kernel; "" unless src_channels is 3 or 4."""
+    return lib().icamd_mip_f16_kernel_name(src_channels).decode()
+
+
+def mip_pyramid_f16_device(src, height, width, src_channels, *, levels=None, n_images=1, row_stride_bytes=None,
+                           src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None, stream=None):
+    """icamd_mip_pyramid_f16_device on `src`, a contiguous CUDA tensor of halves (torch.float16, or the same bits as int16 /
+    uint16 / uint8).  Returns (flat, views) as mip_pyramid_device does: flat is [n_images, dst_image_stride] torch.uint8, views[l - 1]
+    level l as a [n_images, h_l, w_l, src_channels] torch.float16 view, for l = 1 .. levels-1.  No synchronisation."""
+    _assert_halves_cuda(src)
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    stride = width * src_channels * 2 if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    total, offs = mip_pyramid_size(src_channels * 2, height, width, levels)
+    per = total if dst_image_stride_bytes is None else dst_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
+    _check_out(out, n_images, per, "mip_pyramid_f16_device")
+    st = lib().icamd_mip_pyramid_f16_device(src_channels, height, width, stride, levels, n_images, img_stride, per, _ptr(src),
+                                            _ptr(out), _stream_handle(stream))
+    if not _check(st, "icamd_mip_pyramid_f16_device"):
+        return None
+    views = []
+    for l in range(1, levels):
+        h, w = mip_level_shape(height, width, l)
+        views.append(out[:, offs[l - 1]:offs[l]].view(torch.float16).view(n_images, h, w, src_channels))
+    return out, views
+
+
+def bptc_mip_chain_size(codec, height, width, levels=None):
+    """mip_chain_size for BC7 / BC6H_UF16 / BC6H_SF16: (bytes of one image's chain, [offset of level l for l in 0..levels]);
+    (0, None) where the codec / size / level count is refused."""
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    offs = (ctypes.c_size_t * (max(levels, 0) + 1))()
+    n = lib().icamd_bptc_mip_chain_size(codec, height, width, levels, offs)
+    return (n, list(offs)) if n else (0, None)
+
+
+def bptc_mip_workspace_size(codec, src_channels, height, width, levels=None, n_images=1):
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    return lib().icamd_bptc_mip_workspace_size(codec, src_channels, height, width, levels, n_images)
+
+
+def _encode_bptc_mips(what, call, codec, src, height, width, pixel_bytes, src_channels, levels, n_images, row_stride_bytes,
+                      src_image_stride_bytes, dst_image_stride_bytes, out, workspace, stream):
+    if levels is None:
+        levels = mip_max_levels(height, width)
+    stride = width * pixel_bytes if row_stride_bytes is None else row_stride_bytes
+    img_stride = height * stride if src_image_stride_bytes is None else src_image_stride_bytes
+    total, offs = bptc_mip_chain_size(codec, height, width, levels)
+    per = total if dst_image_stride_bytes is None else dst_image_stride_bytes
+    if out is None:
+        out = torch.empty((n_images, max(per, 1)), dtype=torch.uint8, device=src.device)
+    _check_out(out, n_images, per, what)
+    ws_bytes = bptc_mip_workspace_size(codec, src_channels, height, width, levels, n_images) if total else 0
+    if workspace is None and ws_bytes:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=src.device)
+    if workspace is not None and not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("%s: workspace must be a contiguous uint8 CUDA tensor" % what)
+    ws_ptr = _ptr(workspace) if workspace is not None else None
+    ws_len = workspace.numel() if workspace is not None else 0
+    st = call(height, width, stride, levels, n_images, img_stride, per, _ptr(src), _ptr(out), ws_ptr, ws_len, _stream_handle(stream))
+    if not _check(st, "icamd_" + what) or offs is None:
+        return None
+    return out, [out[:, offs[l]:offs[l + 1]] for l in range(levels)]
+
+
+def encode_bc7_mips_device(src, height, width, src_components, *, bc7_modes=BC7_MODES_DEFAULT, levels=None, swap_rb=False,
+                           mip_filter=0, n_images=1, row_stride_bytes=None, src_image_stride_bytes=None,
+                           dst_image_stride_bytes=None, out=None, workspace=None, stream=None):
+    """BC7 mip chain (icamd_encode_bc7_mips_device) of `src` (a torch.uint8 CUDA tensor, contiguous bytes): bc7_modes as
+    encode_bc7_device, mip_filter 0 .. 3 as encode_mips_device.  Returns (flat, views) as encode_etc2_mips_device does.  The
+    workspace is allocated here unless the caller passes one (at least bptc_mip_workspace_size bytes).  No synchronisation."""
+    _assert_u8_cuda(src)
+    fn = lib().icamd_encode_bc7_mips_device
+    return _encode_bptc_mips("encode_bc7_mips_device", lambda *tail: fn(bc7_modes, src_components, int(swap_rb), mip_filter, *tail),
+                             BC7, src, height, width, src_components, src_components, levels, n_images, row_stride_bytes,
+                             src_image_stride_bytes, dst_image_stride_bytes, out, workspace, stream)
+
+
+def encode_bc6h_mips_device(codec, src, height, width, src_channels, *, bc6h_modes=BC6H_MODES_DEFAULT, levels=None, n_images=1,
+                            row_stride_bytes=None, src_image_stride_bytes=None, dst_image_stride_bytes=None, out=None,
+                            workspace=None, stream=None):
+    """BC6H mip chain (icamd_encode_bc6h_mips_device) of `src`, a contiguous CUDA tensor of halves as encode_bc6h_device takes
+    them: bc6h_modes as encode_bc6h_modes_device.  Returns (flat, views) as encode_etc2_mips_device does.  No synchronisation."""
+    _assert_halves_cuda(src)
+    fn = lib().icamd_encode_bc6h_mips_device
+    return _encode_bptc_mips("encode_bc6h_mips_device", lambda *tail: fn(codec, bc6h_modes, src_channels, *tail), codec, src,
+                             height, width, src_channels * 2, src_channels, levels, n_images, row_stride_bytes,
+                             src_image_stride_bytes, dst_image_stride_bytes, out, workspace, stream)
+
+
+def bptc_mip_kernel_name(codec, src_channels, modes=0):
+    """Name of the kernel of the chain's encode launch ("" if refused); modes: BC7_MODES_* / BC6H_MODES_*."""
+    return lib().icamd_bptc_mip_kernel_name(codec, src_channels, modes).decode()
+
+
 def decode_bc6h_device(codec, blocks, height, width, *, padding_bytes_per_row=0, n_images=1, stream=None):
     """icamd_decode_bc6h_device: torch.uint8 blocks -> a [n_images, height * (width * 4 + padding_bytes_per_row / 2)] tensor of
     torch.float16: RGBA16F rows, A = 1; the padding samples are zero.  None where the call answers false.  No synchronisation."""

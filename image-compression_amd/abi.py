@@ -95,6 +95,13 @@ PROTOTYPES = (
     ("icamd_bc6h_metric_kernel_name", s, [i, i]),
     ("icamd_encode_bc6h_modes_device", i, [i, i, i, u, u, u, u, u, u, z, z, p, p, p]),
     ("icamd_bc6h_modes_kernel_name", s, [i, i, i]),
+    ("icamd_mip_pyramid_f16_device", i, [i, u, u, u, u, u, z, z, p, p, p]),
+    ("icamd_mip_f16_kernel_name", s, [i]),
+    ("icamd_bptc_mip_chain_size", z, [i, u, u, u, p]),
+    ("icamd_bptc_mip_workspace_size", z, [i, i, u, u, u, u]),
+    ("icamd_encode_bc7_mips_device", i, [i, i, i, i, u, u, u, u, u, z, z, p, p, p, z, p]),
+    ("icamd_encode_bc6h_mips_device", i, [i, i, i, u, u, u, u, u, z, z, p, p, p, z, p]),
+    ("icamd_bptc_mip_kernel_name", s, [i, i, i]),
     ("icamd_device_count", i, []),
     ("icamd_last_error", s, []),
     ("icamd_version", s, []),

@@ -9,23 +9,13 @@
 // 8-byte stores per pixel on the blocks the image's edge clips.  Lanes of a wave hold different modes: no wave-uniform shortcut.
 // Metric: the walk of metric_walk.inc (blocks in raster order of the images' own grids, four per lane) over Bc6hAcc; sums are
 // 64-bit from the lane on, lanes meet by wave shuffles and every wave adds its sums to the image's record.
-#include "bc6h_block.h"
+#include "bptc_encode_bodies.inc"  // bc6h_encode_one
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
 
 #include "metric_walk.inc"
-
-template <int C, bool SIGNED, bool WIDE>
-__device__ __forceinline__ void bc6h_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<WIDE>(P);
-  if (!t.valid) return;
-  uint32_t rg[16], b[16], out[4];
-  bc6h_fetch<C>(P.src + (uint64_t)t.img * P.src_image_stride, P.height, P.width, P.row_stride, t.brow * 4u, t.bcol * 4u, rg, b);
-  encode_bc6h<SIGNED>(rg, b, out);
-  store_stream16(tile_dst<16>(P, t), out[0], out[1], out[2], out[3]);
-}
 
 template <bool SIGNED>
 __device__ __forceinline__ void bc6h_decode_one(const DecodeParams &P, uint32_t k) {
@@ -76,10 +66,10 @@ extern "C" {
 
 #define ICAMD_BC6H_DEFINE(stem, codec, chans, is_signed)                                                                    \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_kernel(GridParams P) {                             \
-    bc6h_encode_one<chans, is_signed, true>(P);                                                                             \
+    bc6h_encode_one<chans, is_signed, true>(P, tile_of_launch(P));                                                                             \
   }                                                                                                                         \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_narrow_kernel(GridParams P) {                      \
-    bc6h_encode_one<chans, is_signed, false>(P);                                                                            \
+    bc6h_encode_one<chans, is_signed, false>(P, tile_of_launch(P));                                                                            \
   }                                                                                                                         \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_metric_##stem##_kernel(MetricParams P) {                    \
     bc6h_metric<chans, is_signed>(P);                                                                                       \

@@ -3,21 +3,11 @@
 // bc6h_kernels.hip does, fits the block's one two-subset candidate and writes whichever is strictly closer, in one 16-byte store.
 // One 4 x 4 block per lane on the tiles of launch_tiled with the GridParams and the fetch of bc6h_kernels.hip; integer only, no
 // LDS, no wave-uniform shortcut: a lane's mode is data (bc6h_modes_block.h).
-#include "bc6h_modes_block.h"
+#include "bptc_encode_bodies.inc"  // bc6h_modes_encode_one
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-template <int C, bool SIGNED, bool WIDE>
-__device__ __forceinline__ void bc6h_modes_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<WIDE>(P);
-  if (!t.valid) return;
-  uint32_t rg[16], b[16], out[4];
-  bc6h_fetch<C>(P.src + (uint64_t)t.img * P.src_image_stride, P.height, P.width, P.row_stride, t.brow * 4u, t.bcol * 4u, rg, b);
-  encode_bc6h_modes<SIGNED>(rg, b, out);
-  store_stream16(tile_dst<16>(P, t), out[0], out[1], out[2], out[3]);
-}
 
 extern "C" {
 
@@ -30,10 +20,10 @@ extern "C" {
 
 #define ICAMD_BC6H_MODES_DEFINE(stem, codec, chans, is_signed)                                                              \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_kernel(GridParams P) {                             \
-    bc6h_modes_encode_one<chans, is_signed, true>(P);                                                                       \
+    bc6h_modes_encode_one<chans, is_signed, true>(P, tile_of_launch(P));                                                                       \
   }                                                                                                                         \
   __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_##stem##_narrow_kernel(GridParams P) {                      \
-    bc6h_modes_encode_one<chans, is_signed, false>(P);                                                                      \
+    bc6h_modes_encode_one<chans, is_signed, false>(P, tile_of_launch(P));                                                                      \
   }
 ICAMD_BC6H_MODES_KERNELS(ICAMD_BC6H_MODES_DEFINE)
 #undef ICAMD_BC6H_MODES_DEFINE

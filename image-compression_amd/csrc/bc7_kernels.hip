@@ -3,21 +3,11 @@
 // 64 consecutive blocks' row segments and writes 64 consecutive 16-byte blocks), the decoder on blocks in raster order like the
 // DXT decoders.  Integer only, everything in registers (no LDS, no scratch, no wave-uniform shortcut).  The metric kernels are
 // in metric_kernels.hip (metric_bc7_block).
-#include "bc7_block.h"
+#include "bptc_encode_bodies.inc"  // bc7_encode_one
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
-
-template <int COMPS, bool WIDE>
-__device__ __forceinline__ void bc7_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<WIDE>(P);
-  if (!t.valid) return;
-  uint32_t px[16], out[4];
-  load_tile_block<COMPS>(P, t, px);
-  encode_bc7<COMPS>(px, P.swap_rb != 0, out);
-  store_stream16(tile_dst<16>(P, t), out[0], out[1], out[2], out[3]);
-}
 
 // Blocks in raster order of the images' block grids; RGBA8 rows.  Blocks the image's edge clips are written pixel by pixel.
 __device__ __forceinline__ void bc7_decode_one(const DecodeParams &P, uint32_t k) {
@@ -47,10 +37,10 @@ __device__ __forceinline__ void bc7_decode_one(const DecodeParams &P, uint32_t k
 
 extern "C" {
 // *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgba8_kernel(GridParams P) { bc7_encode_one<4, true>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgb888_kernel(GridParams P) { bc7_encode_one<3, true>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgba8_narrow_kernel(GridParams P) { bc7_encode_one<4, false>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgb888_narrow_kernel(GridParams P) { bc7_encode_one<3, false>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgba8_kernel(GridParams P) { bc7_encode_one<4, true>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgb888_kernel(GridParams P) { bc7_encode_one<3, true>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgba8_narrow_kernel(GridParams P) { bc7_encode_one<4, false>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_rgb888_narrow_kernel(GridParams P) { bc7_encode_one<3, false>(P, tile_of_launch(P)); }
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_decode_kernel(DecodeParams P) {
   const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
   if (k < P.total_blocks) bc7_decode_one(P, k);

@@ -3,28 +3,18 @@
 // bc7_kernels.hip does, measures it, fits the block's one candidate (mode 1 on opaque blocks, mode 5 on the others) and
 // writes whichever is strictly closer.  One 4 x 4 block per lane on the tiles of launch_tiled, as bc7_kernels.hip; integer
 // only, everything in registers (no LDS, no scratch, no wave-uniform shortcut: every branch of bc7_modes_block.h is per lane).
-#include "bc7_modes_block.h"
+#include "bptc_encode_bodies.inc"  // bc7_modes_encode_one
 #include "ic_launch.h"
 #include "ic_amd.h"
 
 namespace icamd {
 
-template <int COMPS, bool WIDE>
-__device__ __forceinline__ void bc7_modes_encode_one(const GridParams &P) {
-  const TileCoord t = locate_tile<WIDE>(P);
-  if (!t.valid) return;
-  uint32_t px[16], out[4];
-  load_tile_block<COMPS>(P, t, px);
-  encode_bc7_modes<COMPS>(px, P.swap_rb != 0, out);
-  store_stream16(tile_dst<16>(P, t), out[0], out[1], out[2], out[3]);
-}
-
 extern "C" {
 // *_kernel: 256 x 1-block tiles (block grids more than 128 columns wide); *_narrow_kernel: any tile shape
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgba8_kernel(GridParams P) { bc7_modes_encode_one<4, true>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgb888_kernel(GridParams P) { bc7_modes_encode_one<3, true>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgba8_narrow_kernel(GridParams P) { bc7_modes_encode_one<4, false>(P); }
-__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgb888_narrow_kernel(GridParams P) { bc7_modes_encode_one<3, false>(P); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgba8_kernel(GridParams P) { bc7_modes_encode_one<4, true>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgb888_kernel(GridParams P) { bc7_modes_encode_one<3, true>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgba8_narrow_kernel(GridParams P) { bc7_modes_encode_one<4, false>(P, tile_of_launch(P)); }
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc7_modes_rgb888_narrow_kernel(GridParams P) { bc7_modes_encode_one<3, false>(P, tile_of_launch(P)); }
 }  // extern "C"
 
 const char *bc7_modes_kernel_name(int comps) {

@@ -178,37 +178,26 @@ struct Etc2MipPlan {
   bool th;
 };
 
-inline Etc2MipPlan etc2_mip_plan(const Etc2MipIn &in) {
-  Etc2MipPlan plan = {};
-  plan.form = kMipRefused;
-  if (!etc2_mip_codec(in.codec) || in.comps < 1 || in.comps > 4 || in.levels == 0 || in.levels > mip_max_levels(in.height, in.width))
-    return plan;
-  size_t block_off[kMipMaxLevels + 1], pixel_off[kMipMaxLevels + 1];
-  plan.chain_bytes = etc2_mip_chain_bytes(in.codec, in.height, in.width, in.levels, block_off);
-  plan.pyramid_image_stride = mip_pyramid_bytes(in.height, in.width, in.levels, in.comps, pixel_off);
-  plan.workspace_bytes = (size_t)plan.pyramid_image_stride * in.n_images;
-  plan.th = in.modes != 0;
-  plan.n_images = in.n_images;
-  if (in.levels > 1) {
-    const MipChainIn pyr = { kMipPyramidMode, in.comps, in.filter, in.height, in.width, in.levels, in.n_images, in.row_stride,
-                             in.src_image_stride, plan.pyramid_image_stride };
-    (void)mip_plan_passes(pyr, false, kMipWorkspace, plan.pyramid_image_stride, nullptr, pixel_off, plan.pyramid);
-  }
-  Etc2MipTable &T = plan.table;
-  T.n_levels = in.levels;
+// Fills the table for `levels` levels of a height x width image in the given order and returns the workgroups of one image
+// (grid.x), or 0 where they are 2^31 and more (an image of some 2^43 pixels): the table is then filled up to the level that
+// crossed the limit.  Level 0 has the source's row stride, the others tight rows of pixel_bytes per pixel at pixel_off[l] of the
+// image's pyramid; every level gets the tile shape launch_tiled gives it alone (encode_tile_shape with max_log2_cols).
+inline uint32_t etc2_mip_fill_table(Etc2MipTable &T, uint32_t height, uint32_t width, uint32_t levels, int order, uint32_t row_stride,
+                                    uint32_t pixel_bytes, const size_t *pixel_off, const size_t *block_off, uint32_t max_log2_cols) {
+  T.n_levels = levels;
   uint64_t wg = 0;
-  for (uint32_t k = 0; k < in.levels; ++k) {
-    const uint32_t l = in.order == kEtc2MipLargestFirst ? k : in.levels - 1u - k;
+  for (uint32_t k = 0; k < levels; ++k) {
+    const uint32_t l = order == kEtc2MipLargestFirst ? k : levels - 1u - k;
     Etc2MipLevel &L = T.level[k];
     L.level = l;
-    L.height = mip_dim(in.height, l);
-    L.width = mip_dim(in.width, l);
+    L.height = mip_dim(height, l);
+    L.width = mip_dim(width, l);
     L.block_rows = (uint32_t)(((uint64_t)L.height + 3u) / 4u);
     L.block_cols = (uint32_t)(((uint64_t)L.width + 3u) / 4u);
     L.pix_offset = l == 0 ? 0 : pixel_off[l];
-    L.row_stride = l == 0 ? in.row_stride : L.width * (uint32_t)in.comps;
+    L.row_stride = l == 0 ? row_stride : L.width * pixel_bytes;
     L.dst_offset = block_off[l];
-    const TileShape shape = encode_tile_shape(L.block_cols, L.row_stride, 4u);
+    const TileShape shape = encode_tile_shape(L.block_cols, L.row_stride, max_log2_cols);
     L.log2_tile_cols = shape.log2_tile_cols;
     L.force_gather = shape.force_gather;
     const uint32_t cols = 1u << L.log2_tile_cols, rows = 256u >> L.log2_tile_cols;
@@ -227,13 +216,35 @@ inline Etc2MipPlan etc2_mip_plan(const Etc2MipIn &in) {
       T.bulk_tiles = (uint32_t)n_tiles;  // (below 2^31, or the plan is refused below)
     }
     wg += n_tiles;
-    if (wg >= (1ull << 31)) {  // more workgroups than a grid's x holds (an image of some 2^43 pixels)
-      plan.pyramid.n_passes = 0;
-      return plan;
-    }
+    if (wg >= (1ull << 31)) return 0;  // more workgroups than a grid's x holds
     L.n_tiles = (uint32_t)n_tiles;
   }
-  T.first_wg[in.levels] = plan.grid_x = (uint32_t)wg;
+  T.first_wg[levels] = (uint32_t)wg;
+  return (uint32_t)wg;
+}
+
+inline Etc2MipPlan etc2_mip_plan(const Etc2MipIn &in) {
+  Etc2MipPlan plan = {};
+  plan.form = kMipRefused;
+  if (!etc2_mip_codec(in.codec) || in.comps < 1 || in.comps > 4 || in.levels == 0 || in.levels > mip_max_levels(in.height, in.width))
+    return plan;
+  size_t block_off[kMipMaxLevels + 1], pixel_off[kMipMaxLevels + 1];
+  plan.chain_bytes = etc2_mip_chain_bytes(in.codec, in.height, in.width, in.levels, block_off);
+  plan.pyramid_image_stride = mip_pyramid_bytes(in.height, in.width, in.levels, in.comps, pixel_off);
+  plan.workspace_bytes = (size_t)plan.pyramid_image_stride * in.n_images;
+  plan.th = in.modes != 0;
+  plan.n_images = in.n_images;
+  if (in.levels > 1) {
+    const MipChainIn pyr = { kMipPyramidMode, in.comps, in.filter, in.height, in.width, in.levels, in.n_images, in.row_stride,
+                             in.src_image_stride, plan.pyramid_image_stride };
+    (void)mip_plan_passes(pyr, false, kMipWorkspace, plan.pyramid_image_stride, nullptr, pixel_off, plan.pyramid);
+  }
+  plan.grid_x = etc2_mip_fill_table(plan.table, in.height, in.width, in.levels, in.order, in.row_stride, (uint32_t)in.comps, pixel_off,
+                                    block_off, 4u);
+  if (plan.grid_x == 0) {
+    plan.pyramid.n_passes = 0;
+    return plan;
+  }
   const bool kernels = mip_kernel_form(kMipPyramidMode, in.comps, in.filter).exists &&
                        etc2_mip_kernel_index(in.codec, in.comps, 2, false) >= 0 &&
                        (!plan.th || etc2_mip_kernel_index(in.codec, in.comps, 2, true) >= 0);

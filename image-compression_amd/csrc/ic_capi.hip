@@ -1934,6 +1934,122 @@ const char *icamd_etc2_mip_kernel_name(int codec, int src_components, int etc_st
   return icamd::etc2_mip_kernel_form(codec, src_components, etc_strategy, etc2_modes == ICAMD_ETC2_MODES_TH);
 }
 
+// ---- mip chains of BC7 and BC6H (EXTENSION): the plan is bptc_mip_plan.h's; here are the argument checks ----
+size_t icamd_bptc_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets) {
+  return icamd::bptc_mip_chain_bytes(codec, height, width, levels, level_offsets);
+}
+
+size_t icamd_bptc_mip_workspace_size(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t levels,
+                                     uint32_t n_images) {
+  return icamd::bptc_mip_plan({ codec, src_channels, ICAMD_MIP_FILTER_BOX, 0, height, width, levels, n_images, 0, 0, 0 }).workspace_bytes;
+}
+
+// What the two entry points share once codec, modes, channels, swap_rb and filter are accepted: the geometry checks in the order
+// of icamd_encode_etc2_mips_device, then the pyramid passes and the one encode launch.
+static int encode_bptc_mips(int codec, int modes, int chans, int swap_rb, int filter, uint32_t height, uint32_t width,
+                            uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                            size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace, size_t workspace_bytes,
+                            void *hip_stream) {
+  const bool halves = codec != ICAMD_BC7;
+  const uint32_t pixel_bytes = icamd::bptc_mip_pixel_bytes(codec, chans);
+  if (levels == 0 || levels > mip_max_levels(height, width))
+    return fail(ICAMD_ERR_ARG, "levels must be 1 .. floor(log2(max(height, width))) + 1");
+  if ((uint64_t)row_stride_bytes < (uint64_t)width * pixel_bytes) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
+  const icamd::BptcMipPlan plan = icamd::bptc_mip_plan({ codec, chans, filter, modes, height, width, levels, n_images, row_stride_bytes,
+                                                         src_image_stride_bytes, dst_image_stride_bytes });
+  const size_t src_bytes = (size_t)(height - 1u) * row_stride_bytes + (size_t)width * pixel_bytes;
+  if (n_images > 1 && (src_image_stride_bytes < src_bytes || dst_image_stride_bytes < plan.chain_bytes))
+    return fail(ICAMD_ERR_ARG, "image stride smaller than an image");
+  if (plan.workspace_bytes && (!d_workspace || workspace_bytes < plan.workspace_bytes))
+    return fail(ICAMD_ERR_ARG, "workspace smaller than icamd_bptc_mip_workspace_size");
+  if (halves && (reinterpret_cast<uintptr_t>(d_src) % 2u || reinterpret_cast<uintptr_t>(d_workspace) % 2u || row_stride_bytes % 2u ||
+                 src_image_stride_bytes % 2u))
+    return fail(ICAMD_ERR_ARG, "BC6H: d_src, d_workspace, row_stride_bytes and src_image_stride_bytes must be even");
+  if (n_images == 0) return ICAMD_OK;
+  int rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (plan.form != icamd::kMipLaunch) return fail(ICAMD_ERR_ARG, "BC7 / BC6H mip chain: more workgroups than one launch holds");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const icamd::MipBuffers buffers = { static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_workspace), static_cast<uint8_t *>(d_dst) };
+  // the pixel pyramid into the workspace (BC7: built unswapped, averaging is per channel), then every level of every image in
+  // one launch (per piece of 65 535 images)
+  for (uint32_t k = 0; k < plan.pyramid.n_passes; ++k)
+    ICAMD_HIP(halves ? icamd::launch_mip_f16_pass(chans, plan.pyramid.pass[k], buffers, stream)
+                     : icamd::launch_mip_pass(icamd::kMipPyramidMode, chans, filter, plan.pyramid.pass[k], buffers, false, stream),
+              "launch mip pyramid");
+  ICAMD_HIP(icamd::launch_bptc_mip(codec, chans, modes, swap_rb != 0, plan, buffers, src_image_stride_bytes, dst_image_stride_bytes,
+                                   stream), "launch bptc mip chain");
+  return ICAMD_OK;
+}
+
+int icamd_encode_bc7_mips_device(int bc7_modes, int src_components, int swap_rb, int filter, uint32_t height, uint32_t width,
+                                 uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                                 size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
+                                 size_t workspace_bytes, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (bc7_modes != ICAMD_BC7_MODES_DEFAULT && bc7_modes != ICAMD_BC7_MODES_EXTENDED)
+    return fail(ICAMD_ERR_ARG, "bc7_modes must be ICAMD_BC7_MODES_DEFAULT or ICAMD_BC7_MODES_EXTENDED");
+  if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
+  if (filter < 0 || filter > (ICAMD_MIP_FILTER_SRGB | ICAMD_MIP_FILTER_ALPHA_WEIGHTED))
+    return fail(ICAMD_ERR_ARG, "BC7 chains take ICAMD_MIP_FILTER_BOX or a combination of ICAMD_MIP_FILTER_SRGB and "
+                               "ICAMD_MIP_FILTER_ALPHA_WEIGHTED");
+  if ((filter & ICAMD_MIP_FILTER_ALPHA_WEIGHTED) && src_components != 4)
+    return fail(ICAMD_ERR_ARG, "ICAMD_MIP_FILTER_ALPHA_WEIGHTED needs a 4-component source");
+  return encode_bptc_mips(ICAMD_BC7, bc7_modes, src_components, swap_rb, filter, height, width,
+                          row_stride_bytes, levels, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, d_workspace,
+                          workspace_bytes, hip_stream);
+} ICAMD_ABI_CATCH
+
+int icamd_encode_bc6h_mips_device(int codec, int bc6h_modes, int src_channels, uint32_t height, uint32_t width,
+                                  uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                                  size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *d_workspace,
+                                  size_t workspace_bytes, void *hip_stream) try {
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  if (!bc6h_codec(codec)) return fail(ICAMD_ERR_ARG, "BC6H: the codec must be ICAMD_BC6H_UF16 or ICAMD_BC6H_SF16");
+  if (bc6h_modes != ICAMD_BC6H_MODES_DEFAULT && bc6h_modes != ICAMD_BC6H_MODES_EXTENDED)
+    return fail(ICAMD_ERR_ARG, "bc6h_modes must be ICAMD_BC6H_MODES_DEFAULT or ICAMD_BC6H_MODES_EXTENDED");
+  if (src_channels != 3 && src_channels != 4) return fail(ICAMD_ERR_ARG, "BC6H needs 3 or 4 source channels");
+  return encode_bptc_mips(codec, bc6h_modes, src_channels, 0, ICAMD_MIP_FILTER_BOX, height, width,
+                          row_stride_bytes, levels, n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, d_workspace,
+                          workspace_bytes, hip_stream);
+} ICAMD_ABI_CATCH
+
+const char *icamd_bptc_mip_kernel_name(int codec, int src_channels, int modes) {
+  return icamd::bptc_mip_kernel_form(codec, src_channels, modes);
+}
+
+// The half-float pixel pyramid: the checks of icamd_mip_pyramid_device with 2 * src_channels bytes per pixel, and even addresses.
+int icamd_mip_pyramid_f16_device(int src_channels, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
+                                 uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes,
+                                 const void *d_src, void *d_dst, void *hip_stream) try {
+  if (src_channels != 3 && src_channels != 4) return fail(ICAMD_ERR_ARG, "src_channels must be 3 or 4");
+  if (!d_src || !d_dst || height == 0 || width == 0) return ICAMD_FALSE;
+  const int pixel_bytes = 2 * src_channels;
+  int rc = mip_check_geometry(icamd::kMipPyramidMode, pixel_bytes, height, width, row_stride_bytes, levels, n_images,
+                              src_image_stride_bytes, dst_image_stride_bytes);
+  if (rc != ICAMD_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(d_src) % 2u || reinterpret_cast<uintptr_t>(d_dst) % 2u || row_stride_bytes % 2u ||
+      src_image_stride_bytes % 2u || dst_image_stride_bytes % 2u)
+    return fail(ICAMD_ERR_ARG, "half-float pyramid: pointers, row_stride_bytes and the image strides must be even");
+  if (n_images == 0) return ICAMD_OK;
+  rc = require_device();
+  if (rc != ICAMD_OK) return rc;
+  if (levels == 1) return ICAMD_OK;
+  size_t pixel_off[icamd::kMipMaxLevels + 1];
+  (void)icamd::mip_pyramid_bytes(height, width, levels, pixel_bytes, pixel_off);
+  icamd::MipChainPlan plan = {};
+  const icamd::MipChainIn in = { icamd::kMipPyramidMode, pixel_bytes, ICAMD_MIP_FILTER_BOX, height, width, levels, n_images,
+                                 row_stride_bytes, src_image_stride_bytes, dst_image_stride_bytes };
+  (void)icamd::mip_plan_passes(in, false, icamd::kMipOutput, dst_image_stride_bytes, nullptr, pixel_off, plan);
+  const icamd::MipBuffers buffers = { static_cast<const uint8_t *>(d_src), nullptr, static_cast<uint8_t *>(d_dst) };
+  for (uint32_t k = 0; k < plan.n_passes; ++k)
+    ICAMD_HIP(icamd::launch_mip_f16_pass(src_channels, plan.pass[k], buffers, static_cast<hipStream_t>(hip_stream)),
+              "launch half-float mip pyramid");
+  return ICAMD_OK;
+} ICAMD_ABI_CATCH
+
+const char *icamd_mip_f16_kernel_name(int src_channels) { return icamd::mip_f16_kernel_name(src_channels); }
+
 // icamd_mip_pyramid_device / icamd_mip_pyramid_filtered_device (the former is filter 0)
 static int mip_pyramid(int src_components, int filter, uint32_t height, uint32_t width, uint32_t row_stride_bytes, uint32_t levels,
                        uint32_t n_images, size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src,

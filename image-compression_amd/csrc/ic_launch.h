@@ -3,6 +3,7 @@
 // Which kernels a call gets is decided in the host-only plans: pvrtc_plan.h (PVRTC), blockops_plan.h (Pad, Downsample and
 // the chunks of CopySubimage, CreateSolid and the transcode), mip_plan.h (the passes, grids and kernels of the mip chains) and
 // etc2_mip_plan.h (the level table and grid of the ETC2-family chains' one encode launch, and the encoders' tile shape),
+// bptc_mip_plan.h (the same for the BC7 and BC6H chains, with the half-float pyramid's passes),
 // dxt_plan.h (the workgroup size of the DXT encoders) and decode_plan.h (the pieces of a decode or metric call, fewer than 2^31
 // blocks each); the launchers here run what a plan says.  The raster decoders' cut of a block index (raster_block) and their
 // launch (launch_raster_decode) are here, next to DecodeParams; the metric kernels' walk and launch are in metric_walk.inc.
@@ -14,6 +15,7 @@
 #include <atomic>
 
 #include "blockops_plan.h"
+#include "bptc_mip_plan.h"
 #include "etc2_mip_plan.h"
 #include "ic_device.h"
 #include "mip_plan.h"
@@ -299,12 +301,24 @@ struct MipBuffers {  // what MipBase names: the caller's source, workspace and o
 hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
                            hipStream_t stream);
 const char *mip_kernel_name(int mode, int comps, int filter);  // "" where launch_mip_pass has no kernel
+// The launches of a planned pass with the kernel given (mip_kernels.hip): what launch_mip_pass and launch_mip_f16_pass share.
+hipError_t launch_mip_kernel(void (*kernel)(MipParams), const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
+                             hipStream_t stream);
+// The half-float pixel pyramid (extension, mip_f16_kernels.hip; icamd_mip_pyramid_f16_device): a pass planned by mip_plan_passes
+// with 2 * chans bytes per pixel for the component count, chans = halves per pixel, 3 or 4.  Pixels only: enc_mask is not read.
+hipError_t launch_mip_f16_pass(int chans, const MipPassPlan &pass, const MipBuffers &buffers, hipStream_t stream);
+const char *mip_f16_kernel_name(int chans);  // "" unless chans is 3 or 4
 // Mip chains of the ETC2 family (extension, etc2_mip_kernels.hip): the encode launch of a plan of etc2_mip_plan.h -- every level
 // of every image in one launch per piece of grid.y -- or (th) the T / H pass over the same grid, after it on the stream.  The
 // pixel pyramid is in the workspace by then (launch_mip_pass on the same stream).  hipErrorInvalidValue where the list has no
 // kernel.
 hipError_t launch_etc2_mip(int codec, int comps, uint32_t etc_strategy, bool th, bool swap_rb, const Etc2MipPlan &plan,
                            const MipBuffers &buffers, uint64_t src_image_stride, uint64_t dst_image_stride, hipStream_t stream);
+// Mip chains of BC7 and BC6H (extension, bptc_mip_kernels.hip): the encode launch of a plan of bptc_mip_plan.h, as
+// launch_etc2_mip.  chans: bytes (BC7) or halves (BC6H) per source pixel; modes: ICAMD_BC7_MODES_* / ICAMD_BC6H_MODES_*; swap_rb
+// is BC7's.  The pixel pyramid is in the workspace by then (launch_mip_pass / launch_mip_f16_pass on the same stream).
+hipError_t launch_bptc_mip(int codec, int chans, int modes, bool swap_rb, const BptcMipPlan &plan, const MipBuffers &buffers,
+                           uint64_t src_image_stride, uint64_t dst_image_stride, hipStream_t stream);
 
 // Compressed-domain operations on block grids.  BlockOpParams is what a kernel receives: launch_blockop
 // (blockops_kernels.hip) fills it, per launch, from the caller's BlockOpCall and the plan of blockops_plan.h.

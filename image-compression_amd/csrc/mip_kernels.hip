@@ -18,10 +18,7 @@ typedef void (*MipKernel)(MipParams);
 static const MipKernel kMipKernels[] = { ICAMD_MIP_KERNELS(ICAMD_MIP_POINTER) };  // by mip_kernel_index
 #undef ICAMD_MIP_POINTER
 
-hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
-                           hipStream_t stream) {
-  const int k = mip_kernel_index(mode, comps, filter);
-  if (k < 0) return hipErrorInvalidValue;
+hipError_t launch_mip_kernel(MipKernel kernel, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb, hipStream_t stream) {
   uint8_t *const base[] = { const_cast<uint8_t *>(buffers.src), buffers.workspace, buffers.out };  // by MipBase
   MipParams P = {};
   P.src_image_stride = pass.in_image_stride;
@@ -46,10 +43,17 @@ hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &p
     for (uint32_t y = 0; y < mip_pieces(pass.tile_rows); ++y) {
       const MipPiece rows = mip_piece(pass.tile_rows, y);
       P.tile_row0 = rows.first;
-      hipLaunchKernelGGL(kMipKernels[k], dim3(pass.grid_x, rows.count, images.count), dim3(kThreadsPerWorkgroup), 0, stream, P);
+      hipLaunchKernelGGL(kernel, dim3(pass.grid_x, rows.count, images.count), dim3(kThreadsPerWorkgroup), 0, stream, P);
     }
   }
   return hipGetLastError();
+}
+
+hipError_t launch_mip_pass(int mode, int comps, int filter, const MipPassPlan &pass, const MipBuffers &buffers, bool swap_rb,
+                           hipStream_t stream) {
+  const int k = mip_kernel_index(mode, comps, filter);
+  if (k < 0) return hipErrorInvalidValue;
+  return launch_mip_kernel(kMipKernels[k], pass, buffers, swap_rb, stream);
 }
 
 const char *mip_kernel_name(int mode, int comps, int filter) { return mip_kernel_form(mode, comps, filter).name; }

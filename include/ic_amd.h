@@ -1213,6 +1213,77 @@ int icamd_encode_bc6h_modes_device(int codec, int bc6h_modes, int src_channels, 
                                    const void *d_src, void *d_dst, void *hip_stream);
 const char *icamd_bc6h_modes_kernel_name(int codec, int src_channels, int bc6h_modes);
 
+/* ---- half-float pixel pyramid (EXTENSION: levels 1 .. levels-1 of RGB16F / RGBA16F images) ----
+ * What icamd_mip_pyramid_device is for 8-bit pixels, for pixels of src_channels (3 or 4) binary16 samples, given and written as
+ * bit patterns: rows of level l are tight (w_l * src_channels * 2 bytes), levels 1 .. levels-1 sit back to back, image i at
+ * d_dst + i * dst_image_stride_bytes.  Geometry, cascade and odd-size rule are that entry point's: h_l = max(1, h >> l), pixel
+ * (x, y) of level l + 1 from rows 2 y and min(2 y + 1, h_l - 1) and columns 2 x and min(2 x + 1, w_l - 1) of level l, each level
+ * made from the ROUNDED level above.  It filters linear light: there is no filter argument, and all src_channels samples of a
+ * pixel (alpha too) are treated alike.
+ * The filter, per sample, from the four samples p0 .. p3 above it -- exact integer arithmetic on the 16-bit patterns:
+ *   Clean.  Let m = h & 0x7FFF.  If m > 0x7C00 (NaN), h := 0.  If m == 0x7C00 (+-Inf), h := (h & 0x8000) | 0x7BFF.
+ *   Fixed point.  Let e = (h >> 10) & 31 and f = h & 1023.  F(h) = +-(e == 0 ? f : (1024 + f) << (e - 1)): the value in units
+ *     of 2^-24, below 2^40 in magnitude.
+ *   Sum and shift.  S = F(p0) + F(p1) + F(p2) + F(p3) in 64 bits (|S| < 2^42), A = |S|, n = the bit length of A,
+ *     s = max(2, n - 11).
+ *   Round.  q = A >> s, rem = A & (2^s - 1); add 1 to q if rem > 2^(s-1), or if rem == 2^(s-1) and q is odd (nearest even).
+ *   Output.  M = ((s - 2) << 10) + q; a carry of q into 2048 runs into the exponent, and M never exceeds 0x7BFF.  M == 0
+ *     (S == 0, or an |S| of at most 2 units that rounds to nothing) gives 0x0000: -0 is never written.  Otherwise M, with
+ *     | 0x8000 if S < 0.
+ * That is the half nearest to the mean of the four cleaned values, ties to even.
+ *   Example: (0x3C00, 0x3C00, 0x3C01, 0x3C01) gives 0x3C00 and (0x3C01, 0x3C01, 0x3C02, 0x3C02) gives 0x3C02 (ties);
+ *     (0x7C00, 0x7C00, 0x7C00, 0x7C00) gives 0x7BFF; (0x3C00, 0xBC00, 0x0001, 0x8001) gives 0x0000.
+ * Statuses: ICAMD_ERR_ARG for src_channels other than 3 or 4; ICAMD_FALSE for null pointers or an empty image; ICAMD_ERR_ARG
+ * for levels of 0 or more than L_max, a row stride smaller than a row, (n_images > 1) image strides smaller than an image / a
+ * pyramid, or an odd d_src, d_dst, row_stride_bytes or image stride (samples are 2-byte aligned; no wider alignment is assumed);
+ * ICAMD_OK for n_images == 0.  Then ICAMD_ERR_NO_DEVICE without a GPU.  levels == 1 writes nothing.  No allocation, no
+ * synchronisation.  One launch per six levels (seven where the pass's input level is at most 128 x 128). */
+int icamd_mip_pyramid_f16_device(int src_channels, uint32_t height, uint32_t width, uint32_t row_stride_bytes,
+                                 uint32_t levels, uint32_t n_images, size_t src_image_stride_bytes,
+                                 size_t dst_image_stride_bytes, const void *d_src, void *d_dst, void *hip_stream);
+/* Name of the __global__ kernel; "" unless src_channels is 3 or 4. */
+const char *icamd_mip_f16_kernel_name(int src_channels);
+
+/* ---- mip chains of BC7 and BC6H (EXTENSION: ICAMD_BC7, ICAMD_BC6H_UF16, ICAMD_BC6H_SF16) ----
+ * The mip entry points of the mip-chain section keep refusing these codecs (ICAMD_ERR_ARG, sizes 0); these are their chains.
+ * Geometry, cascade, level sizes and packing are those of icamd_encode_mips_device.  P_l is what the pixel-pyramid entry point
+ * writes for the source: icamd_mip_pyramid_filtered_device(src_components, filter, ...) for BC7 (built unswapped: averaging is
+ * per channel, so swap_rb commutes), icamd_mip_pyramid_f16_device(src_channels, ...) for BC6H.  Level l of image i is exactly
+ * the bytes icamd_encode_bc7_device(bc7_modes, src_components, swap_rb, h_l, w_l, h_l, w_l, w_l * src_components, 1, ...), or
+ * icamd_encode_bc6h_modes_device(codec, bc6h_modes, src_channels, h_l, w_l, h_l, w_l, w_l * src_channels * 2, 1, ...), writes
+ * for P_l (P_0: the source with its own strides).  Levels sit back to back at the icamd_bptc_mip_chain_size offsets, largest
+ * first: the level views go straight into icamd_container_write.
+ * What runs: the pixel-pyramid kernels into the workspace, then ONE encode launch over every level of every image (per 65 535
+ * images), whose workgroups find their level in a table in the kernel argument and run the per-level kernels' code on it: the
+ * 1 + L launches of pyramid + one encode call per level become 2 (3 where the pyramid takes two passes).
+ * BC7: src_components 3 or 4, any swap_rb; filter ICAMD_MIP_FILTER_BOX or ICAMD_MIP_FILTER_SRGB with either, ALPHA_WEIGHTED and
+ * SRGB | ALPHA_WEIGHTED with 4 components; ICAMD_MIP_FILTER_NORMAL and 5..7 are ICAMD_ERR_ARG.  BC6H: src_channels 3 or 4;
+ * no filter argument (the data is linear light).
+ * Workspace: the whole pixel pyramid of every image (levels 1 .. levels-1, tight rows), 0 for levels == 1, where d_workspace
+ * may be NULL.  For BC6H d_workspace must be 2-byte aligned, as d_src, row_stride_bytes and src_image_stride_bytes.
+ * Statuses, in this order, all before a device is touched: ICAMD_FALSE for null pointers or an empty image; ICAMD_ERR_ARG for
+ * a codec, modes, components / channels or a filter outside the rules; ICAMD_ERR_ARG for levels of 0 or more than L_max, a
+ * row stride smaller than a row, (n_images > 1) image strides smaller than an image / a chain, a workspace smaller than
+ * icamd_bptc_mip_workspace_size, or BC6H's odd pointers and strides; ICAMD_OK for n_images == 0.  Then ICAMD_ERR_NO_DEVICE
+ * without a GPU.  No allocation, no synchronisation: it can be captured on one stream. */
+/* Bytes of one image's chain; fills level_offsets[0 .. levels] when non-NULL.  0 for every other codec, an empty image or
+ * levels outside 1 .. L_max. */
+size_t icamd_bptc_mip_chain_size(int codec, uint32_t height, uint32_t width, uint32_t levels, size_t *level_offsets);
+/* src_channels: bytes (BC7) or halves (BC6H) per source pixel.  0 also for arguments the encode refuses. */
+size_t icamd_bptc_mip_workspace_size(int codec, int src_channels, uint32_t height, uint32_t width, uint32_t levels,
+                                     uint32_t n_images);
+int icamd_encode_bc7_mips_device(int bc7_modes, int src_components, int swap_rb, int filter, uint32_t height, uint32_t width,
+                                 uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                                 size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src, void *d_dst,
+                                 void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int icamd_encode_bc6h_mips_device(int codec, int bc6h_modes, int src_channels, uint32_t height, uint32_t width,
+                                  uint32_t row_stride_bytes, uint32_t levels, uint32_t n_images,
+                                  size_t src_image_stride_bytes, size_t dst_image_stride_bytes, const void *d_src, void *d_dst,
+                                  void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* Name of the __global__ kernel of the encode launch: modes is ICAMD_BC7_MODES_* / ICAMD_BC6H_MODES_*; "" for combinations
+ * the encode refuses. */
+const char *icamd_bptc_mip_kernel_name(int codec, int src_channels, int modes);
+
 /* ---- runtime ---- */
 int icamd_device_count(void);             /* HIP devices visible; 0 if none */
 const char *icamd_last_error(void);       /* thread-local message for the last negative status */
