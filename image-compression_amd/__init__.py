@@ -80,6 +80,11 @@ BC6H_UF16, BC6H_SF16 = 34, 35
 # writes (mode field 00011); EXTENDED = one fused kernel that also fits one two-subset candidate per block and writes it where
 # it is strictly closer in the t domain.
 BC6H_MODES_DEFAULT, BC6H_MODES_EXTENDED = 0, 1
+# EXTENSIONS (include/ic_amd.h ICAMD_BC1A, ICAMD_BC2): BC1 with punch-through alpha (8 bytes per block; a texel is transparent iff
+# its alpha is < 128, fully opaque blocks are the DXT1 bytes, the others a stated three-colour search) and BC2 (16 bytes: sixteen
+# 4-bit alphas, then DXT5's colour block), both from RGBA8 sources and decoded to RGBA8 as the formats define.
+# encode_device / decode_device / measure_error_device / encode_batch_sharded_device / containers only (38 and up are unassigned)
+BC1A, BC2 = 36, 37
 OK, FALSE = 0, 1
 
 EXPORTS = abi.EXPORTS  # every function of include/ic_amd.h; the prototypes live in abi.py
@@ -308,7 +313,7 @@ def compress_host(compressor, fmt, buffer, height, width, *, padding_bytes_per_r
 def decode_device(codec, blocks, height, width, *, swap_rb=False, padding_bytes_per_row=0, n_images=1, stream=None):
     _assert_u8_cuda(blocks)
     # BC4 and EAC_R11 -> R8, BC5 and EAC_RG11 -> RG8
-    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, ETC2_RGB8A1: 4, BC7: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
+    comps = {DXT5: 4, PVRTC2: 4, PVRTC4: 4, ETC2_RGBA8: 4, ETC2_RGB8A1: 4, BC7: 4, BC1A: 4, BC2: 4, BC4: 1, BC5: 2, EAC_R11: 1, EAC_RG11: 2}.get(codec, 3)
     per_out = height * (width * comps + padding_bytes_per_row)
     per_in = encoded_size(codec, height, width)
     out = torch.zeros((n_images, per_out), dtype=torch.uint8, device=blocks.device)

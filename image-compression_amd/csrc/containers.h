@@ -8,6 +8,8 @@
 //             the legacy header has no code for ETC1 or PVRTC); BC7: FOURCC "DX10" followed by the 20-byte DDS_HEADER_DXT10
 //             (dxgiFormat 98 = DXGI_FORMAT_BC7_UNORM, resourceDimension 3 = TEXTURE2D, miscFlag 0, arraySize 1, miscFlags2 0);
 //             BC6H: the same two headers with dxgiFormat 95 = DXGI_FORMAT_BC6H_UF16 / 96 = DXGI_FORMAT_BC6H_SF16;
+//             BC1A: FOURCC DXT1 with ddspf.dwFlags = DDPF_FOURCC | DDPF_ALPHAPIXELS (0x5), the one field in which its header
+//             differs from DXT1's; BC2: FOURCC DXT3;
 //   * KTX  -- KTX 1.1: 12-byte identifier, 13 little-endian uint32 fields, then per mip level uint32 imageSize + data
 //             (glInternalFormat: COMPRESSED_RGB_S3TC_DXT1_EXT 0x83F0, COMPRESSED_RGBA_S3TC_DXT5_EXT 0x83F3,
 //             ETC1_RGB8_OES 0x8D64, COMPRESSED_RGBA_PVRTC_2BPPV1_IMG 0x8C03, COMPRESSED_RED_RGTC1 0x8DBB with base format
@@ -15,13 +17,15 @@
 //             COMPRESSED_R11_EAC 0x9270 with GL_RED, COMPRESSED_RG11_EAC 0x9272 with GL_RG,
 //             COMPRESSED_SIGNED_R11_EAC 0x9271 with GL_RED, COMPRESSED_SIGNED_RG11_EAC 0x9273 with GL_RG,
 //             COMPRESSED_RGB8_PUNCHTHROUGH_ALPHA1_ETC2 0x9276 with GL_RGBA, COMPRESSED_RGBA_BPTC_UNORM 0x8E8C with GL_RGBA,
-//             COMPRESSED_RGB_BPTC_UNSIGNED_FLOAT 0x8E8F and COMPRESSED_RGB_BPTC_SIGNED_FLOAT 0x8E8E with GL_RGB);
+//             COMPRESSED_RGB_BPTC_UNSIGNED_FLOAT 0x8E8F and COMPRESSED_RGB_BPTC_SIGNED_FLOAT 0x8E8E with GL_RGB,
+//             COMPRESSED_RGBA_S3TC_DXT1_EXT 0x83F1 (BC1A) and COMPRESSED_RGBA_S3TC_DXT3_EXT 0x83F2 (BC2) with GL_RGBA);
 //   * PKM  -- 16-byte big-endian header, exactly one level: "PKM 10" with type 0 for ETC1, "PKM 20" with type 3
 //             (ETC2_RGBA_NO_MIPMAPS) for ETC2 RGBA8, type 4 (ETC2_RGBA1_NO_MIPMAPS) for ETC2 RGB8A1, type 5 / 6 (ETC2_R /
 //             ETC2_RG _NO_MIPMAPS) for EAC R11 / RG11, type 7 / 8 (ETC2_R_SIGNED / ETC2_RG_SIGNED _NO_MIPMAPS) for the signed two;
 //   * PVR  -- PVR v3: 52-byte little-endian header (pixel format 1 = PVRTC 2bpp RGBA, 6 = ETC1, 7 = DXT1, 11 = DXT5,
-//             12 = BC4, 13 = BC5, 15 = BC7, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11; signed EAC R11 / RG11 are
-//             formats 25 / 26 with the channel-type field 1, signed byte normalised, where every other codec has 0),
+//             9 = DXT3 (BC2), 12 = BC4, 13 = BC5, 15 = BC7, 23 = ETC2 RGBA, 24 = ETC2 RGB A1, 25 = EAC R11, 26 = EAC RG11; signed EAC R11 / RG11 are
+//             formats 25 / 26 with the channel-type field 1, signed byte normalised, where every other codec has 0; PVR has
+//             ONE DXT1 code: BC1A is format 7 like DXT1, the reader finds the transparent index in the blocks),
 //             no metadata, levels follow largest first.  PVRTC data is stored in the Z-order the encoder already
 //             produces (pvrtc_compressor.cc:551-580).
 // Mip level l of an h x w texture is max(1, h >> l) x max(1, w >> l) pixels; its block stream is what
@@ -50,6 +54,7 @@ inline void put_be16(uint8_t *p, uint32_t v) {
 }
 
 inline bool container_bc6h(int codec) { return codec == ICAMD_BC6H_UF16 || codec == ICAMD_BC6H_SF16; }
+inline bool container_bc1a_bc2(int codec) { return codec == ICAMD_BC1A || codec == ICAMD_BC2; }  // DDS, KTX, PVR; no PKM
 
 inline size_t container_header_size(int container, int codec) {
   switch (container) {
@@ -65,7 +70,7 @@ inline bool container_supports(int container, int codec) {
   switch (container) {
     case ICAMD_CONTAINER_DDS:
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_BC7 ||
-             container_bc6h(codec);
+             container_bc6h(codec) || container_bc1a_bc2(codec);
     case ICAMD_CONTAINER_KTX:
       if (container_bc6h(codec)) return true;  // (BC6H: DDS and KTX only)
       [[fallthrough]];
@@ -73,7 +78,7 @@ inline bool container_supports(int container, int codec) {
       return codec == ICAMD_DXT1 || codec == ICAMD_DXT5 || codec == ICAMD_ETC1 || codec == ICAMD_PVRTC2 || codec == ICAMD_BC4 ||
              codec == ICAMD_BC5 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
              codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
-             codec == ICAMD_EAC_SIGNED_RG11 || codec == ICAMD_BC7;
+             codec == ICAMD_EAC_SIGNED_RG11 || codec == ICAMD_BC7 || container_bc1a_bc2(codec);
     case ICAMD_CONTAINER_PKM:
       return codec == ICAMD_ETC1 || codec == ICAMD_ETC2_RGBA8 || codec == ICAMD_ETC2_RGB8 || codec == ICAMD_EAC_R11 ||
              codec == ICAMD_EAC_RG11 || codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_EAC_SIGNED_R11 ||
@@ -110,9 +115,9 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
       put_le32(out + 20, (uint32_t)level0_bytes);                                        // dwPitchOrLinearSize
       put_le32(out + 28, levels);                                                        // dwMipMapCount
       put_le32(out + 76, 32);                                                            // ddspf.dwSize
-      put_le32(out + 80, 0x4u);                                                          // DDPF_FOURCC
-      memcpy(out + 84, codec == ICAMD_DXT1 ? "DXT1" : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1"
-                       : codec == ICAMD_BC5 ? "ATI2" : "DX10", 4);
+      put_le32(out + 80, codec == ICAMD_BC1A ? 0x4u | 0x1u : 0x4u);                      // DDPF_FOURCC [| DDPF_ALPHAPIXELS: BC1A]
+      memcpy(out + 84, (codec == ICAMD_DXT1 || codec == ICAMD_BC1A) ? "DXT1" : codec == ICAMD_BC2 ? "DXT3"
+                       : codec == ICAMD_DXT5 ? "DXT5" : codec == ICAMD_BC4 ? "ATI1" : codec == ICAMD_BC5 ? "ATI2" : "DX10", 4);
       put_le32(out + 108, 0x1000u | (levels > 1 ? 0x8u | 0x400000u : 0u));               // DDSCAPS_TEXTURE [COMPLEX MIPMAP]
       if (codec == ICAMD_BC7 || container_bc6h(codec)) {  // DDS_HEADER_DXT10
         // dxgiFormat: DXGI_FORMAT_BC7_UNORM, DXGI_FORMAT_BC6H_UF16, DXGI_FORMAT_BC6H_SF16
@@ -137,12 +142,13 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
                                 : codec == ICAMD_EAC_R11 ? 0x9270u : codec == ICAMD_EAC_RG11 ? 0x9272u
                                 : codec == ICAMD_EAC_SIGNED_R11 ? 0x9271u : codec == ICAMD_EAC_SIGNED_RG11 ? 0x9273u
                                 : codec == ICAMD_ETC2_RGB8A1 ? 0x9276u : codec == ICAMD_BC7 ? 0x8E8Cu
-                                : codec == ICAMD_BC6H_UF16 ? 0x8E8Fu : codec == ICAMD_BC6H_SF16 ? 0x8E8Eu : 0x8C03u;
+                                : codec == ICAMD_BC6H_UF16 ? 0x8E8Fu : codec == ICAMD_BC6H_SF16 ? 0x8E8Eu
+                                : codec == ICAMD_BC1A ? 0x83F1u : codec == ICAMD_BC2 ? 0x83F2u : 0x8C03u;
       put_le32(out + 28, internal);
       const uint32_t base = (codec == ICAMD_BC4 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_SIGNED_R11) ? 0x1903u     // GL_RED
                             : (codec == ICAMD_BC5 || codec == ICAMD_EAC_RG11 || codec == ICAMD_EAC_SIGNED_RG11) ? 0x8227u  // GL_RG
                             : (codec == ICAMD_DXT5 || codec == ICAMD_PVRTC2 || codec == ICAMD_ETC2_RGBA8 ||
-                               codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_BC7) ? 0x1908u : 0x1907u;                           // GL_RGBA / GL_RGB
+                               codec == ICAMD_ETC2_RGB8A1 || codec == ICAMD_BC7 || container_bc1a_bc2(codec)) ? 0x1908u : 0x1907u;                         // GL_RGBA / GL_RGB
       put_le32(out + 32, base);
       put_le32(out + 36, width);
       put_le32(out + 40, height);
@@ -168,7 +174,8 @@ inline void container_write_header(int container, int codec, uint32_t height, ui
     case ICAMD_CONTAINER_PVR: {
       put_le32(out, 0x03525650u);  // "PVR\3"
       put_le32(out + 4, 0);        // flags
-      put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : codec == ICAMD_DXT1 ? 7u
+      put_le64(out + 8, codec == ICAMD_PVRTC2 ? 1u : codec == ICAMD_ETC1 ? 6u : (codec == ICAMD_DXT1 || codec == ICAMD_BC1A) ? 7u
+                        : codec == ICAMD_BC2 ? 9u
                         : codec == ICAMD_BC4 ? 12u : codec == ICAMD_BC5 ? 13u : codec == ICAMD_BC7 ? 15u
                         : codec == ICAMD_ETC2_RGBA8 ? 23u
                         : codec == ICAMD_ETC2_RGB8 ? 22u : codec == ICAMD_ETC2_RGB8A1 ? 24u

@@ -1,6 +1,8 @@
 // decode_kernels.hip -- DXT1 / DXT5 / ETC1 decode kernels for gfx950 ("next" row 8f.1): one block per
 // lane, 8/16-byte coalesced block loads, 12/16-byte row-segment stores (Compressor4x4Helper::Decompress,
-// internal/compressor4x4_helper.h:218-262: blocks past the image edge are clipped).
+// internal/compressor4x4_helper.h:218-262: blocks past the image edge are clipped).  BC1A and BC2 (extensions, bc1a_block.h)
+// decode here too, to RGBA8 rows.
+#include "bc1a_block.h"      // decode_bc1a, decode_bc2
 #include "blockops_block.h"  // decode_block.h + the palette-plane row decoders
 #include "codec_info.h"
 #include "ic_launch.h"
@@ -59,7 +61,50 @@ __device__ __forceinline__ void decode_one(const DecodeParams &P, uint32_t k) {
   }
 }
 
+// BC1A (8-byte blocks) and BC2 (16-byte blocks) as the formats define them (bc1a_block.h): four 16-byte row stores (RGBA8),
+// clipped at the image's edge.
+template <int CODEC>
+__device__ __forceinline__ void bc1a_bc2_decode_one(const DecodeParams &P, uint32_t k) {
+  const auto [img, rem, brow, bcol] = raster_block(P, k);
+  const uint8_t *src = P.blocks + (size_t)img * P.src_image_stride + (size_t)rem * codec_block_bytes(CODEC);
+  uint32_t px[16];
+  if (CODEC == ICAMD_BC2) {
+    const U4 v = load_stream(reinterpret_cast<const U4 *>(src));  // no alignment assumed: the caller owns the block pointer
+    const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+    decode_bc2(w, P.swap_rb != 0u, px);
+  } else {
+    const U2 v = load_stream(reinterpret_cast<const U2 *>(src));
+    decode_bc1a(v.x, v.y, P.swap_rb != 0u, px);
+  }
+  uint8_t *dst = P.pixels + (size_t)img * P.dst_image_stride;
+  const uint32_t row = brow * 4u, col = bcol * 4u;
+  if (row + 4u <= P.height && col + 4u <= P.width) {
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+      store_stream16(dst + (size_t)(row + y) * P.row_stride + (size_t)col * 4u, px[4 * y], px[4 * y + 1], px[4 * y + 2],
+                     px[4 * y + 3]);
+  } else {  // clipped at the image's edge, pixel by pixel
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (row + y < P.height && col + x < P.width) {
+          uint8_t *q = dst + (size_t)(row + y) * P.row_stride + (size_t)(col + x) * 4u;
+          const uint32_t p = px[4 * y + x];
+          q[0] = (uint8_t)p; q[1] = (uint8_t)(p >> 8); q[2] = (uint8_t)(p >> 16); q[3] = (uint8_t)(p >> 24);
+        }
+  }
+}
+
 extern "C" {
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc1a_decode_kernel(DecodeParams P) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k < P.total_blocks) bc1a_bc2_decode_one<ICAMD_BC1A>(P, k);
+}
+__global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_bc2_decode_kernel(DecodeParams P) {
+  const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
+  if (k < P.total_blocks) bc1a_bc2_decode_one<ICAMD_BC2>(P, k);
+}
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_dxt1_decode_kernel(DecodeParams P) {
   const uint32_t k = blockIdx.x * kThreadsPerWorkgroup + threadIdx.x;
   if (k < P.total_blocks) decode_one<ICAMD_DXT1>(P, k);
@@ -181,6 +226,8 @@ hipError_t launch_decode(int codec, const DecodeParams &P, hipStream_t stream) {
   if (codec == ICAMD_DXT1) kernel = icamd_dxt1_decode_kernel;
   else if (codec == ICAMD_DXT5) kernel = icamd_dxt5_decode_kernel;
   else if (codec == ICAMD_ETC1) kernel = icamd_etc1_decode_kernel;
+  else if (codec == ICAMD_BC1A) kernel = icamd_bc1a_decode_kernel;
+  else if (codec == ICAMD_BC2) kernel = icamd_bc2_decode_kernel;
   else if (codec == ICAMD_PVRTC2) kernel = tiles ? icamd_pvrtc2_decode_tile_kernel : icamd_pvrtc2_decode_kernel;
   else if (codec == ICAMD_PVRTC4) kernel = tiles ? icamd_pvrtc4_decode_tile_kernel : icamd_pvrtc4_decode_kernel;
   else return hipErrorInvalidValue;

@@ -220,12 +220,12 @@ bool resolve_codec(int compressor, int format, int *codec, int *comps = nullptr,
 }
 
 // Which source component counts a codec encodes from (icamd_encode_device): DXT1 / ETC1 / ETC2 RGB8 3 or 4, DXT5 / ETC2 RGBA8 /
-// ETC2 RGB8A1 4,
+// ETC2 RGB8A1 / BC1A / BC2 4,
 // BC4 and EAC R11 1..4, BC5 and EAC RG11 2..4, BC7 3 or 4.
 bool codec_accepts_components(int codec, int comps) {
   switch (codec) {
     case ICAMD_DXT1: case ICAMD_ETC1: case ICAMD_ETC2_RGB8: case ICAMD_BC7: return comps == 3 || comps == 4;
-    case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: case ICAMD_ETC2_RGB8A1: return comps == 4;
+    case ICAMD_DXT5: case ICAMD_ETC2_RGBA8: case ICAMD_ETC2_RGB8A1: case ICAMD_BC1A: case ICAMD_BC2: return comps == 4;
     case ICAMD_BC4: case ICAMD_EAC_R11: return comps >= 1 && comps <= 4;
     case ICAMD_BC5: case ICAMD_EAC_RG11: return comps >= 2 && comps <= 4;
   }
@@ -234,6 +234,8 @@ bool codec_accepts_components(int codec, int comps) {
 // The one- and two-channel codecs (R, or R and G, of 1..4-byte pixels; R8 / RG8 rows out): BC4 / BC5 and EAC R11 / RG11.
 bool plane_codec(int codec) { return codec == ICAMD_BC4 || codec == ICAMD_BC5 || codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
 bool eac11_codec(int codec) { return codec == ICAMD_EAC_R11 || codec == ICAMD_EAC_RG11; }
+// BC1 with punch-through alpha and BC2 (EXTENSIONS, include/ic_amd.h ICAMD_BC1A): RGBA8 in, RGBA8 rows out
+bool bc1a_bc2_codec(int codec) { return codec == ICAMD_BC1A || codec == ICAMD_BC2; }
 
 // The sizes PvrtcCompressor::Compress accepts (pvrtc.cc:636-650): a square power of two of at least 8 x 8 (for a square
 // power of two, width % 8 == 0 && height % 4 == 0 is width >= 8).  The reference sizes its output with the uint32 product
@@ -492,6 +494,7 @@ const char *icamd_kernel_name(int codec, int src_components) {
     case ICAMD_BC4: case ICAMD_BC5: return icamd::bc45_kernel_name(codec, src_components);
     case ICAMD_EAC_R11: case ICAMD_EAC_RG11: return icamd::eac11_kernel_name(codec, src_components);
     case ICAMD_BC7: return icamd::bc7_kernel_name(src_components);
+    case ICAMD_BC1A: case ICAMD_BC2: return icamd::bc1a_bc2_kernel_name(codec, src_components);
   }
   return "";
 }
@@ -529,6 +532,9 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
   if (plane_codec(codec))
     return plane_encode_device_impl(codec, src_components, swap_rb, height, width, grid_height, grid_width, row_stride_bytes,
                                     n_images, src_image_stride_bytes, dst_image_stride_bytes, d_src, d_dst, stream);
+  // EXTENSIONS (include/ic_amd.h ICAMD_BC1A, ICAMD_BC2): the transparency rule and the alpha word need the fourth byte
+  if (codec == ICAMD_BC1A && src_components != 4) return fail(ICAMD_ERR_ARG, "BC1A needs a 4-component source");
+  if (codec == ICAMD_BC2 && src_components != 4) return fail(ICAMD_ERR_ARG, "BC2 needs a 4-component source");
   if (src_components != 3 && src_components != 4) return fail(ICAMD_ERR_ARG, "src_components must be 3 or 4");
   // EXTENSION (include/ic_amd.h ICAMD_ETC2_RGBA8): the alpha half needs the fourth byte; checked before any device work
   if (codec == ICAMD_ETC2_RGBA8 && src_components != 4) return fail(ICAMD_ERR_ARG, "ETC2 RGBA8 needs a 4-component source");
@@ -541,7 +547,7 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     return pvrtc_encode_device_impl(codec, src_components, height, width, row_stride_bytes, n_images, src_image_stride_bytes,
                                     dst_image_stride_bytes, d_src, d_dst, stream, false);
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
-      codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7)
+      codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7 && !bc1a_bc2_codec(codec))
     return fail(ICAMD_ERR_ARG, "unknown codec");
   if (!codec_accepts_components(codec, src_components)) return fail(ICAMD_ERR_ARG, "DXT5 needs a 4-component source");
   if (row_stride_bytes < width * (uint32_t)src_components) return fail(ICAMD_ERR_ARG, "row stride smaller than a row");
@@ -558,6 +564,8 @@ int icamd_encode_device(int codec, int etc_strategy, int src_components, int swa
     ICAMD_HIP(icamd::launch_etc2_a1(P, stream), "launch etc2 rgb8a1");
   else if (codec == ICAMD_BC7)  // EXTENSION (include/ic_amd.h ICAMD_BC7): mode 6 from 3- or 4-component sources
     ICAMD_HIP(icamd::launch_bc7_encode(src_components, P, stream), "launch bc7");
+  else if (bc1a_bc2_codec(codec))
+    ICAMD_HIP(icamd::launch_bc1a_bc2_encode(codec, P, stream), codec == ICAMD_BC2 ? "launch bc2" : "launch bc1a");
   else
     ICAMD_HIP(icamd::launch_dxt(codec, src_components, P, stream), "launch dxt");
   return ICAMD_OK;
@@ -588,7 +596,7 @@ int icamd_encode_etc2_device(int codec, int etc_strategy, int etc2_modes, int sr
 } ICAMD_ABI_CATCH
 
 const char *icamd_etc2_kernel_name(int codec, int src_components, int etc2_modes) {
-  if (codec == ICAMD_BC7) return "";  // (as for an unknown codec: not an ETC2-family codec, include/ic_amd.h ICAMD_BC7)
+  if (codec == ICAMD_BC7 || bc1a_bc2_codec(codec)) return "";  // (as for an unknown codec: not ETC2-family codecs, include/ic_amd.h ICAMD_BC7)
   if (etc2_modes == ICAMD_ETC2_MODES_DEFAULT) return icamd_kernel_name(codec, src_components);
   if (etc2_modes == ICAMD_ETC2_MODES_TH && codec == ICAMD_ETC2_RGB8) return icamd::etc2_th_kernel_name(src_components);
   return "";
@@ -668,7 +676,7 @@ int icamd_encode_etc2_colour_device(int codec, int etc_strategy, int colour_mode
 } ICAMD_ABI_CATCH
 
 const char *icamd_etc2_colour_kernel_name(int codec, int src_components, int colour_modes) {
-  if (codec == ICAMD_BC7) return "";  // (as for an unknown codec)
+  if (codec == ICAMD_BC7 || bc1a_bc2_codec(codec)) return "";  // (as for an unknown codec)
   if (colour_modes == ICAMD_ETC2_COLOUR_DEFAULT) return icamd_kernel_name(codec, src_components);
   if ((colour_modes != ICAMD_ETC2_COLOUR_PLANAR && colour_modes != ICAMD_ETC2_COLOUR_PLANAR_TH) ||
       !etc2_colour_accepts(codec, src_components))
@@ -901,7 +909,8 @@ int icamd_decode_device(int codec, int swap_rb, uint32_t height, uint32_t width,
   if (!d_blocks || !d_pixels || height == 0 || width == 0) return ICAMD_FALSE;
   const bool plane = plane_codec(codec);  // (BC4 / BC5 and EAC R11 / RG11: R8 / RG8 rows)
   if (codec != ICAMD_DXT1 && codec != ICAMD_DXT5 && codec != ICAMD_ETC1 && codec != ICAMD_PVRTC2 && codec != ICAMD_PVRTC4 &&
-      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7 && !plane)
+      codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 && codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_BC7 &&
+      !bc1a_bc2_codec(codec) && !plane)
     return ICAMD_FALSE;
   if (plane && swap_rb) return fail(ICAMD_ERR_ARG, eac11_codec(codec) ? "EAC R11 / RG11 decode: swap_rb must be 0" : "BC4 / BC5 decode: swap_rb must be 0");
   if (n_images == 0) return ICAMD_OK;
@@ -1753,7 +1762,7 @@ int icamd_container_write(int container, int codec, uint32_t height, uint32_t wi
   if (container < ICAMD_CONTAINER_DDS || container > ICAMD_CONTAINER_PVR) return fail(ICAMD_ERR_ARG, "unknown container");
   if (codec < ICAMD_DXT1 || (codec > ICAMD_PVRTC2 && !plane_codec(codec) && codec != ICAMD_ETC2_RGBA8 && codec != ICAMD_ETC2_RGB8 &&
                              codec != ICAMD_ETC2_RGB8A1 && codec != ICAMD_EAC_SIGNED_R11 && codec != ICAMD_EAC_SIGNED_RG11 &&
-                             codec != ICAMD_BC7 && codec != ICAMD_BC6H_UF16 && codec != ICAMD_BC6H_SF16))
+                             codec != ICAMD_BC7 && codec != ICAMD_BC6H_UF16 && codec != ICAMD_BC6H_SF16 && !bc1a_bc2_codec(codec)))
     return fail(ICAMD_ERR_ARG, "unknown codec");  // (PVRTC4 has no container code)
   if (!level_data || !level_sizes || !out) return ICAMD_FALSE;
   const size_t need = icamd_container_size(container, codec, height, width, levels);

@@ -263,6 +263,10 @@ const char *bc7_kernel_name(int comps);  // "" unless comps is 3 or 4
 // ICAMD_BC7_MODES_EXTENDED): one fused kernel in place of launch_bc7_encode's, the same GridParams.
 hipError_t launch_bc7_modes_encode(int comps, const GridParams &P, hipStream_t stream);
 const char *bc7_modes_kernel_name(int comps);  // "" unless comps is 3 or 4
+// BC1A / BC2 (extensions, bc1a_bc2_kernels.hip): codec ICAMD_BC1A / ICAMD_BC2.  Encode: GridParams as for DXT5 (etc_strategy is
+// not read), RGBA8 sources only.  The decode kernels (RGBA8 rows) are launch_decode's, the metric kernels launch_metric's.
+hipError_t launch_bc1a_bc2_encode(int codec, const GridParams &P, hipStream_t stream);
+const char *bc1a_bc2_kernel_name(int codec, int comps);  // "" unless comps == 4
 // BC6H (extension, bc6h_kernels.hip; icamd_encode_bc6h_device): codec ICAMD_BC6H_UF16 / ICAMD_BC6H_SF16, chans = halves per source
 // pixel, 3 or 4.  Encode (mode field 00011): GridParams (swap_rb, etc_strategy and force_gather are not read: addresses are 64-bit
 // per lane).  Decode (all fourteen modes): DecodeParams as launch_decode (swap_rb is not read), RGBA16F rows.  Metric: MetricParams

@@ -14,6 +14,7 @@
 #ifndef ICAMD_METRIC_BLOCK_H_
 #define ICAMD_METRIC_BLOCK_H_
 
+#include "bc1a_block.h"  // decode_bc1a, decode_bc2
 #include "bc45_block.h"  // blockops_block.h (decode_block_rows), decode_block.h, dxt_block.h (packed 16-bit helpers)
 #include "bc7_block.h"  // decode_bc7
 #include "eac11_block.h"  // decode_eac11
@@ -167,6 +168,27 @@ ICAMD_DEV void metric_etc2_a1_block(const uint32_t *w, bool swap, const uint8_t 
   uint32_t S[16], D[16];
   load_block<4>(img, h, wd, stride, row, col, S, wide_ok);
   decode_etc2_a1(w[0], w[1], swap, D);
+  if (row + 4 > h || col + 4 > wd) {
+    ICAMD_UNROLL
+    for (int y = 0; y < 4; ++y)
+      ICAMD_UNROLL
+      for (int x = 0; x < 4; ++x)
+        if (row + (uint32_t)y >= h || col + (uint32_t)x >= wd) S[4 * y + x] = D[4 * y + x];
+  }
+  ICAMD_UNROLL
+  for (int y = 0; y < 4; ++y) metric_row4<4>(&S[4 * y], &D[4 * y], a);
+}
+
+// BC1A (w[0..1]) or BC2 (w[0..3]) block (EXTENSIONS, bc1a_block.h) against the RGBA8 source pixels, four channels, with the
+// decoders' own math (decode_bc1a / decode_bc2, swap included: a transparent BC1A texel is (0, 0, 0, 0), a BC2 alpha is
+// nibble x 17); a pixel outside the image compares with itself.  PRECONDITION row < h, col < wd.
+template <bool BC2>
+ICAMD_DEV void metric_bc1a_bc2_block(const uint32_t *w, bool swap, const uint8_t *img, uint32_t h, uint32_t wd, uint32_t stride,
+                                     uint32_t row, uint32_t col, bool wide_ok, MetricAcc &a) {
+  uint32_t S[16], D[16];
+  load_block<4>(img, h, wd, stride, row, col, S, wide_ok);
+  if (BC2) decode_bc2(w, swap, D);
+  else decode_bc1a(w[0], w[1], swap, D);
   if (row + 4 > h || col + 4 > wd) {
     ICAMD_UNROLL
     for (int y = 0; y < 4; ++y)

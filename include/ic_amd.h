@@ -294,7 +294,56 @@ enum { ICAMD_DXT1 = 0, ICAMD_DXT5 = 1, ICAMD_ETC1 = 2, ICAMD_PVRTC2 = 3,
         * definition and the metric are stated in full), icamd_bc6h_kernel_name, icamd_bc6h_metric_kernel_name, icamd_encoded_size
         * and the container functions (DDS with the DX10 extension header, dxgiFormat 95 / 96; KTX 0x8E8F / 0x8E8E with GL_RGB; no
         * PKM, no PVR).  Every other entry point refuses them as it refuses an unknown codec. */
-       ICAMD_BC6H_UF16 = 34, ICAMD_BC6H_SF16 = 35 };
+       ICAMD_BC6H_UF16 = 34, ICAMD_BC6H_SF16 = 35,
+       /* EXTENSIONS: BC1 with punch-through alpha ("DXT1A", COMPRESSED_RGBA_S3TC_DXT1_EXT; ICAMD_BC1A, 8 bytes per 4 x 4 block) and
+        * BC2 ("DXT3", COMPRESSED_RGBA_S3TC_DXT3_EXT; ICAMD_BC2, 16 bytes per block: the alpha word, then the colour word).  Blocks in
+        * raster order.  Values 38 and up are unassigned.  ICAMD_DXT1 and ICAMD_DXT5 are unchanged: they write and decode the bytes
+        * they always did.
+        *   Common rules.  src_components == 4 only (anything else: ICAMD_ERR_ARG); etc_strategy is ignored, as for DXT.  Grids, row
+        *       strides, image strides, batches, padded grids and edge replication as for ICAMD_DXT5: a block's sixteen texels are
+        *       the ones ICAMD_DXT5 is handed for it.  Texel p = 4 y + x; its 2-bit colour index is at bits 2p..2p+1 of the
+        *       little-endian index dword.  Canonical colour: R = byte 0 (byte 2 when swap_rb), G = byte 1, B the remaining byte.
+        *   Decode (icamd_decode_device, RGBA8 rows; with swap_rb the stored R goes to the third byte, as for ICAMD_DXT5): the
+        *       formats' own rules.  E0, E1 = the 565 colours c0, c1 widened by bit replication; blends per channel, truncating.
+        *       BC1A: c0 > c1: palette E0, E1, (2 E0 + E1) / 3, (E0 + 2 E1) / 3, alpha 255.  Otherwise -- c0 == c1 included --
+        *       E0, E1, (E0 + E1) / 2 with alpha 255, and index 3 is (0, 0, 0, 0).  (ICAMD_DXT1's decoder keeps the reference's
+        *       c0 == c1 rule and opaque black for index 3; it has no alpha channel.)
+        *       BC2: the colour word ALWAYS decodes in four-colour mode, whatever the order of c0 and c1; the alpha of texel p is
+        *       nibble p of the little-endian 64-bit alpha word (bits 4p..4p+3) times 17.
+        *   Encode, BC1A: a DEFINITION, not a heuristic.  A texel is TRANSPARENT iff its byte 3 is < 128, the rule
+        *       of ICAMD_ETC2_RGB8A1.
+        *       1. All 16 transparent: the block is 00 00 00 00 ff ff ff ff.
+        *       2. None transparent: the 8 bytes icamd_encode_device(ICAMD_DXT1, ..., 4, swap_rb, ...) writes for the block (PARITY
+        *          PINNED through ICAMD_DXT1).  Under the BC1A decoder every such block is fully opaque and decodes to the RGB it
+        *          has under the DXT1 decoder: the general path stores c0 > c1, the constant-colour path stores equal endpoints
+        *          only with index 0 and index 3 only with c0 > c1 (checked over all 2^24 colours against the constant table).
+        *       3. 1..15 transparent: three-colour mode.  Over the OPAQUE texels only, L = 4 R + 8 G + B on the canonical channels;
+        *          lo = the first opaque texel in raster order with the smallest L, hi = the first with the largest L (the DXT1
+        *          encoder's tie rules with the transparent texels left out); a = Quantize565(lo), b = Quantize565(hi) on canonical
+        *          R, G, B (Quantize8: i = v (2^n - 1) + 128, (i + (i >> 8)) >> 8); stored c0 = min(a, b), c1 = max(a, b) as
+        *          16-bit values -- they may be equal.  Palette: the decoder's, P0 = E(c0), P1 = E(c1), P2 = (P0 + P1) >> 1 per
+        *          channel.  An opaque texel takes the k in {0, 1, 2} with the smallest squared RGB distance to its canonical
+        *          colour, ties to the smallest k; a transparent texel takes 3, and the colour stored under it plays no part
+        *          anywhere.  No constant-colour table refinement and no refit in this path.
+        *       Examples.  Every texel (100, 150, 200), alpha 255 for x < 2 and 0 for x >= 2: b8 64 b8 64 f0 f0 f0 f0; columns 0 and
+        *       1 decode to (99, 150, 198, 255), columns 2 and 3 to (0, 0, 0, 0).  Every texel (200, 100, 50, 255) except texel 0 =
+        *       (10, 20, 30, 255), texel 5 = (105, 60, 40, 200) and texel 15 with alpha 127: a4 08 26 c3 54 59 55 d5; texel 0
+        *       decodes to (8, 20, 33, 255), texel 1 to (198, 101, 49, 255), texel 5 to (103, 60, 41, 255), texel 15 to (0, 0, 0, 0).
+        *       So no texel gains or loses transparency, and a fully opaque image encodes to exactly the ICAMD_DXT1 stream.
+        *   Encode, BC2: bytes 8..15 are bytes 8..15 of the block icamd_encode_device(ICAMD_DXT5, ...) writes (the always-four-colour
+        *       colour block, PARITY PINNED through ICAMD_DXT5).  Bytes 0..7 are the alpha word: nibble p = Quantize8(alpha_p, 15),
+        *       i = 15 a + 128, (i + (i >> 8)) >> 8 -- so 0 -> 0, 127 -> 7, 128 -> 8, 200 -> 12, 255 -> 15.  No has_one_pixel
+        *       special case: the gathered texels of such a block are all the corner pixel.
+        *   Metric (icamd_measure_error_device, src_components == 4): all four decoded channels against the source with the
+        *       decoders' own math, as ICAMD_ETC2_RGB8A1 and ICAMD_DXT5 -- so colour under a transparent texel counts against 0, and
+        *       a source alpha that is not 0 / 255 counts against 0 / 255 for BC1A and against nibble x 17 for BC2.
+        * Reachable through icamd_encode_device, icamd_encode_batch_sharded_device, icamd_decode_device,
+        * icamd_measure_error_device, icamd_encoded_size, icamd_kernel_name, icamd_metric_kernel_name and the container functions
+        * (BC1A: DDS FourCC DXT1 with ddspf.dwFlags = DDPF_FOURCC | DDPF_ALPHAPIXELS = 0x5, the only difference from ICAMD_DXT1's
+        * header; KTX 0x83F1 with GL_RGBA; PVR 7 -- PVR has one DXT1 code.  BC2: DDS FourCC DXT3; KTX 0x83F2 with GL_RGBA; PVR 9.
+        * No PKM) only: no Compressor + format pair selects them; every other family's entry points refuse them as they refuse an
+        * unknown codec, and icamd_mip_chain_size answers 0. */
+       ICAMD_BC1A = 36, ICAMD_BC2 = 37 };
 
 /* Status codes.  0 = the reference's `true`; 1 = the reference's `false` (argument
  * validation, unsupported format, external-storage size mismatch); < 0 = the device
